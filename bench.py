@@ -25,14 +25,21 @@ including auto-resets"): right after creation all 65 536 envs are at step 0 of t
 at once, every DistCache is cold, nobody resets -- a heavier, unrepresentative transient (measured: k_step 160 us vs 100 us; clocks and spares
 have nothing to do with it, see profiles/r02_driver_repro.txt).  A DISCLOSED pre-roll ("preroll" in the JSON: --preroll-steps untimed steps
 of the measured batch, default 1500 = 1.5 max_steps horizons -- at step 1000 the 40 % of the envs that survived their first episode hit max_steps together
-and the next few dozen steps are a second such transient, so the window must not sit on a multiple of max_steps) therefore precedes the W warm-up steps; the first K steps of that pre-roll are
-timed too and reported as "preroll.cold_start" so that the transient's own rate is on record next to `value`.
+and the next few dozen steps are a second such transient, so the window must not sit on a multiple of max_steps) therefore precedes the W warm-up steps; with --full the first K steps of that pre-roll
+are timed too and reported as "preroll.cold_start" so that the transient's own rate is on record next to `value`.
 
-Rank 0 prints ONE JSON line: the contract fields + "roofline" (dominant kernel, HIP-event timed on the launch stream,
-plus the end-to-end and per-kernel fractions and the on-box copy peak) + "workload_rates" (resets/s, descents/s,
-BFS maps/s) + "repeats" (4 further runs of K steps, median) + "extra_workloads" (the 80x24 default and nohide-symbol
-configs of SURVEY.md 8d through the same harness, short runs) + "cpu_baseline" (the C oracle on the host cores,
-bounded samples at 65 536 / 1 024 / 64 envs; N=1 only).
+Rank 0 prints ONE JSON line.  A plain run does only what `value` needs: clock-warm, pre-roll, warm-up, the K timed steps
+(no HIP-event pairs in them), the line with the contract fields.  --full adds everything else, as before: "value_cold_start"
+(the first K pre-roll steps timed), "roofline" (dominant kernel, HIP-event timed on the launch stream, plus the end-to-end and
+per-kernel fractions and the on-box copy peak) + "workload_rates" (resets/s, descents/s, BFS maps/s) + "repeats" (4 further
+runs of K steps, median) + "long_window" + "step_us" + "extra_workloads" (the 80x24 default and nohide-symbol configs of
+SURVEY.md 8d through the same harness, short runs) + "cpu_baseline" (the C oracle on the host cores, bounded samples at
+65 536 / 1 024 / 64 envs; N=1 only); with N > 1 also "strong_scaling" and the "allgather" legs.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's shard), right after the timed region:
+obs.npy (float32 [k, C, H, W]), reward.npy and done.npy (float32 [k]) of the envs of a fixed sample, drawn with numpy
+seed 0 and sorted, as many as fit in 48 MB (all of them when they do; 24 480 of the 65 536 mini envs).  The inputs are a
+function of the arguments alone (per-env seeds, action table seeded by rank), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -47,6 +54,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "rogue-gym_amd"))
 
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BYTES = 48 << 20           # --dump-outputs: at most this many bytes of obs + reward + done (the limit for a dump is 64 MB)
 KERNELS = ["k_step", "k_render", "k_obs", "k_build", "k_regen"]   # rg_timing_read_all's order; k_regen = the background generator (side stream)
 
 # --workload: the default is BASELINE.json configs[1] (the one the metric is quoted on).  The others are the larger configs of
@@ -217,6 +225,20 @@ def copy_peak(torch, dev):
     return 2.0 * n * reps / (ms * 1e-3) / 1e9
 
 
+def dump_outputs(path, obs, reward, done):
+    """--dump-outputs: the last step's (obs, reward, done) of a fixed, seeded sample of envs as float32 .npy files (module docstring)."""
+    import numpy as np
+    import torch
+
+    n = obs.shape[0]
+    k = min(n, DUMP_BYTES // (obs[0].numel() * 4 + 8))
+    idx = np.sort(np.random.RandomState(0).choice(n, k, replace=False)) if k < n else np.arange(n)
+    sel = torch.from_numpy(idx).to(obs.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("obs", obs), ("reward", reward), ("done", done)):
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, sel).to(torch.float32).cpu().numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (the reference's executor owns its workers too,
     python/src/thread_impls.rs:14-34) -- one process per GPU, rendezvous on 127.0.0.1, RCCL.  Rank 0 inherits stdout and prints the one
@@ -258,21 +280,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="mini")
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="default: the workload's own size (65 536 for mini)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also every side measurement beside `value` (module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0's shard, a fixed sample of at most 48 MB) to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline legs")
     ap.add_argument("--persistent-obs", action="store_true", help="A/B aid: the measured batch with its observation tensor bound (rg_obs_bind: in-place updates); the line then "
                     "says so in `config.workload` and is not the headline metric")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short extra_workloads runs (default / nohide-symbol)")
-    ap.add_argument("--no-repeats", action="store_true", help="skip the 4 further runs of K steps (median)")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the short extra_workloads runs (default / nohide-symbol)")
+    ap.add_argument("--no-repeats", action="store_true", help="(--full) skip the 4 further runs of K steps (median)")
     ap.add_argument("--clock-warm-s", type=float, default=1.5, help="untimed fixed-duration stepping of a SCRATCH batch before anything else (0 = off)")
     ap.add_argument("--preroll-steps", type=int, default=1500, help="untimed steps of the MEASURED batch before the warm-up: reach the steady-state episode mix "
-                    "the metric is defined on (the first --steps of them are timed and reported as preroll.cold_start); 0 = off.  1.5 x max_steps: "
+                    "the metric is defined on (with --full the first --steps of them are timed and reported as preroll.cold_start); 0 = off.  1.5 x max_steps: "
                     "not on a multiple of max_steps, where the survivors of the synchronised first episodes all reset at once")
-    ap.add_argument("--time-every", type=int, default=0, help="time every N-th launch of each kernel with a HIP-event pair (default: every 7th; every 5th when steps < 64, every one when < 16); odd on purpose: "
-                    "an even stride could lock onto a period of the workload")
-    ap.add_argument("--gather-steps", type=int, default=50, help="extra steps timed WITH the observation all-gather (N>1)")
+    ap.add_argument("--time-every", type=int, default=0, help="(--full) time every N-th launch of each kernel with a HIP-event pair (default: every 7th; every 5th when steps < 64, every one when < 16); "
+                    "odd on purpose: an even stride could lock onto a period of the workload")
+    ap.add_argument("--gather-steps", type=int, default=50, help="(--full) extra steps timed WITH the observation all-gather (N>1)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -338,44 +364,52 @@ def main():
     n, env = hz.n, hz.env
     preroll = None
     if args.preroll_steps > 0:
-        kc = min(K, args.preroll_steps)
-        barrier()
-        c0 = time.perf_counter()
-        for _ in range(kc):
-            hz.step()
-        barrier()
-        cdt = torch.tensor([time.perf_counter() - c0], dtype=torch.float64)
-        if world > 1:
-            dist.all_reduce(cdt, op=dist.ReduceOp.MAX)
+        kc = min(K, args.preroll_steps) if args.full else 0
+        if kc:
+            barrier()
+            c0 = time.perf_counter()
+            for _ in range(kc):
+                hz.step()
+            barrier()
+            cdt = torch.tensor([time.perf_counter() - c0], dtype=torch.float64)
+            if world > 1:
+                dist.all_reduce(cdt, op=dist.ReduceOp.MAX)
         for _ in range(args.preroll_steps - kc):
             hz.step()
         torch.cuda.synchronize()
         preroll = {"steps": args.preroll_steps,
                    "why": "the metric is the steady-state rate (SURVEY.md 8d); a freshly created batch has every env at step 0 of its first episode "
-                          "(all start-room monsters awake, cold DistCaches, no resets), a heavier transient",
-                   "cold_start": {"steps": kc, "ms_per_step": float(cdt.item()) / kc * 1e3, "value": n * world * kc / float(cdt.item()),
-                                  "note": "the first %d steps after creation, no warm-up at all" % kc}}
-    hz.timing(1); hz.timing(0)  # create the event pool NOW (32 768 hipEventCreate calls: ~50 ms of host time with an idle GPU) -- not between the warm-up and the timed region
+                          "(all start-room monsters awake, cold DistCaches, no resets), a heavier transient"}
+        if kc:
+            preroll["cold_start"] = {"steps": kc, "ms_per_step": float(cdt.item()) / kc * 1e3, "value": n * world * kc / float(cdt.item()),
+                                     "note": "the first %d steps after creation, no warm-up at all" % kc}
+    if args.full:
+        hz.timing(1); hz.timing(0)  # create the event pool NOW (32 768 hipEventCreate calls: ~50 ms of host time with an idle GPU) -- not between the warm-up and the timed region
     for _ in range(W):
         hz.step()
     # HIP-event pairs handed to a launch cost stream time: measured in round 4 at ~10 us per step with every 3rd launch of both kernels timed (a
     # 20-step window: 131-143 us per step against 120-129 without, tools/tmp/window_fit2.py).  So few samples for short runs: every 5th launch = 4 pairs
     # per kernel for the driver's 20 steps (round 5, same box: 651-656 M with the four pairs per kernel, 666-676 M with none; two pairs cost the same as four).  The strides are odd out of caution only: since round 4 the generator runs beside EVERY k_step, there are no
     # two kinds of launch left to alternate between.
+    # A plain run carries none: only --full samples the kernels.
     every = args.time_every if args.time_every > 0 else (1 if K < 16 else (5 if K < 64 else 7))
-    hz.timing(every)  # HIP-event pairs on the launch stream around every `every`-th launch of each kernel
-    env.counters(reset=True)
+    if args.full:
+        hz.timing(every)  # HIP-event pairs on the launch stream around every `every`-th launch of each kernel
+        env.counters(reset=True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(K):
-        hz.step()
+        last = hz.step()
     barrier()
     dt = time.perf_counter() - t0
-    per_kernel = hz.read_timing()
-    hz.timing(0)
-    counts = env.counters(reset=True)
-    sclk_after = hz.sclk()
+    if args.full:
+        per_kernel = hz.read_timing()
+        hz.timing(0)
+        counts = env.counters(reset=True)
+        sclk_after = hz.sclk()
     env.check_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
 
     tmax = torch.tensor([dt], dtype=torch.float64)
     props = torch.cuda.get_device_properties(dev)
@@ -390,7 +424,7 @@ def main():
 
     # ---- 4 further runs of K steps (no event timing): the spread of the headline number ----
     repeats = None
-    if not args.no_repeats:
+    if args.full and not args.no_repeats:
         runs = [dt_max / K * 1e3]
         for _ in range(4):
             barrier()
@@ -409,7 +443,7 @@ def main():
     # SURVEY.md 8(d) defines the metric on "steady-state over >= 1 000 lock-step batch steps": when the timed region is shorter (the driver's command:
     # 20 steps), the same batch runs one 1 000-step window right behind it, so that the contract's own window is in the line too
     long_window = None
-    if K < 1000:
+    if args.full and K < 1000:
         barrier()
         l0 = time.perf_counter()
         for _ in range(1000):
@@ -421,13 +455,13 @@ def main():
         long_window = {"steps": 1000, "ms_per_step": float(lw.item()) / 1000 * 1e3, "value": n * world * 1000 / float(lw.item())}
 
     # what one step costs a caller that waits on every step: percentiles over their own 1 000-step window (event pair on every launch)
-    step_us = hz.step_percentiles(1000)
+    step_us = hz.step_percentiles(1000) if args.full else None
 
     # BASELINE.json's metric reads "whole node at 65 536 envs ... 1/2/4/8 GPU": `value` keeps 65 536 envs PER GPU (weak scaling, the contract's default); this
     # leg is the other reading -- 65 536 envs IN TOTAL, 65 536 / N per GPU -- so that the line answers both.  A second, smaller batch on every rank (seeds = the
     # global env index again), its own pre-roll, 200 timed steps, max over ranks.
     strong = None
-    if world > 1:
+    if args.full and world > 1:
         total = 65536 if args.workload == "mini" else WORKLOADS[args.workload][1]
         per = max(64, total // world)
         sz = Harness(torch, args.workload, per, rank, local_rank)
@@ -453,7 +487,7 @@ def main():
     # headline down: each leg runs under a watchdog (a collective that never completes cannot be caught as an exception), and a failure is
     # reported inside "allgather" instead of being raised.
     gather = None
-    if world > 1 and args.gather_steps > 0:
+    if args.full and world > 1 and args.gather_steps > 0:
         import threading
 
         rec = env._h.L.rg_compact_record_bytes(env._h.h, 0)
@@ -516,6 +550,32 @@ def main():
 
     out = None
     if rank == 0:
+        build_id = env._h.L.rg_build_id().decode()
+        out = {
+            "metric": "env-steps/sec (whole node) at 65 536 envs, 32x16 mini-dungeon" if args.workload == "mini" and n == 65536 and not args.persistent_obs
+                      else "env-steps/sec (whole node), workload %s, %d envs per GPU" % (args.workload, n),
+            "value": n * world * K / dt_max,
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "n_gpus_visible": torch.cuda.device_count(),
+            "rank_devices": rank_devices,   # per rank: LOCAL_RANK, the HIP device it stepped on and that device's PCI bus id -- a mis-mapped LOCAL_RANK shows here
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": dt_max / K * 1e3,
+            "value_is": "steady-state episode mix: EXACTLY `steps` timed steps after a disclosed pre-roll of the measured batch (`preroll`) + `warmup` steps",
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8/u16 integer state, f32 observation",
+            "data": "synthetic (per-env seed = env index, uniform-random 11-action policy)",
+            "config": {"workload": "%s, %d envs per GPU (%d total), %s-image obs [N,%d,%d,%d] f32, max_steps 1000, auto-reset"
+                                   % (hz.desc, n, n * world, hz.obs_kind, env.channels, env.height, env.width), "envs_per_gpu": n,
+                       "parallelism": "env-sharded x%d, no data-path collective" % world},
+            "build_id": build_id,  # sha256[:16] of the library's sources (__graft_entry__.source_id)
+            "clock_warm": clock_warm,
+            "preroll": preroll,
+        }
+    if rank == 0 and args.full:
         # the dominant kernel of the STEP (what bounds ms_per_step): the longer of the two serial kernels.  k_regen is timed too and shown in
         # gpu_time_share -- by duration x launches it holds the GPU as long as k_step does -- but it runs beside k_step on a low-priority stream and
         # moves ~7 MB per launch (SALU-bound level generation): pricing the step's bytes against ITS clock would say nothing about either.
@@ -535,38 +595,15 @@ def main():
             traffic_src = pj.get("_measured", "profiles/pmc_traffic.json (rocprofv3 --pmc passes; build not stamped)")
             traffic_all = {k: {"hbm_bytes_per_launch": v.get("hbm_bytes_per_launch"), "hbm_bytes_per_env_step": (v.get("hbm_bytes_per_launch") or 0) / 65536.0}
                            for k, v in pj.items() if isinstance(v, dict) and "hbm_bytes_per_launch" in v}
-        build_id = env._h.L.rg_build_id().decode()
         if traffic is not None and traffic_build != build_id:
             # the PMC passes are a separate rocprofv3 collection (profiles/pmc_traffic.json): a figure taken on another build of the kernels is not reported
             traffic_src = "profiles/pmc_traffic.json was collected on build %s, this library is %s: traffic withheld" % (traffic_build, build_id)
             traffic, traffic_all = None, None
-        out = {
-            "metric": "env-steps/sec (whole node) at 65 536 envs, 32x16 mini-dungeon" if args.workload == "mini" and n == 65536 and not args.persistent_obs
-                      else "env-steps/sec (whole node), workload %s, %d envs per GPU" % (args.workload, n),
-            "value": n * world * K / dt_max,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "n_gpus_visible": torch.cuda.device_count(),
-            "rank_devices": rank_devices,   # per rank: LOCAL_RANK, the HIP device it stepped on and that device's PCI bus id -- a mis-mapped LOCAL_RANK shows here
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": dt_max / K * 1e3,
-            "value_is": "steady-state episode mix: EXACTLY `steps` timed steps after a disclosed pre-roll of the measured batch (`preroll`) + `warmup` steps",
+        out.update({
             "value_cold_start": preroll["cold_start"]["value"] if preroll else None,   # the first `steps` steps after creation, no warm-up at all
             "value_median_of_repeats": repeats["median_value"] if repeats else None,   # 5 runs of `steps` steps; runs 1-4 without HIP-event pairs
             "value_long_window": long_window["value"] if long_window else None,        # 1 000 steps right behind the timed region (SURVEY.md 8d's own window), when `steps` < 1 000
             "long_window": long_window,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8/u16 integer state, f32 observation",
-            "data": "synthetic (per-env seed = env index, uniform-random 11-action policy)",
-            "config": {"workload": "%s, %d envs per GPU (%d total), %s-image obs [N,%d,%d,%d] f32, max_steps 1000, auto-reset"
-                                   % (hz.desc, n, n * world, hz.obs_kind, env.channels, env.height, env.width), "envs_per_gpu": n,
-                       "parallelism": "env-sharded x%d, no data-path collective" % world},
-            "build_id": build_id,  # sha256[:16] of the library's sources (__graft_entry__.source_id)
-            "clock_warm": clock_warm,
-            "preroll": preroll,
             "sclk_mhz_after_timed_region": sclk_after,
             # flat and small on purpose (the driver keeps a prefix of the line).  `achieved` is the contract's definition: the WHOLE step's algorithmic
             # bytes over the dominant kernel's clock.  `traffic` is that kernel's own measured HBM bytes per launch (PMC, calibrated), to be read against
@@ -591,7 +628,7 @@ def main():
             "workload_rates": {"per": "whole job, per second (rank 0's counters x n_gpus)",
                                **{k + "_per_s": v * world / dt_max for k, v in counts.items()},
                                "per_batch_step": {k: v / K for k, v in counts.items()}},
-        }
+        })
         if repeats:
             out["repeats"] = repeats
         if gather is not None:
@@ -606,7 +643,7 @@ def main():
     hz.close()
     del hz, env
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         try:
             peak = copy_peak(torch, dev)
             out["roofline"]["copy_peak_GBps"] = peak

@@ -98,7 +98,7 @@ def test_bench_two_ranks_on_one_device():
         env.pop(k, None)
     # the driver's own command form: no launcher -- bench.py starts its N ranks itself
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5", "--envs-per-gpu", "8192", "--gather-steps", "10",
-           "--clock-warm-s", "0.2"]
+           "--clock-warm-s", "0.2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -124,7 +124,7 @@ def test_bench_eight_ranks_on_one_device():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "10", "--warmup", "2", "--envs-per-gpu", "2048", "--gather-steps", "4",
-           "--clock-warm-s", "0", "--preroll-steps", "20", "--no-repeats"]
+           "--clock-warm-s", "0", "--preroll-steps", "20", "--no-repeats", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,4 +1,4 @@
-"""One compact line from bench.py's JSON (stdin): value, ms/step, per-kernel averages, generation counters.  Usage: python bench.py ... | python tools/ab_line.py TAG"""
+"""One compact line from bench.py's JSON (stdin): value, ms/step, per-kernel averages, generation counters.  Usage: python bench.py --full ... | python tools/ab_line.py TAG"""
 import json, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

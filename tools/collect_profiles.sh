@@ -8,12 +8,12 @@ tag=${1:-r04}; commit=${2:-unknown}
 out=gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-extra --no-repeats"
+Q="--full --no-cpu-baseline --no-extra --no-repeats"
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_BRANCH"
 SQ2="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY"
 # 1. bench lines: default run (extras, repeats, cpu baseline) and the DRIVER's exact command
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_driver_cmd.json 2>> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_driver_cmd.json 2>> $out/${tag}_bench.err
 # 2. calibration of FETCH_SIZE / WRITE_SIZE on this box
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/${tag}_cal_f -- python tools/pmc_calibrate.py > $out/${tag}_cal.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/${tag}_cal_w -- python tools/pmc_calibrate.py >> $out/${tag}_cal.log 2>&1
@@ -26,7 +26,7 @@ for wl in mini default nohide-symbol; do
     *) S="--steps 80 --warmup 10 --preroll-steps 100"; P="--steps 20 --warmup 5 --preroll-steps 60";;
   esac
   W="--workload $wl $Q --clock-warm-s 0"
-  python bench.py --workload $wl --no-extra --no-cpu-baseline $S > $out/${tag}_bench_${wl}.json 2>> $out/${tag}_bench.err
+  python bench.py --workload $wl --full --no-extra --no-cpu-baseline $S > $out/${tag}_bench_${wl}.json 2>> $out/${tag}_bench.err
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${tag}_trace_$wl -- python bench.py $W $S > $out/${tag}_trace_$wl.log 2>&1
   cp "$(find /tmp/${tag}_trace_$wl -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats_$wl.csv
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/${tag}_fetch_$wl -- python bench.py $W $P > $out/${tag}_pmc_$wl.log 2>&1
@@ -55,7 +55,7 @@ for wl in mini default nohide-symbol; do
     default) S="--steps 400 --warmup 50 --preroll-steps 500";;
     *) S="--steps 80 --warmup 10 --preroll-steps 100";;
   esac
-  python bench.py --workload $wl --no-extra --no-cpu-baseline --no-repeats --persistent-obs $S > $out/${tag}_bench_bound_${wl}.json 2>> $out/${tag}_bench.err
+  python bench.py --workload $wl --full --no-extra --no-cpu-baseline --no-repeats --persistent-obs $S > $out/${tag}_bench_bound_${wl}.json 2>> $out/${tag}_bench.err
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${tag}_trace_bound -- python bench.py --workload mini $Q --clock-warm-s 0 --persistent-obs --steps 2000 --warmup 200 > $out/${tag}_trace_bound.log 2>&1
 cp "$(find /tmp/${tag}_trace_bound -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats_bound_mini.csv

@@ -1,20 +1,21 @@
 #!/bin/bash
 # Evidence for the driver-run bench line: the driver's exact command under the four combinations of
 # {first spares awaited in rg_create | left in the background (round-1 behaviour)} x {clock-warm phase on | off}.
-# Writes gpurun_out/driver_repro_*.json (one bench line each).
-mkdir -p gpurun_out
+# Writes OUTDIR/driver_repro_*.json (one bench line each; --full, for the per-kernel times and clocks).  Usage: tools/driver_repro.sh [OUTDIR, default tools/tmp]
+out=${1:-tools/tmp}
+mkdir -p $out
 for spares in wait async; do
   for warm in 1.5 0; do
     if [ $spares = async ]; then export ROGUE_GYM_HIP_ASYNC_FIRST_SPARES=1; else unset ROGUE_GYM_HIP_ASYNC_FIRST_SPARES; fi
     for rep in 1 2; do
-      python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-repeats --clock-warm-s $warm > gpurun_out/driver_repro_${spares}_warm${warm}_$rep.json 2> gpurun_out/driver_repro.err
+      python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra --no-repeats --clock-warm-s $warm > $out/driver_repro_${spares}_warm${warm}_$rep.json 2> $out/driver_repro.err
     done
   done
 done
 unset ROGUE_GYM_HIP_ASYNC_FIRST_SPARES
-python3 - <<'P'
-import glob, json
-for f in sorted(glob.glob("gpurun_out/driver_repro_*_*.json")):
+OUT=$out python3 - <<'P'
+import glob, json, os
+for f in sorted(glob.glob(os.path.join(os.environ["OUT"], "driver_repro_*_*.json"))):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
         pk = d["roofline"]["per_kernel"]

@@ -1,5 +1,5 @@
 """Step-latency jitter against the level-per-lane producer's launch shape (VERDICT r5 task 5b): for each setting of the development library's knobs, one
-`bench.py --steps 20 --warmup 5` run; prints its long-window rate and the per-step GPU-time percentiles (bench.py `step_us`: an event pair on every launch of a
+`bench.py --full --steps 20 --warmup 5` run; prints its long-window rate and the per-step GPU-time percentiles (bench.py `step_us`: an event pair on every launch of a
 1 000-step window).  Usage: python tools/jitter_sweep.py [mini|default]  (needs rogue-gym_amd/variants/librogue_gym_hip_dev.so: __graft_entry__.build())."""
 import json
 import os
@@ -27,7 +27,7 @@ for name, knobs in SETS:
     env = dict(os.environ)
     if knobs is not None:
         env.update(knobs, ROGUE_GYM_HIP_LIB=DEV)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extra", "--no-repeats", "--workload", wl]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extra", "--no-repeats", "--workload", wl]
     if wl != "mini":
         cmd += ["--preroll-steps", "500"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
