@@ -1,6 +1,7 @@
 // rg_obs.hip -- render / observation-encode kernels of the batched Rogue-Gym stepper (gfx950).
 //
 //   k_obs<gray|symbol> : fused RunTime::draw_screen (mirror refresh of Redraw envs) + PlayerState::{gray,symbol}_image
+//   k_obs_stream       : the same for the plain gray image of grids of at most 512 cells, streamed in runs of envs
 //   k_render, k_gray, k_symbol, k_encode_scalar : unfused fallbacks
 //
 // Built as its own translation unit with -Os: these kernels are bandwidth/latency-bound and measurably faster with less
@@ -194,6 +195,44 @@ __device__ __forceinline__ void store_obs(float4 *p, float4 v) {
 struct ObsTabs { uint32_t w[RG_OBS_REC_WORDS(RG_OBS_MAX_ROOMS)]; };
 #define OBS_ENV_BYTES(hw) ((((size_t)(hw) + sizeof(ObsTabs)) + 15) & ~(size_t)15)
 
+// Phase A of a Redraw (RunTime::draw_screen, rogue/mod.rs:278-290): the 8 tile words of uint4 `i` of an env's grid (cells 8i .. 8i+7) -> 8 glyph bytes
+// (bit 7: an object on the cell is drawn, draw_ranges) and 8 visited bytes of the history plane
+__device__ __forceinline__ void draw_cells8(uint4 v, int i, int W, int HW, uint32_t g[2], uint32_t hb[2]) {
+    const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+    g[0] = g[1] = hb[0] = hb[1] = 0;
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        uint32_t cw = (q[t >> 1] >> ((t & 1) * 16)) & 0xffff;
+        int idx = i * 8 + t;
+        bool inner = idx >= W && idx < HW - W;  // rows 1..H-2 only (rogue/mod.rs:278-290)
+        uint32_t gl = ' ';
+        if (inner && (cw & C_VISIBLE)) gl = glyph_of(cw);
+        if (inner && (cw & (C_VISIBLE | C_DRAWN))) gl = ((cw & C_GOLD) ? (uint32_t)'*' : gl) | 0x80u;  // bit 7: an object on this cell is drawn (draw_ranges);
+                                                                                                  // gold is drawn over a monster, under the player
+        g[t >> 2] |= gl << ((t & 3) * 8);
+        hb[t >> 2] |= ((cw & C_VISITED) ? 1u : 0u) << ((t & 3) * 8);
+    }
+}
+// Phase B: whether the monster at (x, y) is drawn as seen from the player at (px, py) (core/src/lib.rs:271-283): adjacent, or in the same room
+// (Floor::in_same_room, floor.rs:381-393) -- room rects and metas from the env's observation record staged in LDS
+__device__ __forceinline__ bool monster_shown(const RgConfig &c, const ObsTabs *tb, int nrooms, int px, int py, int x, int y) {
+    int dx = px - x, dy = py - y;
+    bool show = dx * dx + dy * dy <= 2;
+    if (!show) {
+        int id = room_id_of(c, px, py);
+        if (id >= 0 && room_id_of(c, x, y) == id) {
+            if ((reinterpret_cast<const uint8_t *>(&tb->w[2 * nrooms + 1])[id] & RM_KIND_MASK) == RK_EMPTY) show = true;
+            else {
+                int x0, y0, x1, y1;
+                unpack_rect(tb->w[nrooms + 1 + id], x0, y0, x1, y1);
+                bool ina = px >= x0 && px < x1 && py >= y0 && py < y1, inb = x >= x0 && x < x1 && y >= y0 && y < y1;
+                show = ina == inb;
+            }
+        }
+    }
+    return show;
+}
+
 // LDS-only workgroup barrier: unlike __syncthreads() it does not drain vmcnt, so the prefetched global loads of the next env stay in flight
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -356,20 +395,8 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs(RgState S, RgConfig c, uint
                 uint2 *hist8 = reinterpret_cast<uint2 *>(S.hist + (size_t)e * HW);
                 for (int i = lt; i < Q8; i += tpe) {
                     uint4 v = i == lt ? v0 : cell4[i];
-                    uint32_t q[4] = {v.x, v.y, v.z, v.w};
-                    uint32_t g[2] = {0, 0}, hb[2] = {0, 0};
-#pragma unroll
-                    for (int t = 0; t < 8; t++) {
-                        uint32_t cw = (q[t >> 1] >> ((t & 1) * 16)) & 0xffff;
-                        int idx = i * 8 + t;
-                        bool inner = idx >= W && idx < HW - W;  // rows 1..H-2 only (rogue/mod.rs:278-290)
-                        uint32_t gl = ' ';
-                        if (inner && (cw & C_VISIBLE)) gl = glyph_of(cw);
-                        if (inner && (cw & (C_VISIBLE | C_DRAWN))) gl = ((cw & C_GOLD) ? (uint32_t)'*' : gl) | 0x80u;  // bit 7: an object on this cell is drawn (draw_ranges);
-                                                                                                                  // gold is drawn over a monster, under the player
-                        g[t >> 2] |= gl << ((t & 3) * 8);
-                        hb[t >> 2] |= ((cw & C_VISITED) ? 1u : 0u) << ((t & 3) * 8);
-                    }
+                    uint32_t g[2], hb[2];
+                    draw_cells8(v, i, W, HW, g, hb);
                     reinterpret_cast<uint2 *>(scr)[i] = make_uint2(g[0], g[1]);
                     if (upd_hist) hist8[i] = make_uint2(hb[0], hb[1]);
                 }
@@ -387,20 +414,7 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs(RgState S, RgConfig c, uint
             uint32_t w = tb->w[lt];
             if ((w >> 24) & MF_ALIVE) {
                 int x = POS_X(w), y = POS_Y(w);
-                int dx = px - x, dy = py - y;
-                bool show = dx * dx + dy * dy <= 2;
-                if (!show) {  // Floor::in_same_room (floor.rs:381-393)
-                    int id = room_id_of(c, px, py);
-                    if (id >= 0 && room_id_of(c, x, y) == id) {
-                        if ((reinterpret_cast<const uint8_t *>(&tb->w[2 * nrooms + 1])[id] & RM_KIND_MASK) == RK_EMPTY) show = true;
-                        else {
-                            int x0, y0, x1, y1;
-                            unpack_rect(tb->w[nrooms + 1 + id], x0, y0, x1, y1);
-                            bool ina = px >= x0 && px < x1 && py >= y0 && py < y1, inb = x >= x0 && x < x1 && y >= y0 && y < y1;
-                            show = ina == inb;
-                        }
-                    }
-                }
+                const bool show = monster_shown(c, tb, nrooms, px, py, x, y);
                 const uint32_t under = scr[y * W + x];
                 if (show && (under & 0x80u) && under != (0x80u | '*')) scr[y * W + x] = (uint8_t)(0x80u | mtile[(w >> 16) & 0xff]);
             }
@@ -434,6 +448,129 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs(RgState S, RgConfig c, uint
                              ((fl & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u) | (KIND == 1 && bad ? RG_FLAG_ERR_TILE : 0);
             else if (BOUND && !redraw && lt == 0) atomicAnd(&S.flags[e], ~RG_FLAG_SCR_CHANGED);  // (atomic: the one-hot kind ORs its error bit into the same word)
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_obs_stream: the gray image without status / history planes, no config groups, not bound, on grids of at most 512 cells (the headline workload:
+// 65 536 mini envs).  Same bits, flags and mirrors as k_obs<0, false>.
+// ---------------------------------------------------------------------------------------------
+// One wave owns a RUN of OBS_RUN consecutive envs (4: 16 384 waves at 65 536 envs, eight per SIMD; runs of 8 and 16 and smaller grids measured slower,
+// profiles/r07_experiments.txt), whose mirrors are one contiguous stretch of the screen array and whose images are one contiguous stretch
+// of the tensor.  It issues the run's flag words (one coalesced load) and every mirror word of the run at once -- nothing of the stream waits on a flag --
+// ballots on RG_FLAG_REDRAW, and streams each env without a pending Redraw (98 % of them) mirror word -> glyph table -> one whole-line float4 store per
+// 64 words.  The run's Redraw envs are drawn afterwards from the tiles, one at a time, by the whole wave (the staged path of k_obs: LDS draw, overlays,
+// mirror write-back, encode, flag word); the tile loads of the first are issued before the stream's stores, so its latency hides behind them, and the
+// barriers are the wave's own.  k_obs instead walks its envs as a chain per block -- flag word -> mirror or tiles -> stores -- one env per round trip.
+#ifndef OBS_RUN
+#define OBS_RUN 4
+#endif
+#ifndef OBS_STREAM_WAVES
+#define OBS_STREAM_WAVES 16384
+#endif
+__global__ void __launch_bounds__(WAVE) k_obs_stream(RgState S, RgConfig c, float *__restrict__ out, int hi_prio) {
+    if (hi_prio) __builtin_amdgcn_s_setprio(3);
+    __shared__ float lutf[128];                              // glyph -> gray value
+    __shared__ uint8_t mtile[RG_MAX_ENEMY_KINDS + 6];        // monster type -> glyph
+    __shared__ __align__(16) uint8_t scr[512];               // the staged screen of a Redraw env (HW <= 512: rgk_obs)
+    __shared__ ObsTabs tb;                                   // its observation record
+    const int lane = threadIdx.x, W = c.width, HW = W * c.height, Q4 = HW >> 2, Q8 = HW >> 3, n = S.n;
+    const int nrooms = c.room_num_x * c.room_num_y, rec_words = RG_OBS_REC_WORDS(nrooms);
+    for (int g = lane; g < 128; g += WAVE) lutf[g] = (float)(uint8_t)tile_to_sym((uint32_t)g) / (float)(uint8_t)c.symbols;  // python/src/lib.rs:84 (same single division)
+    for (int g = lane; g < RG_MAX_ENEMY_KINDS + 6; g += WAVE) mtile[g] = c.mon[g].tile;
+    lds_barrier();
+    auto gray4 = [&](uint32_t w) {
+        w &= 0x7f7f7f7fu;
+        float4 v; v.x = lutf[w & 0xff]; v.y = lutf[(w >> 8) & 0xff]; v.z = lutf[(w >> 16) & 0xff]; v.w = lutf[w >> 24];
+        return v;
+    };
+    // a run's flag words (lane i: env i) and mirror words (words lane and lane + 64 of each env: Q4 <= 128); zeros past the batch
+    struct Run { uint32_t fl, w0[OBS_RUN], w1[OBS_RUN]; };
+    auto load_run = [&](int r, Run &R) {
+        const int base = r * OBS_RUN, cnt = n - base;
+        R.fl = lane < cnt && lane < OBS_RUN ? S.flags[base + lane] : 0u;
+        const uint32_t *m = reinterpret_cast<const uint32_t *>(S.screen) + (size_t)base * Q4;
+#pragma unroll
+        for (int i = 0; i < OBS_RUN; i++) {
+            R.w0[i] = i < cnt && lane < Q4 ? m[i * Q4 + lane] : 0u;
+            R.w1[i] = i < cnt && lane + WAVE < Q4 ? m[i * Q4 + lane + WAVE] : 0u;
+        }
+    };
+    // Persistent waves, one run ahead: the next run's loads are issued before this run's stores, so a wave's loads and stores overlap and
+    // the waves of the grid drift out of step (a wave with ONE run loads everything, then stores everything, all waves in the same phase)
+    const int nruns = (n + OBS_RUN - 1) / OBS_RUN;
+    Run cur;
+    load_run(blockIdx.x, cur);
+    for (int r = blockIdx.x; r < nruns; r += gridDim.x) {
+        const int base = r * OBS_RUN, cnt = n - base < OBS_RUN ? n - base : OBS_RUN;
+        Run nxt;
+        load_run(r + gridDim.x, nxt);
+        const uint32_t fl = cur.fl;
+#ifdef RG_EXP_OBS_STREAM_BOUND
+        uint64_t rmask = 0;  // (experiment build: every env streamed from its mirror, Redraws NOT drawn -- the bound of the stream, profiles/r07_experiments.txt)
+#else
+        uint64_t rmask = __ballot(fl & RG_FLAG_REDRAW);
+#endif
+        // the first Redraw env's tile words and observation record: in flight while the stream's stores issue
+        auto load_tiles = [&](int e, uint4 &v, uint32_t &rec) {
+            v = lane < Q8 ? reinterpret_cast<const uint4 *>(S.cell + (size_t)e * HW)[lane] : make_uint4(0, 0, 0, 0);
+            rec = lane < rec_words ? S.obs_rec[(size_t)e * rec_words + lane] : 0u;
+        };
+        uint4 tv = make_uint4(0, 0, 0, 0);
+        uint32_t trec = 0;
+        if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);
+        float4 *o = reinterpret_cast<float4 *>(out) + (size_t)base * Q4;
+#pragma unroll
+        for (int i = 0; i < OBS_RUN; i++) {
+            if (i >= cnt || ((rmask >> i) & 1)) continue;  // (run-uniform)
+            if (lane < Q4) store_obs(&o[i * Q4 + lane], gray4(cur.w0[i]));
+            if (lane + WAVE < Q4) store_obs(&o[i * Q4 + lane + WAVE], gray4(cur.w1[i]));
+        }
+        while (rmask) {
+            const int i = __builtin_ctzll(rmask);
+            rmask &= rmask - 1;
+            const int e = base + i;
+            const uint32_t fle = __builtin_amdgcn_readlane(fl, i);
+            const uint4 v = tv;
+            const uint32_t t_rec = trec;
+            if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);
+            lds_barrier();  // the previous Redraw's LDS reads done
+            if (lane < rec_words) tb.w[lane] = t_rec;
+            // the history plane is rewritten only when the visited set changed since it was last written (k_step: HIST_DIRTY), never on a stale Redraw
+            const bool upd_hist = !(fle & RG_FLAG_HIST_STALE) && (fle & RG_FLAG_HIST_DIRTY);
+            if (lane < Q8) {
+                uint32_t g[2], hb[2];
+                draw_cells8(v, lane, W, HW, g, hb);
+                reinterpret_cast<uint2 *>(scr)[lane] = make_uint2(g[0], g[1]);
+                if (upd_hist) reinterpret_cast<uint2 *>(S.hist + (size_t)e * HW)[lane] = make_uint2(hb[0], hb[1]);
+            }
+            lds_barrier();
+            // entity overlays; draw priority monster < gold < player (core/src/lib.rs:271-283), as in k_obs
+            const uint32_t ppos = tb.w[nrooms];
+            const int px = POS_X(ppos), py = POS_Y(ppos);
+            if (lane < nrooms) {
+                const uint32_t mw = tb.w[lane];
+                if ((mw >> 24) & MF_ALIVE) {
+                    const int x = POS_X(mw), y = POS_Y(mw);
+                    const uint32_t under = scr[y * W + x];
+                    if (monster_shown(c, &tb, nrooms, px, py, x, y) && (under & 0x80u) && under != (0x80u | '*')) scr[y * W + x] = (uint8_t)(0x80u | mtile[(mw >> 16) & 0xff]);
+                }
+            }
+            lds_barrier();
+            if (lane == 0 && (scr[py * W + px] & 0x80u)) scr[py * W + px] = (uint8_t)(0x80u | '@');
+            lds_barrier();
+            uint32_t *m4 = reinterpret_cast<uint32_t *>(S.screen + (size_t)e * HW);
+            float4 *oe = reinterpret_cast<float4 *>(out) + (size_t)e * Q4;
+            for (int q = lane; q < Q4; q += WAVE) {
+                const uint32_t g = reinterpret_cast<const uint32_t *>(scr)[q] & 0x7f7f7f7fu;
+                m4[q] = g;
+                store_obs(&oe[q], gray4(g));
+            }
+            if (lane == 0)  // (rg_obs.hip k_obs: a stale Redraw leaves the history mirror one level behind)
+                S.flags[e] = (fle & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fle & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY))) |
+                             ((fle & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u);
+        }
+        cur = nxt;
     }
 }
 
@@ -562,6 +699,21 @@ int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, 
         if (blocks > cap) blocks = cap;
     }
     const int hi_prio = !(c->width <= 32 && c->room_num_x * c->room_num_y <= 32);  // (rg_kernels.hip rgk_step: those configs step with k_step_w32)
+    // gray, no status / history planes, no config groups, not bound, one wave per env (<= 512 cells): the run-streaming kernel
+    bool stream = !kind && !groups && !bound && sflag == 0 && !with_hist && tpe == WAVE;
+#ifdef RG_DEV_KNOBS
+    if (const char *ev = getenv("RG_OBS_STREAM")) stream = stream && atoi(ev) != 0;  // (RG_OBS_STREAM=0: k_obs<0, false> -- tests/test_gpu_obs_stream.py)
+#endif
+    if (stream) {
+        int sblocks = (S->n + OBS_RUN - 1) / OBS_RUN, cap = OBS_STREAM_WAVES;  // persistent waves, each looping over runs
+#ifdef RG_DEV_KNOBS
+        if (const char *ev = getenv("RG_OBS_BLOCKS")) if (atoi(ev) > 0) cap = atoi(ev);
+#endif
+        if (sblocks > cap) sblocks = cap;
+        if (ev0 || ev1) hipExtLaunchKernelGGL(k_obs_stream, dim3(sblocks), dim3(WAVE), 0, st, ev0, ev1, 0, *S, *c, out, hi_prio);
+        else hipLaunchKernelGGL(k_obs_stream, dim3(sblocks), dim3(WAVE), 0, st, *S, *c, out, hi_prio);
+        return 1;
+    }
 #define RG_LAUNCH_OBS(...) do { if (ev0 || ev1) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(bthreads), (uint32_t)smem, st, ev0, ev1, 0, *S, *c, sflag, with_hist, out, err_any, tpe, epb, planes_sym, hi_prio); \
                                else hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(bthreads), smem, st, *S, *c, sflag, with_hist, out, err_any, tpe, epb, planes_sym, hi_prio); } while (0)
     if (bound && !groups && !kind) RG_LAUNCH_OBS(k_obs<0, false, true>);       // (rg_obs_bind: the in-place pass over the last k_step's list)
