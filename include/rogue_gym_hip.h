@@ -41,6 +41,7 @@ typedef struct rg_handle rg_t;
 #define RG_FLAG_ERR_DEAD   0x00020000u  /* ErrorKind::IgnoredInput: action key while dead */
 #define RG_FLAG_ERR_TILE   0x00040000u  /* symbol image: glyph with symbol >= symbols-1 (python/src/lib.rs:96-102) */
 #define RG_FLAG_ERR_INTERNAL 0x00080000u /* a capacity guard of the stepper tripped (each is proven unreachable; see rg_kernels.hip) */
+#define RG_FLAG_ERR_STATE  0x00100000u  /* a loaded record did not fit this env (magic / version / fingerprint / geometry): the env is unchanged (rg_state_load) */
 #define RG_FLAG_ERR_MASK   0x00ff0000u
 
 /* Replaces GameState::__new__ / ParallelGameState::new (python/src/lib.rs:217-225,270-294) and
@@ -262,6 +263,34 @@ int rg_config_resolved(const char *cfg_json, char *buf, size_t cap);
  * it and the engine never does; such keys are accepted, type-checked and written back by rg_dump_config.  Needs no device.  *needed = bytes incl.
  * NUL (buf may be NULL to query). */
 int rg_config_schema(char *buf, size_t cap, size_t *needed);
+
+/* Batched save and restore of env game states (ALE's cloneState / restoreState, for every env of the batch at once).
+ * A STATE RECORD is one env's running game as a fixed-size, position-independent byte string of R = rg_state_record_bytes(h) bytes: no pointers, nothing
+ * that depends on n_env.  R depends only on the config's geometry and room grid and on the handle's key-log capacity.  Layout (rogue-gym_amd/csrc/
+ * rg_state_io.h; every section 16-byte aligned, padding zero):
+ *   header (64 B): u32 magic "RGST", RG_STATE_VERSION, R, H | W << 16, rooms, sections, a 64-bit config fingerprint (FNV-1a of rg_config_canonical's text
+ *                  without seed / seed_range), key-log capacity, key-log length
+ *   cell u16 [H*W], screen u8 [H*W], hist u8 [H*W], dist maps u16 [9][H*W] (configs with enemies), their saved walkable masks (the grid class with
+ *   partial maps), status i32 [10], the env's observation-overlay record, then one u32 per word of the SoA state: player, hunger, gold, level, steps,
+ *   flags, reward, done, the three RNG streams, monster counts, the dist-cache ring (keys, head, length, partial / saved bits), and per room the room,
+ *   monster and gold tables and the overlay positions; last the running episode's key log (the saving handle's capacity; 0 bytes when logging is off).
+ * What a record does NOT carry, deliberately: what decides the env's FUTURE episodes -- seed, seed range, build counter, the pre-generated spare levels and
+ * the previous episode's key log -- belongs to the destination slot.  A restored env plays out the saved episode; when that episode ends it resets from
+ * its OWN seed, as rg_reset would.  Nor the generator's scratch (corridor records, maze stack: dead once a level is complete) and the handle-local flag bits
+ * (RG_FLAG_SCR_CHANGED, the error bits: cleared in the record).  Records are canonical: padding, the key log past its length and the words of
+ * empty slots (a dead monster's hp / exp, an absent gold's amount) are zero, so equal states give equal bytes.
+ * rg_state_save: flushes the pending render (records hold drawn mirrors), then writes k records to out_dev = u8 [k][R] (16-byte aligned), env_ids[i]'s
+ *   state in record i; env_ids NULL = all n_env envs in order (k is then ignored).
+ * rg_state_load: k records of rec_bytes each (R of the SAVING handle: it may differ from this handle's only in the key-log section; as many logged keys are
+ *   loaded as fit) into envs env_ids[i] (NULL = all n_env in order).  Every header is checked on the device against this handle's fingerprint and layout:
+ *   a record that does not fit leaves its env untouched, sets RG_FLAG_ERR_STATE in its flags and is reported by the next rg_sync.  The bound observation
+ *   tensor (rg_obs_bind) is re-encoded in full at its next call.  A key log that the record did not hold completely is reported as truncated.
+ * Both are asynchronous on the handle's stream.  The background generators neither read nor write what a load writes, so stream order suffices: nothing
+ * is drained.  Host-side ids are range-checked and a load refuses duplicates; device-side ids (ids_on_device != 0, i32) are the caller's responsibility
+ * (an id out of range is skipped and raises RG_FLAG_ERR_STATE).  Not for handles with config groups; rg_state_record_bytes returns -1 for them. */
+int rg_state_record_bytes(const rg_t *h);
+int rg_state_save(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, uint8_t *out_dev);
+int rg_state_load(rg_t *h, const uint8_t *rec_dev, size_t rec_bytes, const int32_t *env_ids, int k, int ids_on_device);
 
 /* Parity/debug: synchronous copy of env i's internal state to the host. */
 typedef struct rg_debug_state {

@@ -14,6 +14,7 @@
 
 #include "../../include/rogue_gym_hip.h"
 #include "rg_state.h"
+#include "rg_state_io.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -45,6 +46,9 @@ void rgk_pack(const RgState *S, int with_hist, uint8_t *out, hipStream_t st);
 void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int row_bytes, hipStream_t st);
 void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st);
 int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, int kind, float *out, uint32_t *err_any, int planes_sym, int bound, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
+void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
+                    uint8_t *mark, hipStream_t st);
 }
 
 #define RG_TIMED_KERNELS 5   // k_step, k_render, k_obs (or the unfused encode), k_build, k_regen
@@ -108,6 +112,14 @@ struct rg_handle {
     size_t ev_used[RG_TIMED_KERNELS] = {0, 0, 0, 0, 0};
     uint64_t timing_seq[RG_TIMED_KERNELS] = {0, 0, 0, 0, 0};   // launches seen while timing is on (sampled or not)
     uint64_t timing_stride = 1;
+    // state records (rg_state_save / rg_state_load; rg_state_io.h)
+    uint64_t state_fp = 0;             // config fingerprint: FNV-1a 64 of the canonical config without seed / seed_range (create_homog)
+    uint64_t *io_desc = nullptr;       // word descriptors of the record's SoA section (built on first use: the state's addresses never change)
+    uint32_t *io_guard = nullptr;      // ... and per word its guard (rg_state_io.h RG_IO_GUARD_SHIFT)
+    uint32_t io_words = 0;
+    int32_t *io_ids = nullptr; size_t io_ids_cap = 0;  // host-side env ids, uploaded
+    uint8_t *io_ok = nullptr; size_t io_ok_cap = 0;    // per record of a load: its header fitted
+    uint8_t *io_mark = nullptr;                        // [n] per env: restored by the load in flight (k_state_stairs clears it)
 };
 
 #define RG_TIMING_MAX 4096
@@ -225,6 +237,14 @@ static int create_homog(const RgParsed &parsed, const EnvSeed *seeds, int n_env,
         }
     }
     h->cfg = h->parsed.cfg;
+    {   // the config fingerprint a state record carries: the canonical config without what differs between the envs of a group (seed, seed range)
+        RgParsed q = h->parsed;
+        q.has_seed_range = false;
+        const std::string js = rg_dump_config_json(q, 0, 0, false);
+        uint64_t f = 0xcbf29ce484222325ull;
+        for (unsigned char ch : js) { f ^= ch; f *= 0x100000001b3ull; }
+        h->state_fp = f;
+    }
     h->planes_sym = h->cfg.symbols;
     h->cfg.max_steps = max_steps > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)max_steps;
     h->cfg.auto_reset = auto_reset ? 1 : 0;
@@ -659,6 +679,7 @@ int rg_sync(rg_t *h) {
     if (err) {
         HIPCHK(h, hipMemsetAsync(h->d_err, 0, 4, h->stream));
         if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config)";
+        else if (err & RG_FLAG_ERR_STATE) h->err = "state record refused: it does not fit this env (magic / version / config fingerprint / geometry), the env is unchanged";
         else if (err & RG_FLAG_ERR_KEY) h->err = "Invalid input (key is not in the ai keymap)";
         else if (err & RG_FLAG_ERR_DEAD) h->err = "Ignored input (action while the player is dead)";
         else h->err = "Invalid tile in symbol image (symbol >= symbols - 1)";
@@ -811,6 +832,7 @@ int rg_step_fetch(rg_t *h, const uint8_t *keys_host, int n_keys, uint8_t *screen
     const uint32_t err = h->pin_err[0];
     if (err) {
         if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config)";
+        else if (err & RG_FLAG_ERR_STATE) h->err = "state record refused: it does not fit this env (magic / version / config fingerprint / geometry), the env is unchanged";
         else if (err & RG_FLAG_ERR_KEY) h->err = "Invalid input (key is not in the ai keymap)";
         else if (err & RG_FLAG_ERR_DEAD) h->err = "Ignored input (action while the player is dead)";
         else h->err = "Invalid tile in symbol image (symbol >= symbols - 1)";
@@ -1103,7 +1125,8 @@ int rg_history_keys(rg_t *h, int env, int which, uint8_t *keys, size_t cap, uint
     const uint32_t buf = which ? (cur ^ 1u) : cur;
     uint32_t l = 0;
     HIPCHK(h, hipMemcpy(&l, h->S.klog_len + buf * n + env, 4, hipMemcpyDeviceToHost));
-    if (len) *len = l;
+    if (len) *len = l & ~RG_KLOG_PARTIAL;
+    if (l & RG_KLOG_PARTIAL) { h->err = "action history incomplete: the episode was restored from a state record that did not hold all of its " + std::to_string(l & ~RG_KLOG_PARTIAL) + " keys"; return 2; }
     if (l > (uint32_t)h->S.klog_cap) { h->err = "action history truncated: " + std::to_string(l) + " keys in the episode, capacity " + std::to_string(h->S.klog_cap); return 2; }
     if (keys) {
         if (cap < l) { h->err = "rg_history_keys: buffer too small"; return 3; }
@@ -1312,6 +1335,153 @@ int rg_dev_sp_ready(rg_t *h, uint32_t *out_host, int *slots) {
     return 0;
 }
 #endif
+// ---- state records (rg_state_io.h / rg_state_io.hip) ----
+// The layout of this handle's records: fixed by geometry, room grid and the optional arrays, plus the key-log capacity
+static void state_layout(const rg_handle *h, RgIoLayout *L) {
+    memset(L, 0, sizeof *L);
+    const RgConfig &c = h->cfg;
+    const uint32_t hw = (uint32_t)c.width * (uint32_t)c.height, nr = (uint32_t)(c.room_num_x * c.room_num_y);
+    L->hw = hw; L->H = (uint32_t)c.height; L->W = (uint32_t)c.width; L->rooms = nr;
+    L->sections = (c.n_enemies > 0 ? RG_SEC_DCMAP : 0u) | (h->S.dc_walk ? RG_SEC_DCWALK : 0u) | (h->S.obs_rec ? RG_SEC_OBSREC : 0u) | (h->S.ovl ? RG_SEC_OVL : 0u);
+    uint32_t off = RG_STATE_HDR_BYTES;
+    L->o_cell = off; off += RG_STATE_PAD16(2 * hw);
+    L->o_screen = off; off += RG_STATE_PAD16(hw);
+    L->o_hist = off; off += RG_STATE_PAD16(hw);
+    if (L->sections & RG_SEC_DCMAP) { L->b_dcmap = 2u * RG_DIST_SLOTS * hw; L->o_dcmap = off; off += RG_STATE_PAD16(L->b_dcmap); }
+    if (L->sections & RG_SEC_DCWALK) { L->b_dcwalk = 4u * RG_DIST_SLOTS * (uint32_t)c.height * RG_WALK_WORDS(c.width); L->o_dcwalk = off; off += RG_STATE_PAD16(L->b_dcwalk); }
+    L->o_status = off; off += 48;
+    if (L->sections & RG_SEC_OBSREC) { L->b_obsrec = 4u * RG_OBS_REC_WORDS(nr); L->o_obsrec = off; off += RG_STATE_PAD16(L->b_obsrec); }
+    // the SoA words: 13 player / runtime scalars, 12 RNG words, mon_cnt, 9 dist-cache keys + 4 ring words, 7 per room, rooms + 1 overlay positions
+    L->n_words = 13 + 12 + 1 + RG_DIST_SLOTS + 4 + 7 * nr + ((L->sections & RG_SEC_OVL) ? nr + 1 : 0);
+    L->o_words = off; off += RG_STATE_PAD16(4 * L->n_words);
+    L->base = off;
+    L->klog_cap = h->S.klog ? (uint32_t)h->S.klog_cap : 0u;
+    L->R = off + RG_STATE_PAD16(L->klog_cap);
+    L->fp_lo = (uint32_t)h->state_fp; L->fp_hi = (uint32_t)(h->state_fp >> 32);
+}
+
+// the word descriptors of the record's SoA section, in record order (state_layout counts them)
+static int state_prepare(rg_handle *h) {
+    if (!h->io_mark && !dev_alloc(h, &h->io_mark, (size_t)h->S.n)) return 1;
+    if (h->io_desc) return 0;
+    const RgState &S = h->S;
+    const size_t n = (size_t)S.n;
+    const int nr = h->cfg.room_num_x * h->cfg.room_num_y;
+    std::vector<uint64_t> d;
+    auto add = [&](const void *p, int lg, int slots, bool flags = false) {
+        for (int s = 0; s < slots; s++)
+            d.push_back(((uint64_t)(uintptr_t)((const uint8_t *)p + ((size_t)s * n << lg)) & RG_IO_DESC_PTR_MASK) | ((uint64_t)lg << RG_IO_DESC_LG_SHIFT) |
+                        (flags ? RG_IO_DESC_FLAGS : 0ull));
+    };
+    add(S.p_pos, 1, 1); add(S.p_hp, 2, 1); add(S.p_hpmax, 2, 1); add(S.p_lvl, 2, 1); add(S.p_exp, 2, 1); add(S.food, 2, 1); add(S.quiet, 2, 1);
+    add(S.pack_gold, 2, 1); add(S.dlevel, 2, 1); add(S.steps, 2, 1); add(S.flags, 2, 1, true); add(S.reward, 2, 1); add(S.done, 0, 1);
+    add(S.rng, 2, 12); add(S.mon_cnt, 2, 1);
+    add(S.dc_key, 1, RG_DIST_SLOTS); add(S.dc_head, 0, 1); add(S.dc_len, 0, 1); add(S.dc_part, 1, 1); add(S.dc_own, 1, 1);
+    add(S.room_rect, 2, nr); add(S.room_meta, 0, nr);
+    const size_t i_w0 = d.size(); add(S.mon_w0, 2, nr);
+    const size_t i_hp = d.size(); add(S.mon_hp, 2, nr); add(S.mon_exp, 2, nr);
+    const size_t i_gp = d.size(); add(S.gold_pos, 2, nr);
+    const size_t i_ga = d.size(); add(S.gold_amt, 2, nr);
+    if (S.ovl) add(S.ovl, 1, nr + 1);
+    // the words of an EMPTY slot are stale (whatever the generator's tables held there): a dead monster's hp / exp and an absent gold's amount are
+    // written as 0, on save and on load, so that equal states give equal records
+    std::vector<uint32_t> g(d.size(), 0u);
+    for (int r = 0; r < nr; r++) {
+        g[i_hp + r] = g[i_hp + nr + r] = (uint32_t)(i_w0 + r + 1) | (24u << RG_IO_GUARD_SHIFT);  // MF_ALIVE: bit 0 of the flag byte
+        g[i_ga + r] = (uint32_t)(i_gp + r + 1) | (16u << RG_IO_GUARD_SHIFT);                       // gold present: 0x10000
+    }
+    RgIoLayout L;
+    state_layout(h, &L);
+    if (d.size() != L.n_words) { h->err = "state record: word table and layout disagree"; return 1; }
+    uint64_t *dd = nullptr;
+    uint32_t *gg = nullptr;
+    if (!dev_alloc(h, &dd, d.size()) || !dev_alloc(h, &gg, g.size())) return 1;
+    HIPCHK(h, hipMemcpy(dd, d.data(), d.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(gg, g.data(), g.size() * 4, hipMemcpyHostToDevice));
+    h->io_desc = dd; h->io_guard = gg; h->io_words = (uint32_t)d.size();
+    return 0;
+}
+
+// env ids of a save / load: a device pointer as given, or the host ids range-checked (and, for a load, without duplicates) and uploaded
+static int state_ids(rg_handle *h, const char *what, const int32_t *env_ids, int k, int on_device, bool unique, const int32_t **out) {
+    if (on_device) { *out = env_ids; return 0; }
+    std::vector<uint8_t> seen(unique ? (size_t)h->S.n : 0, 0);
+    for (int i = 0; i < k; i++) {
+        const int32_t e = env_ids[i];
+        if (e < 0 || e >= h->S.n) { h->err = std::string(what) + ": env id " + std::to_string(e) + " out of range [0, " + std::to_string(h->S.n) + ")"; return 1; }
+        if (unique) {
+            if (seen[e]) { h->err = std::string(what) + ": env id " + std::to_string(e) + " appears twice"; return 1; }
+            seen[e] = 1;
+        }
+    }
+    if ((size_t)k > h->io_ids_cap) {  // (the old buffer may still be read by a launch in flight: it stays allocated until rg_destroy)
+        size_t cap = h->io_ids_cap ? h->io_ids_cap : 256;
+        while (cap < (size_t)k) cap *= 2;
+        if (!dev_alloc(h, &h->io_ids, cap)) return 1;
+        h->io_ids_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->io_ids, env_ids, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));  // (pageable source: staged before the call returns)
+    *out = h->io_ids;
+    return 0;
+}
+
+int rg_state_record_bytes(const rg_t *h) {
+    if (!h->sub.empty()) { const_cast<rg_t *>(h)->err = "rg_state_record_bytes: not for a handle with config groups"; return -1; }
+    RgIoLayout L;
+    state_layout(h, &L);
+    return (int)L.R;
+}
+
+int rg_state_save(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, uint8_t *out_dev) {
+    if (!h->sub.empty()) { h->err = "rg_state_save: not for a handle with config groups (one handle per config)"; return 1; }
+    if (!out_dev || ((uintptr_t)out_dev & 15u)) { h->err = "rg_state_save: out_dev must be a 16-byte aligned device buffer"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t *ids = nullptr;
+    if (!env_ids) k = h->S.n;
+    else {
+        if (k < 0) { h->err = "rg_state_save: negative record count"; return 1; }
+        if (state_ids(h, "rg_state_save", env_ids, k, ids_on_device, false, &ids)) return 1;
+    }
+    if (k == 0) return 0;
+    if (state_prepare(h) || flush_render(h)) return 1;  // (records hold drawn mirrors: no Redraw is pending in them)
+    RgIoLayout L;
+    state_layout(h, &L);
+    rgk_state_save(&h->S, &L, h->io_desc, h->io_guard, ids, k, out_dev, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int rg_state_load(rg_t *h, const uint8_t *rec_dev, size_t rec_bytes, const int32_t *env_ids, int k, int ids_on_device) {
+    if (!h->sub.empty()) { h->err = "rg_state_load: not for a handle with config groups (one handle per config)"; return 1; }
+    if (!rec_dev || ((uintptr_t)rec_dev & 15u)) { h->err = "rg_state_load: rec_dev must be a 16-byte aligned device buffer"; return 1; }
+    if (rec_bytes < RG_STATE_HDR_BYTES || (rec_bytes & 15u) || rec_bytes > 0x7fffffffu) { h->err = "rg_state_load: rec_bytes is not the size of a state record"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t *ids = nullptr;
+    if (!env_ids) k = h->S.n;
+    else {
+        if (k < 0) { h->err = "rg_state_load: negative record count"; return 1; }
+        if (state_ids(h, "rg_state_load", env_ids, k, ids_on_device, true, &ids)) return 1;
+    }
+    if (k == 0) return 0;
+    if (state_prepare(h)) return 1;
+    if ((size_t)k > h->io_ok_cap) {
+        size_t cap = h->io_ok_cap ? h->io_ok_cap : 256;
+        while (cap < (size_t)k) cap *= 2;
+        if (!dev_alloc(h, &h->io_ok, cap)) return 1;
+        h->io_ok_cap = cap;
+    }
+    RgIoLayout L;
+    state_layout(h, &L);
+    // A load changes player positions: it PRODUCES the stair set of the next k_step (rg_state.h), like k_build and the debug descent.  The background
+    // generators (k_regen, its gate, rg_regen_lanes.hip) read and write only the spare view and the next-level request / structure words, none of which a
+    // load writes (it drops a restored env's structure with the same atomic AND as k_build): stream order is enough, nothing is drained.
+    h->S.stair_gen = h->stair_gen++;
+    rgk_state_load(&h->S, &L, h->io_desc, h->io_guard, ids, k, rec_dev, (uint32_t)rec_bytes, h->io_ok, h->io_mark, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->bound_valid = false;  // the bound observation tensor does not show the restored screens: its next call encodes every env
+    return 0;
+}
+
 int rg_debug_descend(rg_t *h) {
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->sub.empty()) {

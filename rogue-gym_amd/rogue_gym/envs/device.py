@@ -249,6 +249,63 @@ class HipVecRogueEnv:
         names = ("resets", "descents", "dist_maps", "inline_generations", "spares_taken", "redraws", "keys", "partial_maps_continued", "next_level_structures_used")
         return dict(zip(names, (int(v) for v in out)))
 
+    # ---- batched save / restore of game states (rg_state_save / rg_state_load; record layout: include/rogue_gym_hip.h) ----
+    @property
+    def state_bytes(self) -> int:
+        """R: bytes of one state record of this env batch (geometry, room grid and key-log capacity decide it)."""
+        return self._h.state_bytes()
+
+    def _state_ids(self, env_ids, unique):
+        """(pointer, count, on_device, keep-alive) of env_ids: None = every env in order; a list / numpy array (range-checked by the library) or a
+        device tensor (checked here)."""
+        torch = self.torch
+        if env_ids is None:
+            return None, self.num_envs, 0, None
+        if isinstance(env_ids, torch.Tensor) and env_ids.device.type == "cuda":
+            t = env_ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= self.num_envs):
+                raise ValueError("env ids out of range [0, %d)" % self.num_envs)
+            if unique and torch.unique(t).numel() != t.numel():
+                raise ValueError("load_state: duplicate env ids")
+            return C.c_void_p(t.data_ptr()), int(t.numel()), 1, t
+        if isinstance(env_ids, torch.Tensor):
+            env_ids = env_ids.numpy()
+        a = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
+        if unique and np.unique(a).size != a.size:
+            raise ValueError("load_state: duplicate env ids")
+        a = a.astype(np.int32)
+        return C.c_void_p(a.ctypes.data), int(a.size), 0, a
+
+    def save_state(self, env_ids=None):
+        """u8 [k, state_bytes] on this env's device: the state records of env_ids (default: every env, in order), asynchronously on the stream.
+        A record holds the env's whole running game -- grids, mirrors, dist cache, monsters, RNG streams, the episode's key log -- and not what
+        decides its future episodes (seed, spares): those belong to whichever slot it is loaded into."""
+        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
+        out = self.torch.empty((k, self.state_bytes), dtype=self.torch.uint8, device=self.device)
+        if k:
+            self._h.check(self._h.L.rg_state_save(self._h.h, ptr, k, on_dev, C.c_void_p(out.data_ptr())))
+        return out
+
+    def load_state(self, records, env_ids=None):
+        """Restore envs env_ids (default: every env, in order) from state records u8 [k, R] (save_state of this or another batch of the same config,
+        seed aside, or RogueEnv.save_state).  A restored env plays out the saved episode; when that ends it resets from its OWN seed.  A record that
+        does not fit leaves its env unchanged and makes check_errors() raise.  Returns the observation batch, re-encoded."""
+        torch = self.torch
+        if not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.dim() != 2 or records.device != self.device:
+            raise ValueError("load_state needs a uint8 tensor [k, record bytes] on %s" % (self.device,))
+        records = records.contiguous()
+        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=True)
+        if k != records.shape[0]:
+            raise ValueError("load_state: %d records for %d envs" % (records.shape[0], k))
+        if k:
+            self._h.check(self._h.L.rg_state_load(self._h.h, C.c_void_p(records.data_ptr()), int(records.shape[1]), ptr, k, on_dev))
+        return self._encode()
+
+    def clone_state(self, src_ids, dst_ids):
+        """Copy the states of src_ids into dst_ids (through a scratch record batch, so overlapping id sets are well defined): e.g. one
+        interesting env branched into many lanes, clone_state([17] * 4096, range(4096))."""
+        return self.load_state(self.save_state(src_ids), dst_ids)
+
     def enable_history(self, cap_per_env: int):
         self._h.check(self._h.L.rg_history_enable(self._h.h, int(cap_per_env)))
 

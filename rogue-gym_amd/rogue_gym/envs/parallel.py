@@ -5,6 +5,7 @@ string of N keys or N action indices and returns (states, rewards, dones, infos)
 post-reset state with `is_terminal` still true (python/src/thread_impls.rs:69-79); rewards are the clipped gold deltas.  The states come
 back as a StateBatch -- a sequence of PlayerState backed by one pinned host snapshot -- and `images()` turns a whole batch into a
 [N, C, H, W] array with one launch, so nothing in the per-step path is O(N) Python.
+Saving and restoring game states is not offered here: use HipVecRogueEnv.save_state / load_state (or RogueEnv's).
 """
 import json
 from typing import Dict, Iterable, List, Tuple, Union

@@ -188,6 +188,18 @@ class RogueEnv(Env):
         state = self.result = self.game.prev()
         return state, state.gold - purse, state.is_terminal, {}
 
+    def save_state(self) -> bytes:
+        """The running game as a state record (bytes): everything of the episode, its action log included.  A record also loads into a
+        HipVecRogueEnv of the same config (seed aside) and back."""
+        return self.game.save_state()
+
+    def load_state(self, state: bytes) -> PlayerState:
+        """Put the game back into a saved state and return that state (also `self.result`).  PlayerState values handed out earlier keep
+        what they were.  The seed stays this env's: the next reset builds from it."""
+        self.game.load_state(state)
+        state = self.result = self.game.prev()
+        return state
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

@@ -45,6 +45,7 @@ _INT_FUNCS = (
     "rg_reward", "rg_done", "rg_set_stair_reward", "rg_obs_bind", "rg_obs_gray", "rg_obs_symbol", "rg_obs_channels", "rg_fetch_states", "rg_encode_host", "rg_encode_host_batch", "rg_obs_host",
     "rg_host_alloc", "rg_dev_alloc", "rg_snapshot_take", "rg_dev_read", "rg_dev_read_rows", "rg_compact_record_bytes", "rg_pack_compact", "rg_expand_compact", "rg_comm_unique_id", "rg_comm_init", "rg_comm_destroy", "rg_comm_count", "rg_allgather_compact", "rg_status_vec", "rg_history_enable", "rg_history_keys",
     "rg_dump_history", "rg_counters", "rg_counters_ex", "rg_probe_sclk", "rg_dump_config", "rg_config_canonical", "rg_config_resolved", "rg_config_schema", "rg_debug_fetch", "rg_debug_descend", "rg_timing_enable", "rg_timing_read", "rg_timing_read_all", "rg_timing_read_samples",
+    "rg_state_record_bytes", "rg_state_save", "rg_state_load",
 )
 
 
@@ -102,10 +103,11 @@ def load_library():
         "rg_dump_config": [vp, i32, C.c_char_p, sz], "rg_config_canonical": [C.c_char_p, C.c_char_p, sz],
         "rg_config_resolved": [C.c_char_p, C.c_char_p, sz], "rg_config_schema": [C.c_char_p, sz, C.POINTER(sz)],
         "rg_debug_fetch": [vp, i32, C.POINTER(RgDebugState), vp], "rg_debug_descend": [vp],
+        "rg_state_record_bytes": [vp], "rg_state_save": [vp, vp, i32, i32, vp], "rg_state_load": [vp, vp, sz, vp, i32, i32],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
-    optional = {"rg_timing_read_samples", "rg_obs_bind"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+    optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -332,6 +334,41 @@ class _Handle:
         buf = (C.c_uint8 * max(1, n.value))()
         self.check(self.L.rg_history_keys(self.h, env, int(previous), buf, len(buf), C.byref(n)))
         return bytes(buf[: n.value])
+
+    def state_bytes(self):
+        """R: bytes of one state record of this handle (rg_state_record_bytes)."""
+        r = self.L.rg_state_record_bytes(self.h)
+        if r < 0:
+            self.check(1)
+        return r
+
+    def save_state_host(self, env=0):
+        """env's state record as bytes (rg_state_save into a pooled device buffer, one synchronous D2H copy); errors as rg_sync."""
+        r = self.state_bytes()
+        ptr = self.dev_pool.take(r)
+        try:
+            ids = (C.c_int32 * 1)(int(env))
+            self.check(self.L.rg_state_save(self.h, ids, 1, 0, C.c_void_p(ptr)))
+            buf = (C.c_uint8 * r)()
+            self.check(self.L.rg_dev_read(self.h, C.c_void_p(ptr), buf, r))
+            self.check(self.L.rg_sync(self.h))
+        finally:
+            self.dev_pool.give(ptr, r)
+        return bytes(buf)
+
+    def load_state_host(self, record, env=0):
+        """Restore env from a record made by save_state_host (or one row of HipVecRogueEnv.save_state); raises if it does not fit."""
+        import torch
+
+        data = bytes(record)
+        if len(data) < 64 or len(data) % 16:
+            raise ValueError("not a state record (%d bytes)" % len(data))
+        dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(torch.device("cuda", self.device))
+        torch.cuda.synchronize(dev.device)  # (the handle's stream is not torch's: the upload is complete before the load is enqueued)
+        ids = (C.c_int32 * 1)(int(env))
+        self.check(self.L.rg_state_load(self.h, C.c_void_p(dev.data_ptr()), len(data), ids, 1, 0))
+        self.epoch += 1
+        self.check(self.L.rg_sync(self.h))
 
     def dump_history(self, env, previous=False):
         need = C.c_size_t()
@@ -685,6 +722,17 @@ class GameState:
     def dump_history(self):
         return self._h.dump_history(0)
 
+    def save_state(self):
+        """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
+        after a load_state dumps the saved episode's keys."""
+        return self._h.save_state_host(0)
+
+    def load_state(self, state):
+        """Put the game back into a state saved by save_state (or by HipVecRogueEnv.save_state of a handle with the same config, seed aside).
+        The seed stays this game's: the next reset builds from it."""
+        self._h.load_state_host(state, 0)
+        self._prev = None
+
     def dump_config(self):
         buf = C.create_string_buffer(1 << 16)
         self._h.check(self._h.L.rg_dump_config(self._h.h, 0, buf, len(buf)))
@@ -697,7 +745,8 @@ class GameState:
 class ParallelGameState:
     """python/src/lib.rs:260-335: the reference's one-OS-thread-per-env ThreadConductor becomes one
     batched kernel launch; envs auto-reset on terminal (thread_impls.rs:69-79).  states/step/reset return a StateBatch
-    (a sequence of PlayerState, like the reference's Vec<PlayerState>)."""
+    (a sequence of PlayerState, like the reference's Vec<PlayerState>).  Saving and restoring game states is not offered here (it is on GameState
+    and HipVecRogueEnv)."""
 
     def __init__(self, max_steps, configs, device=None, history=0):
         self._h = _Handle(list(configs), max_steps, auto_reset=True, device=device)
