@@ -134,6 +134,19 @@ int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev);
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev);
 int rg_obs_channels(const rg_t *h, int symbol, uint32_t status_flag, int with_hist);
 
+/* Player-centred crop of the same image: out_dev = f32 [n_env][C][2*radius_y+1][2*radius_x+1] (16-byte aligned), C and plane order those of
+ * rg_obs_channels(h, kind, status_flag, with_hist), kind 0 = gray, 1 = one-hot symbol.  With P the image rg_obs_gray / rg_obs_symbol would write
+ * for env e now, padded on every side with the encoding of a blank cell ' ' (gray 0; one-hot: channel 0 = 1, as for every ' ' on the screen;
+ * history 0; status planes their constant value):  out[e][c][j][i] = P_padded[c][cy - radius_y + j][cx - radius_x + i], (cx, cy) the player's
+ * cell in screen coordinates -- bit-identical to slicing the padded full image.  The window has one size for every env, so this call also serves
+ * handles with config groups and mixed-size batches (the rg_obs_* calls refuse those); a config group with more symbols than env 0's is refused
+ * as by rg_obs_symbol.  Pending Redraws are drawn first (history stale / lag rules unchanged); a bound observation tensor (rg_obs_bind) is left
+ * as it is and its next call encodes every env.  centers_dev (nullable) = i32 [n_env][2]: (cy, cx) of each window's centre.
+ * InvalidTileError (a glyph without a symbol, e.g. 'Z', in the one-hot kind): raised, as by rg_obs_symbol, at the next rg_sync -- but only for
+ * such a glyph INSIDE the window; cells outside it are not read.  0 <= radius_y <= RG_MAX_H - 1 (47) and 0 <= radius_x <= RG_MAX_W - 1 (159):
+ * a window that size holds the whole screen from any player cell.  Other radii, another kind or a null out_dev: non-zero, with a message. */
+int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_flag, int with_hist, float *out_dev, int32_t *centers_dev);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

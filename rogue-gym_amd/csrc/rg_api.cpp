@@ -46,6 +46,8 @@ void rgk_pack(const RgState *S, int with_hist, uint8_t *out, hipStream_t st);
 void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int row_bytes, hipStream_t st);
 void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st);
 int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, int kind, float *out, uint32_t *err_any, int planes_sym, int bound, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
+                 uint32_t *err_any, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -773,6 +775,34 @@ int rg_obs_bind(rg_t *h, int kind, uint32_t status_flag, int with_hist, float *o
     }
     h->S.gray_lut = h->gray_lut_mem;
     h->bound_out = out_dev; h->bound_kind = kind; h->bound_valid = false; h->bound_steps = 0;
+    return 0;
+}
+int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_flag, int with_hist, float *out_dev, int32_t *centers_dev) {
+    if (kind != 0 && kind != 1) { h->err = "rg_obs_crop: kind must be 0 (gray) or 1 (symbol), got " + std::to_string(kind); return 1; }
+    if (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1) {
+        h->err = "rg_obs_crop: radii must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) +
+                 ", got (" + std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
+        return 1;
+    }
+    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = "rg_obs_crop: out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group crops its envs straight into the handle's tensor (RgState::ext): the window has one size for every env,
+                            // so a mixed-size batch is served too
+        for (rg_handle *sh : h->sub)
+            if (kind && sh->cfg.symbols > h->planes_sym) {
+                h->err = "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
+                         "), which sets the channel count (python/src/lib.rs:281-285)";
+                return 1;
+            }
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, rg_obs_crop(sh, kind, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev));
+        return 0;
+    }
+    if (flush_render(h)) return 1;  // (pending Redraws drawn by k_render: a bound observation tensor is then re-encoded in full by its next call)
+    if (!rgk_obs_crop(&h->S, &h->cfg, kind, radius_y, radius_x, status_flag & 0x1ffu, with_hist ? 1 : 0, h->planes_sym, out_dev, centers_dev, h->d_err, h->stream)) {
+        h->err = "rg_obs_crop: window too large";
+        return 1;
+    }
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }

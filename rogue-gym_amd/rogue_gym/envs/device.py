@@ -6,6 +6,7 @@ ranks in contiguous index blocks and `all_gather_obs()` assembles the whole-job 
 """
 import ctypes as C
 import json
+import operator
 from typing import Iterable, Optional
 
 import numpy as np
@@ -27,11 +28,28 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False):
+                 persistent_obs: bool = False, crop=None):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
-        must not write to `self.obs`."""
+        must not write to `self.obs`.
+
+        crop (None, r or (ry, rx)): `self.obs` is the player-centred window f32 [N, C, 2ry+1, 2rx+1] of the image instead of the whole screen, padded
+        with blank cells past the screen edge (rg_obs_crop), and `self.crop_center` i32 [N, 2] holds each window's centre (y, x), rewritten with every
+        observation.  The window has one size for every env, so a batch whose envs differ in screen size can be built too.  Not with persistent_obs."""
         import torch
+
+        if crop is not None:
+            if persistent_obs:
+                raise ValueError("crop and persistent_obs cannot be combined: the bound observation tensor is the whole screen")
+            try:
+                ry, rx = (crop, crop) if not isinstance(crop, (tuple, list)) else crop
+                ry, rx = operator.index(ry), operator.index(rx)
+            except (TypeError, ValueError):
+                ry = rx = -1
+            if ry < 0 or rx < 0:
+                raise ValueError("crop must be None, an int >= 0 or a pair (ry, rx) of ints >= 0, got %r" % (crop,))
+            crop = (ry, rx)
+        self.crop = crop
 
         self.torch = torch
         cfgs = [d if isinstance(d, str) else json.dumps(d) for d in config_dicts]
@@ -47,7 +65,9 @@ class HipVecRogueEnv:
             self._action_keys = torch.tensor([ord(a) for a in self.ACTIONS], dtype=torch.uint8, device=self.device)
             self._sym = image_setting.dungeon == DungeonType.SYMBOL
             self.channels = L.rg_obs_channels(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist))
-            self.obs = torch.empty((self.num_envs, self.channels, self.height, self.width), dtype=torch.float32, device=self.device)
+            oh, ow = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
+            self.obs = torch.empty((self.num_envs, self.channels, oh, ow), dtype=torch.float32, device=self.device)
+            self.crop_center = None if crop is None else torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
             p = C.c_void_p()
             self._h.check(L.rg_reward(h, C.byref(p)))
             self.reward = torch.as_tensor(_DevArray(p.value, (self.num_envs,), "<f4"), device=self.device)
@@ -57,8 +77,9 @@ class HipVecRogueEnv:
             self.flags = torch.as_tensor(_DevArray(p.value, (self.num_envs,), "<i4"), device=self.device)
             self._h.check(L.rg_status(h, C.byref(p)))
             self.status = torch.as_tensor(_DevArray(p.value, (self.num_envs, 10), "<i4"), device=self.device)
-            self._h.check(L.rg_screen(h, C.byref(p)))
-            self._screen = torch.as_tensor(_DevArray(p.value, (self.num_envs, self.height, self.width), "|u1"), device=self.device)
+            self._screen = None
+            if crop is None:  # (with a crop the batch may mix screen sizes: no screen tensor then, `screen` raises)
+                self._screen_view()
         self._scratch = {}
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
@@ -69,12 +90,21 @@ class HipVecRogueEnv:
     def screen(self):
         """u8 [num_envs, H, W] glyph mirror (PlayerState.map of every env).  Reading it flushes the pending render (a batch with several
         config groups assembles the groups' screens first); the tensor itself is the same device buffer every time."""
+        return self._screen_view()
+
+    def _screen_view(self):
         p = C.c_void_p()
         self._h.check(self._h.L.rg_screen(self._h.h, C.byref(p)))
+        if self._screen is None:
+            self._screen = self.torch.as_tensor(_DevArray(p.value, (self.num_envs, self.height, self.width), "|u1"), device=self.device)
         return self._screen
 
     def _encode(self):
         L, h = self._h.L, self._h.h
+        if self.crop is not None:
+            self._h.check(L.rg_obs_crop(h, int(self._sym), self.crop[0], self.crop[1], self.image_setting.status.value, int(self.image_setting.includes_hist),
+                                        C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.crop_center.data_ptr())))
+            return self.obs
         fn = L.rg_obs_symbol if self._sym else L.rg_obs_gray
         self._h.check(fn(h, self.image_setting.status.value, int(self.image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         return self.obs
@@ -95,7 +125,7 @@ class HipVecRogueEnv:
         if keys.dtype != self.torch.uint8 or keys.device != self.device or not keys.is_contiguous() or keys.numel() != self.num_envs:
             raise ValueError("step_keys needs a contiguous uint8 tensor of %d keys on %s, got %s %s on %s"
                              % (self.num_envs, self.device, tuple(keys.shape), keys.dtype, keys.device))
-        if self._sym:
+        if self._sym or self.crop is not None:
             self._h.check(self._h.L.rg_step(self._h.h, C.c_void_p(keys.data_ptr()), 1))
             obs = self._encode()
         else:  # the step and the gray observation as one call: fused into one kernel where the config allows it (rg_step_obs_gray)
