@@ -575,6 +575,9 @@ int rg_reset(rg_t *h) {
     { TimedLaunch t(h, 3); rgk_build(&h->S, &h->cfg, h->stream); }  // (k_build and a k_regen in flight share only the atomically advanced build counters)
     HIPCHK(h, hipGetLastError());
     h->render_pending = true;
+    // every env now shows a new level but the in-place pass of a bound observation tensor would serve only the last k_step's list: its next call
+    // encodes every env (as after rg_state_load)
+    h->bound_valid = false;
     return 0;
 }
 

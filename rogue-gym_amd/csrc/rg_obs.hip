@@ -443,10 +443,14 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs(RgState S, RgConfig c, uint
             }
             if (KIND == 1 && bad) { atomicOr(&S.flags[e], RG_FLAG_ERR_TILE); atomicOr(err_any, RG_FLAG_ERR_TILE); }
             const uint32_t seen = BOUND ? RG_FLAG_SCR_CHANGED : 0u;  // (the bound tensor now shows this env's screen)
-            if (redraw && lt == 0)  // a stale Redraw leaves the history mirror one level behind (k_step refreshes it before the next descent)
-                S.flags[e] = (fl & ~(seen | RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fl & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY))) |
-                             ((fl & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u) | (KIND == 1 && bad ? RG_FLAG_ERR_TILE : 0);
-            else if (BOUND && !redraw && lt == 0) atomicAnd(&S.flags[e], ~RG_FLAG_SCR_CHANGED);  // (atomic: the one-hot kind ORs its error bit into the same word)
+            if (redraw && lt == 0) {  // a stale Redraw leaves the history mirror one level behind (k_step refreshes it before the next descent)
+                const uint32_t clr = seen | RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fl & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY);
+                const uint32_t set = (fl & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u;
+                if (KIND == 1) {  // atomic: the other lanes OR their ERR_TILE into the same word (a plain store of this lane's view dropped theirs)
+                    atomicAnd(&S.flags[e], ~clr);
+                    if (set) atomicOr(&S.flags[e], set);
+                } else S.flags[e] = (fl & ~clr) | set;
+            } else if (BOUND && !redraw && lt == 0) atomicAnd(&S.flags[e], ~RG_FLAG_SCR_CHANGED);  // (atomic: the one-hot kind ORs its error bit into the same word)
         }
     }
 }

@@ -128,3 +128,18 @@ def custom_enemy_config(base):
         10,  # kestrel
     ], "appear_rate_gold": 90, "appear_rate_nogold": 60}
     return cfg
+
+
+def crop_window(img, cy, cx, ry, rx, kind, planes, with_hist):
+    """The [C, 2ry+1, 2rx+1] window of one env's image `img` [C, H, W] centred on (cy, cx), padded past the screen edge with the encoding of a
+    blank cell ' ': gray 0, one-hot channel 0 = 1 and the other symbol channels 0, every status plane its constant, history 0.  `planes` is the
+    number of dungeon channels (1 for gray, the symbol count for one-hot)."""
+    c, h, w = img.shape
+    pad = np.zeros((c, h + 2 * ry, w + 2 * rx), img.dtype)
+    if kind:
+        pad[0] = 1.0
+    nst = c - planes - (1 if with_hist else 0)
+    if nst > 0:
+        pad[planes:planes + nst] = img[planes:planes + nst, :1, :1]
+    pad[:, ry:ry + h, rx:rx + w] = img
+    return pad[:, cy:cy + 2 * ry + 1, cx:cx + 2 * rx + 1].copy()

@@ -1,5 +1,5 @@
 """Player-centred cropped observations (rg_obs_crop; HipVecRogueEnv(crop=...)).  The expected crop is always built in torch from the library's own full
-encode (which the oracle pins): the full image padded with the encoding of a blank cell ' ', then gathered at the window centres.  Benchmark shape,
+encode (which tests/test_gpu_obs_oracle.py pins to the oracle at every step; that module also checks the crop itself against the oracle): the full image padded with the encoding of a blank cell ' ', then gathered at the window centres.  Benchmark shape,
 the 80x24 dungeon with descents, edges, pending Redraws, the bound observation tensor, config groups and mixed sizes, refusals and the 'Z' rule."""
 import ctypes as C
 
