@@ -73,3 +73,15 @@ torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print("HipVecRogueEnv(persistent_obs=True): %.0f M env-steps/s" % (n * 500 / dt / 1e6))
 venv.close()
+
+# 3c. the observation in the type the learner consumes: a bf16 image written by the encode pass itself (bit-identical to obs.to(torch.bfloat16)), and the
+#     screen as uint8 symbol ids feeding an nn.Embedding-style lookup ---------------------------------------------------------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, obs_dtype=torch.bfloat16)
+obs, reward, done = venv.step(actions[0, :4096])
+print("HipVecRogueEnv(obs_dtype=torch.bfloat16): obs %s %s" % (tuple(obs.shape), obs.dtype))
+venv.close()
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.SYMBOL, StatusFlag.EMPTY, False), device=0, symbol_ids=True)
+obs, reward, done = venv.step(actions[0, :4096])
+table = torch.randn(venv.symbols, 8, device=venv.device)
+print("HipVecRogueEnv(symbol_ids=True): obs %s %s -> embedded %s" % (tuple(obs.shape), obs.dtype, tuple(table[obs[:, 0].long()].shape)))
+venv.close()

@@ -147,6 +147,33 @@ int rg_obs_channels(const rg_t *h, int symbol, uint32_t status_flag, int with_hi
  * a window that size holds the whole screen from any player cell.  Other radii, another kind or a null out_dev: non-zero, with a message. */
 int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_flag, int with_hist, float *out_dev, int32_t *centers_dev);
 
+/* TYPED observations: the same whole-screen images in the element type a learner consumes, and the screen as a plane of symbol ids.
+ *   kind 0 = gray, 1 = one-hot symbol, dtype RG_OBS_F16 / RG_OBS_BF16: out_dev = T [n_env][C][H][W], C and plane order those of rg_obs_channels.
+ *     Every element is the element rg_obs_gray / rg_obs_symbol would write for the same state, rounded to T by round-to-nearest-even (overflow to
+ *     infinity in F16: a status plane such as gold can exceed 65 504) -- bit-identical to f32_image.to(T).  The gray value keeps its single f32 division
+ *     (python/src/lib.rs:84) and is rounded afterwards.  dtype RG_OBS_F32 with kinds 0 / 1 is accepted and is exactly the rg_obs_gray / rg_obs_symbol call.
+ *   kind 2 = symbol ids, dtype RG_OBS_U8 only: out_dev = u8 [n_env][1 + with_hist][H][W].  Plane 0 is Symbol::from_tile of each screen glyph
+ *     (core/src/symbol.rs:17-40; 255 for a glyph without a symbol): wherever the one-hot image is valid it equals onehot.argmax(1), and ' ' is 0 --
+ *     what an embedding layer indexes with.  The history plane, if asked for, is 0 / 1.  InvalidTileError as rg_obs_symbol: an id >= symbols - 1 sets
+ *     RG_FLAG_ERR_TILE on the env and is reported by the next rg_sync; the byte written is still the id.  status_flag must be 0 (status values do not
+ *     fit a byte; the `status` mirror is a device tensor already).
+ * Side effects are those of the f32 call: pending Redraws are drawn at this call (screen and history mirrors, history stale / lag rules unchanged),
+ * so a handle that only makes typed calls has the same mirrors and flag words, step for step, as one that only makes f32 calls.  A bound
+ * observation tensor (rg_obs_bind) is left as it is and its next call encodes every env.  The pass is timing kernel 2 (rg_timing_*), like the f32 pass.
+ * Refused, non-zero with a message naming the argument: out_dev null or not 16-byte aligned; an unknown kind or dtype; kind 2 with another dtype,
+ * RG_OBS_U8 with kinds 0 / 1; status planes with kind 2; H*W not a multiple of 8 (16 for RG_OBS_U8: a lane writes whole 16-byte pieces of a plane,
+ * and there are NO fallback kernels for other grids); handles with config groups or mixed sizes (as rg_obs_bind).  A refused call launches nothing.
+ * rg_step_obs_typed = rg_step + rg_obs_typed in one trip through the binding (what rg_step_obs_gray is for f32); a refused call does not step.
+ * rg_obs_dtype_bytes: the element size, 4 / 2 / 2 / 1, or -1 for anything else; stateless, needs no device.
+ * Not typed (f32 only): the crop (rg_obs_crop), the bound tensor (rg_obs_bind), rg_expand_compact, rg_obs_host, rg_encode_host[_batch]. */
+#define RG_OBS_F32  0
+#define RG_OBS_F16  1   /* IEEE binary16 */
+#define RG_OBS_BF16 2
+#define RG_OBS_U8   3   /* kind 2 only */
+int rg_obs_dtype_bytes(int dtype);
+int rg_obs_typed(rg_t *h, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev);
+int rg_step_obs_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

@@ -46,6 +46,9 @@ void rgk_pack(const RgState *S, int with_hist, uint8_t *out, hipStream_t st);
 void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int row_bytes, hipStream_t st);
 void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st);
 int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, int kind, float *out, uint32_t *err_any, int planes_sym, int bound, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st);
+int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any, hipStream_t st, hipEvent_t ev0,
+                  hipEvent_t ev1);
 int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
                  uint32_t *err_any, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
@@ -807,6 +810,57 @@ int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_f
     }
     HIPCHK(h, hipGetLastError());
     return 0;
+}
+// Typed observations (f16 / bf16 images, u8 symbol ids).  typed_check: every refusal, before anything is launched (or stepped).
+int rg_obs_dtype_bytes(int dtype) { return dtype == RG_OBS_F32 ? 4 : (dtype == RG_OBS_F16 || dtype == RG_OBS_BF16) ? 2 : dtype == RG_OBS_U8 ? 1 : -1; }
+static int typed_check(rg_t *h, const char *what, int kind, int dtype, uint32_t status_flag, const void *out_dev) {
+    const std::string w = std::string(what) + ": ";
+    if (kind < 0 || kind > 2) { h->err = w + "kind must be 0 (gray), 1 (symbol) or 2 (symbol ids), got " + std::to_string(kind); return 1; }
+    if (rg_obs_dtype_bytes(dtype) < 0) { h->err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1), RG_OBS_BF16 (2) or RG_OBS_U8 (3), got " + std::to_string(dtype); return 1; }
+    if (kind == 2 && dtype != RG_OBS_U8) { h->err = w + "kind 2 (symbol ids) takes dtype RG_OBS_U8 only, got dtype " + std::to_string(dtype); return 1; }
+    if (kind != 2 && dtype == RG_OBS_U8) { h->err = w + "dtype RG_OBS_U8 is for kind 2 (symbol ids) only, got kind " + std::to_string(kind); return 1; }
+    if (kind == 2 && (status_flag & 0x1ffu)) { h->err = w + "status_flag must be 0 for kind 2 (status values do not fit a byte; read the status mirror)"; return 1; }
+    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    if (dtype == RG_OBS_F32) return 0;  // (the f32 call: its own rules)
+    if (!h->sub.empty() || h->mixed) { h->err = w + "not for a handle with config groups or mixed sizes"; return 1; }
+    const int cells = dtype == RG_OBS_U8 ? 16 : 8;
+    if (h->S.hw % cells) {
+        h->err = w + "H*W must be a multiple of " + std::to_string(cells) + " for this dtype (a lane writes whole 16-byte pieces of a plane), got " + std::to_string(h->cfg.height) +
+                 " x " + std::to_string(h->cfg.width);
+        return 1;
+    }
+    return 0;
+}
+static int obs_typed_checked(rg_t *h, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev) {
+    if (dtype == RG_OBS_F32) return obs_common(h, status_flag, with_hist, kind, static_cast<float *>(out_dev));
+    HIPCHK(h, hipSetDevice(h->device));
+    // pending Redraws: drawn first by the Redraw sweep (k_redraw: the staged path of the f32 pass without its encode), by k_render where that does not apply
+    if (h->render_pending) {
+        bool swept;
+        { TimedLaunch t(h, 1); swept = rgk_redraw(&h->S, &h->cfg, h->stream) != 0; if (!swept) t.cancel(); }
+        if (swept) {
+            HIPCHK(h, hipGetLastError());
+            h->render_pending = false;
+            h->bound_valid = false;  // (Redraw flags were consumed without the bound observation tensor being written: its next call encodes every env)
+        } else if (flush_render(h)) return 1;
+    }
+    {
+        TimedLaunch t(h, 2, true);
+        if (!rgk_obs_typed(&h->S, &h->cfg, kind, dtype, status_flag & 0x1ffu, with_hist ? 1 : 0, h->planes_sym, out_dev, h->d_err, h->stream, t.start_ev(), t.stop_ev())) {
+            t.cancel();
+            h->err = "rg_obs_typed: grid not supported";
+            return 1;
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_obs_typed(rg_t *h, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev) {
+    return typed_check(h, "rg_obs_typed", kind, dtype, status_flag, out_dev) ? 1 : obs_typed_checked(h, kind, dtype, status_flag, with_hist, out_dev);
+}
+int rg_step_obs_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev) {
+    if (typed_check(h, "rg_step_obs_typed", kind, dtype, status_flag, out_dev)) return 1;
+    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : obs_typed_checked(h, kind, dtype, status_flag, with_hist, out_dev);
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }

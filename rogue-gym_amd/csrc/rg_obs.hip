@@ -2,6 +2,7 @@
 //
 //   k_obs<gray|symbol> : fused RunTime::draw_screen (mirror refresh of Redraw envs) + PlayerState::{gray,symbol}_image
 //   k_obs_stream       : the same for the plain gray image of grids of at most 512 cells, streamed in runs of envs
+//   k_redraw + k_obs_typed : the same images in f16 / bf16 elements, and the screen as a u8 plane of symbol ids (rg_obs_typed)
 //   k_render, k_gray, k_symbol, k_encode_scalar : unfused fallbacks
 //
 // Built as its own translation unit with -Os: these kernels are bandwidth/latency-bound and measurably faster with less
@@ -833,6 +834,209 @@ __global__ void __launch_bounds__(WAVE) k_obs_crop(const uint16_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_redraw: RunTime::draw_screen of the envs with a pending Redraw into the screen / history mirrors, and nothing else -- the staged path of k_obs without
+// its encode, for the typed pass below (which then streams every env from its mirror).  Same mirrors, history rule and flag words as k_obs leaves.
+// ---------------------------------------------------------------------------------------------
+// A block owns REDRAW_RUN consecutive envs per iteration: one coalesced load of their flag words (the next run's is requested before this run is drawn), a
+// ballot, and the few envs with the flag set (2 % of a random policy's step: k_step keeps the mirror itself on an ordinary turn) are drawn one at a time by the
+// whole block.  k_render walks one env per block iteration and serves every caller and grid; this pass costs a flag sweep where nothing is pending.
+#define REDRAW_RUN 8
+__global__ void __launch_bounds__(OBS_THREADS) k_redraw(RgState S, RgConfig c) {
+    extern __shared__ __align__(16) uint8_t scr[];      // the staged screen [HW]
+    __shared__ uint8_t mtile[RG_MAX_ENEMY_KINDS + 6];    // monster type -> glyph
+    __shared__ ObsTabs tb;                               // the env's observation record
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), B = blockDim.x, W = c.width, HW = W * c.height, n = S.n;
+    const int nrooms = c.room_num_x * c.room_num_y, rec_words = RG_OBS_REC_WORDS(nrooms);
+    for (int g = tid; g < RG_MAX_ENEMY_KINDS + 6; g += B) mtile[g] = c.mon[g].tile;
+    const int nruns = (n + REDRAW_RUN - 1) / REDRAW_RUN;
+    auto load_flags = [&](int r) -> uint32_t {  // lane i of every wave: env i of the run
+        const int e = r * REDRAW_RUN + lane;
+        return lane < REDRAW_RUN && e < n ? S.flags[e] : 0u;
+    };
+    uint32_t fl = load_flags(blockIdx.x);
+    for (int r = blockIdx.x; r < nruns; r += gridDim.x) {
+        const uint32_t fl_nxt = load_flags(r + gridDim.x);
+        uint64_t rmask = __ballot(fl & RG_FLAG_REDRAW);  // (the same in every wave of the block)
+        while (rmask) {
+            const int i = __builtin_ctzll(rmask);
+            rmask &= rmask - 1;
+            const int e = r * REDRAW_RUN + i;
+            const uint32_t fle = __builtin_amdgcn_readlane(fl, i);
+            // the history plane is rewritten only when the visited set changed since it was last written (k_step: HIST_DIRTY), never on a stale Redraw
+            const bool upd_hist = !(fle & RG_FLAG_HIST_STALE) && (fle & RG_FLAG_HIST_DIRTY);
+            lds_barrier();  // the previous env's LDS reads done (and, the first time, the glyph table written)
+            for (int j = tid; j < rec_words; j += B) tb.w[j] = S.obs_rec[(size_t)e * rec_words + j];
+            const uint4 *cell4 = reinterpret_cast<const uint4 *>(S.cell + (size_t)e * HW);
+            uint2 *hist8 = reinterpret_cast<uint2 *>(S.hist + (size_t)e * HW);
+            for (int j = tid; j < (HW >> 3); j += B) {
+                uint32_t g[2], hb[2];
+                draw_cells8(cell4[j], j, W, HW, g, hb);
+                reinterpret_cast<uint2 *>(scr)[j] = make_uint2(g[0], g[1]);
+                if (upd_hist) hist8[j] = make_uint2(hb[0], hb[1]);
+            }
+            lds_barrier();
+            // entity overlays; draw priority monster < gold < player (core/src/lib.rs:271-283), as in k_obs
+            const uint32_t ppos = tb.w[nrooms];
+            const int px = POS_X(ppos), py = POS_Y(ppos);
+            for (int rm = tid; rm < nrooms; rm += B) {
+                const uint32_t mw = tb.w[rm];
+                if ((mw >> 24) & MF_ALIVE) {
+                    const int x = POS_X(mw), y = POS_Y(mw);
+                    const uint32_t under = scr[y * W + x];
+                    if (monster_shown(c, &tb, nrooms, px, py, x, y) && (under & 0x80u) && under != (0x80u | '*')) scr[y * W + x] = (uint8_t)(0x80u | mtile[(mw >> 16) & 0xff]);
+                }
+            }
+            lds_barrier();
+            if (tid == 0 && (scr[py * W + px] & 0x80u)) scr[py * W + px] = (uint8_t)(0x80u | '@');
+            lds_barrier();
+            uint2 *m8 = reinterpret_cast<uint2 *>(S.screen + (size_t)e * HW);
+            for (int j = tid; j < (HW >> 3); j += B) {
+                const uint2 g = reinterpret_cast<const uint2 *>(scr)[j];
+                m8[j] = make_uint2(g.x & 0x7f7f7f7fu, g.y & 0x7f7f7f7fu);
+            }
+            if (tid == 0)  // (k_obs: a stale Redraw leaves the history mirror one level behind; k_step refreshes it before the next descent)
+                S.flags[e] = (fle & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fle & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY))) |
+                             ((fle & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u);
+        }
+        fl = fl_nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_obs_typed: the whole-screen images in 16-bit elements, and the screen as a plane of symbol ids (rg_obs_typed).  KIND 0 gray / 1 one-hot with
+// DT = RG_OBS_F16 / RG_OBS_BF16: every element is the f32 element of k_obs rounded to T (round to nearest even).  KIND 2 with RG_OBS_U8: Symbol::from_tile
+// of every glyph (+ the 0 / 1 history plane).  The mirrors are current (k_redraw, or k_render, ran first on the stream): this pass only reads them.
+// ---------------------------------------------------------------------------------------------
+// A lane's ITEM is one 16-byte piece of every plane of one env: 8 consecutive cells of a 16-bit type (one uint2 of mirror in), 16 cells of u8 (one uint4 in);
+// an env is Q = H*W / cells items.  A block of `B` threads owns a RUN of `run` consecutive envs per iteration -- their mirrors are one contiguous stretch of the
+// screen array, so item j of the run is simply mirror piece j -- with up to OBS_T_ITEMS items per thread (host: run * Q <= OBS_T_ITEMS * B): four envs per wave
+// on the 32x16 grid, four envs per 256-thread block on 80x24.  Lanes are contiguous in j, so every wave-level store covers whole lines of a plane.  Persistent
+// blocks, one run ahead: the next run's mirror pieces are requested before this run's stores issue (k_obs_stream's scheme).  Status planes need the env to be
+// block-uniform: the host gives such a launch run = 1, and the nine values are then scalar loads, converted once per item.
+// No value is converted per cell: gray goes through a 128-entry LDS table of already rounded 16-bit values (one f32 division and one rounding per glyph and
+// block), one-hot and history planes select between the two constants 1.0 / 0 of the type, packed two per register.
+// (The kernel takes the few arrays it reads, not RgState / RgConfig by value, and draws nothing: with the Redraw path of k_obs fused in, every instance
+// spilled 36 to 60 SGPRs.)
+#define OBS_T_ITEMS 4
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_obs16(u4v *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    u4v v = {a, b, c, d};
+    __builtin_nontemporal_store(v, p);
+}
+// the 16 bits of T nearest to the finite f32 `f` (ties to even; binary16 overflows to infinity): what torch.Tensor.to(T) gives
+template <int DT>
+__device__ __forceinline__ uint32_t cvt16(float f) {
+    if (DT == RG_OBS_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);  // v_cvt_f16_f32
+    const uint32_t u = __float_as_uint(f);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// bytes of `w` that are not zero -> 1
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
+
+template <int KIND, int DT>
+__global__ void __launch_bounds__(OBS_THREADS) k_obs_typed(const uint8_t *__restrict__ screen, const uint8_t *__restrict__ hist, const int32_t *__restrict__ status,
+                                                          uint32_t *__restrict__ flags, uint32_t *__restrict__ err_any, int n, int hw, int symbols, int planes,
+                                                          uint32_t sflag, int with_hist, int run, u4v *__restrict__ out) {
+    constexpr int CW = DT == RG_OBS_U8 ? 4 : 2;  // mirror words per item
+    typedef uint32_t wv __attribute__((ext_vector_type(CW)));
+    constexpr uint32_t ONE = DT == RG_OBS_F16 ? 0x3C00u : 0x3F80u;  // 1.0
+    __shared__ uint16_t lut16[128];  // glyph -> gray value, rounded (KIND 0)
+    __shared__ uint8_t luts[128];    // glyph -> symbol id
+    const int tid = threadIdx.x, B = blockDim.x, Q = hw / (4 * CW);
+    for (int g = tid; g < 128; g += B) {
+        const uint32_t sy = tile_to_sym((uint32_t)g);
+        luts[g] = (uint8_t)sy;
+        if (KIND == 0) lut16[g] = (uint16_t)cvt16<DT>((float)(uint8_t)sy / (float)(uint8_t)symbols);  // python/src/lib.rs:84 (the same single f32 division), then rounded
+    }
+    const int nplanes = planes + __popc(sflag) + (with_hist ? 1 : 0);
+    const uint32_t smax = (uint32_t)symbols - 1;  // construct_symbol_map fills channels 0..symbols-2 (symbol.rs:51-71)
+    // item k of this thread: piece j = tid + k B of the run = piece ql[k] of the run's env el[k] (the same in every run: divided once)
+    const int per_run = run * Q;
+    int el[OBS_T_ITEMS], ql[OBS_T_ITEMS];
+#pragma unroll
+    for (int k = 0; k < OBS_T_ITEMS; k++) {
+        const int j = tid + k * B;
+        el[k] = j < per_run ? j / Q : -1;
+        ql[k] = el[k] < 0 ? 0 : j - el[k] * Q;
+    }
+    struct Run { wv w[OBS_T_ITEMS], h[OBS_T_ITEMS]; };
+    auto load_run = [&](int r, Run &R) {  // zeros past the run and past the batch
+        const int base = r * run;
+        const wv *m = reinterpret_cast<const wv *>(screen + (size_t)base * hw), *hm = reinterpret_cast<const wv *>(hist + (size_t)base * hw);
+#pragma unroll
+        for (int k = 0; k < OBS_T_ITEMS; k++) {
+            const bool ok = el[k] >= 0 && base + el[k] < n;
+            R.w[k] = ok ? m[tid + k * B] : (wv)0u;
+            R.h[k] = ok && with_hist ? hm[tid + k * B] : (wv)0u;
+        }
+    };
+    auto gray2 = [&](uint32_t w, int hi) -> uint32_t {  // cells 2 hi, 2 hi + 1 of a mirror word
+        return (uint32_t)lut16[(w >> (16 * hi)) & 0x7f] | ((uint32_t)lut16[(w >> (16 * hi + 8)) & 0x7f] << 16);
+    };
+    auto one2 = [&](bool a, bool b) -> uint32_t { return (a ? ONE : 0u) | (b ? ONE << 16 : 0u); };
+    lds_barrier();  // the tables are ready
+    const int nruns = (n + run - 1) / run;
+    Run cur;
+    load_run(blockIdx.x, cur);
+    for (int r = blockIdx.x; r < nruns; r += gridDim.x) {
+        Run nxt;
+        load_run(r + gridDim.x, nxt);
+        const int base = r * run;
+#pragma unroll
+        for (int k = 0; k < OBS_T_ITEMS; k++) {
+            const int e = base + el[k];
+            if (el[k] < 0 || e >= n) continue;
+            u4v *o = out + (size_t)e * nplanes * Q + ql[k];
+            uint32_t w[CW], h[CW];
+#pragma unroll
+            for (int t = 0; t < CW; t++) { w[t] = cur.w[k][t]; h[t] = cur.h[k][t]; }
+            bool bad = false;  // a glyph without a symbol (InvalidTileError, e.g. 'Z')
+            if (KIND == 0) {
+                store_obs16(o, gray2(w[0], 0), gray2(w[0], 1), gray2(w[1], 0), gray2(w[1], 1));
+            } else if (KIND == 1) {
+                uint32_t s[8];
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    s[t] = luts[(w[t >> 2] >> ((t & 3) * 8)) & 0x7f];
+                    bad = bad || s[t] >= smax;
+                }
+                for (uint32_t ch = 0; ch < smax; ch++)
+                    store_obs16(o + (size_t)ch * Q, one2(s[0] == ch, s[1] == ch), one2(s[2] == ch, s[3] == ch), one2(s[4] == ch, s[5] == ch), one2(s[6] == ch, s[7] == ch));
+                for (uint32_t ch = smax; ch < (uint32_t)planes; ch++) store_obs16(o + (size_t)ch * Q, 0u, 0u, 0u, 0u);  // the last channel is never set
+            } else {
+                uint32_t id[CW];
+#pragma unroll
+                for (int t = 0; t < CW; t++) {
+                    const uint32_t a = luts[w[t] & 0x7f], b = luts[(w[t] >> 8) & 0x7f], c = luts[(w[t] >> 16) & 0x7f], d = luts[(w[t] >> 24) & 0x7f];
+                    bad = bad || a >= smax || b >= smax || c >= smax || d >= smax;
+                    id[t] = a | (b << 8) | (c << 16) | (d << 24);
+                }
+                store_obs16(o, id[0], id[1], id[CW - 2], id[CW - 1]);  // (CW = 4 here: the u8 type is the only one of this kind)
+            }
+            int p = planes;
+            if (KIND != 2 && sflag) {
+                const int eu = __builtin_amdgcn_readfirstlane(e);  // (run = 1 with status planes: the block's one env)
+                for (int b = 0; b < 9; b++)
+                    if (sflag & (1u << b)) {
+                        const uint32_t v = cvt16<DT>((float)status[(size_t)eu * 10 + kStatusIdx[b]]) * 0x10001u;
+                        store_obs16(o + (size_t)p * Q, v, v, v, v);
+                        p++;
+                    }
+            }
+            if (with_hist) {
+                if (KIND == 2) store_obs16(o + (size_t)p * Q, nonzero_bytes(h[0]), nonzero_bytes(h[1]), nonzero_bytes(h[CW - 2]), nonzero_bytes(h[CW - 1]));
+                else
+                    store_obs16(o + (size_t)p * Q, one2(h[0] & 0xffu, h[0] & 0xff00u), one2(h[0] & 0xff0000u, h[0] >> 24), one2(h[1] & 0xffu, h[1] & 0xff00u),
+                                one2(h[1] & 0xff0000u, h[1] >> 24));
+            }
+            // (atomic, as k_obs<1>: the lanes of an env share its flag word)
+            if (KIND != 0 && bad) { atomicOr(&flags[e], RG_FLAG_ERR_TILE); atomicOr(err_any, RG_FLAG_ERR_TILE); }
+        }
+        cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host-callable launchers (used by rg_api.cpp)
 // ---------------------------------------------------------------------------------------------
 static void host_magic(RgCropArgs &a, int which, uint32_t d) {  // (crop kernel: mdiv)
@@ -965,6 +1169,44 @@ int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, 
                                  c->symbols, a, out, centers, err_any);
     else hipLaunchKernelGGL(k_obs_crop<0>, dim3(blocks), dim3(WAVE), smem, st, S->p_pos, S->status, S->screen, S->hist, S->flags, S->ext, S->n, c->width, c->height,
                             c->symbols, a, out, centers, err_any);
+    return 1;
+}
+// the Redraw sweep in front of the typed pass (k_redraw): returns 0 where it does not apply (more rooms than the LDS overlay tables hold: the caller runs k_render)
+int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st) {
+    const int hw = c->width * c->height;
+    if ((hw & 7) || c->room_num_x * c->room_num_y > RG_OBS_MAX_ROOMS || !S->obs_rec) return 0;
+    int B = ((hw / 8 + WAVE - 1) / WAVE) * WAVE;
+    if (B > OBS_THREADS) B = OBS_THREADS;
+    const int nruns = (S->n + REDRAW_RUN - 1) / REDRAW_RUN;
+    hipLaunchKernelGGL(k_redraw, dim3(nruns < 8192 ? nruns : 8192), dim3(B), (size_t)hw, st, *S, *c);
+    return 1;
+}
+// the typed whole-screen pass (rg_obs_typed; kind / dtype combination and arguments checked by the caller, mirrors drawn).  Returns 0 if the grid is not
+// a whole number of 16-byte pieces per plane (there is no fallback kernel).
+int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any,
+                  hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    const int hw = c->width * c->height, cells = dtype == RG_OBS_U8 ? 16 : 8;
+    if (hw % cells) return 0;
+    const int Q = hw / cells;
+    int B = ((Q + WAVE - 1) / WAVE) * WAVE;  // threads per block: an env's items, in whole waves
+    if (B > OBS_THREADS) B = OBS_THREADS;
+    if (Q > OBS_T_ITEMS * B) return 0;  // (cannot happen: RG_MAX_W x RG_MAX_H is 960 items)
+    // envs per block and iteration: as many as its threads hold items for; one (block-uniform) where status planes are written
+    int run = sflag ? 1 : OBS_T_ITEMS * B / Q;
+    if (run < 1) run = 1;
+    const int nruns = (S->n + run - 1) / run, cap = B <= WAVE ? OBS_STREAM_WAVES : 4096;  // persistent grid
+    const int blocks = nruns < cap ? nruns : cap;
+    const int planes = kind == 1 ? planes_sym : 1;
+#define RG_LAUNCH_TYPED(...) do { if (ev0 || ev1) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(B), 0, st, ev0, ev1, 0, S->screen, S->hist, S->status, S->flags, err_any, S->n, hw, \
+                                                                        (int)c->symbols, planes, sflag, with_hist, run, static_cast<u4v *>(out)); \
+                                  else hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(B), 0, st, S->screen, S->hist, S->status, S->flags, err_any, S->n, hw, (int)c->symbols, planes, sflag, \
+                                                          with_hist, run, static_cast<u4v *>(out)); } while (0)
+    if (kind == 2) RG_LAUNCH_TYPED(k_obs_typed<2, RG_OBS_U8>);
+    else if (kind == 0 && dtype == RG_OBS_F16) RG_LAUNCH_TYPED(k_obs_typed<0, RG_OBS_F16>);
+    else if (kind == 0) RG_LAUNCH_TYPED(k_obs_typed<0, RG_OBS_BF16>);
+    else if (dtype == RG_OBS_F16) RG_LAUNCH_TYPED(k_obs_typed<1, RG_OBS_F16>);
+    else RG_LAUNCH_TYPED(k_obs_typed<1, RG_OBS_BF16>);
+#undef RG_LAUNCH_TYPED
     return 1;
 }
 // shader-clock probe: one wave spins for `spin` iterations and reports {s_memtime ticks (shader clock), s_memrealtime ticks (constant 100 MHz)}

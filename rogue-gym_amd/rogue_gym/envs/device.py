@@ -28,15 +28,34 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False, crop=None):
+                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
 
         crop (None, r or (ry, rx)): `self.obs` is the player-centred window f32 [N, C, 2ry+1, 2rx+1] of the image instead of the whole screen, padded
         with blank cells past the screen edge (rg_obs_crop), and `self.crop_center` i32 [N, 2] holds each window's centre (y, x), rewritten with every
-        observation.  The window has one size for every env, so a batch whose envs differ in screen size can be built too.  Not with persistent_obs."""
+        observation.  The window has one size for every env, so a batch whose envs differ in screen size can be built too.  Not with persistent_obs.
+
+        obs_dtype (None, torch.float32, torch.float16 or torch.bfloat16): the element type of `self.obs`.  The 16-bit images are written by the encode pass
+        itself (rg_obs_typed) and are bit-identical to the f32 image's `.to(obs_dtype)`; None / float32 is the f32 path.
+
+        symbol_ids (needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype None): `self.obs` is uint8 [N, 1 + hist, H, W] -- plane 0 holds each cell's symbol
+        id (the one-hot image's argmax(1); ' ' is 0), what an embedding layer indexes with -- instead of the one-hot image.
+
+        Neither with crop or persistent_obs (those are f32 only)."""
         import torch
+
+        if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("obs_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (obs_dtype,))
+        typed16 = obs_dtype in (torch.float16, torch.bfloat16)
+        if symbol_ids:
+            if image_setting.dungeon != DungeonType.SYMBOL or image_setting.status.value != 0 or obs_dtype is not None:
+                raise ValueError("symbol_ids=True needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype=None (the ids are uint8), got %s, status %r, obs_dtype %r"
+                                 % (image_setting.dungeon, image_setting.status, obs_dtype))
+        if (typed16 or symbol_ids) and (crop is not None or persistent_obs):
+            raise ValueError("%s cannot be combined with %s: the crop and the bound observation tensor are float32 only"
+                             % ("symbol_ids=True" if symbol_ids else "obs_dtype=%s" % (obs_dtype,), "crop" if crop is not None else "persistent_obs=True"))
 
         if crop is not None:
             if persistent_obs:
@@ -65,8 +84,13 @@ class HipVecRogueEnv:
             self._action_keys = torch.tensor([ord(a) for a in self.ACTIONS], dtype=torch.uint8, device=self.device)
             self._sym = image_setting.dungeon == DungeonType.SYMBOL
             self.channels = L.rg_obs_channels(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist))
+            # (kind, RG_OBS_* dtype) of rg_obs_typed, or None: the f32 calls
+            self._typed = (2, 3) if symbol_ids else (int(self._sym), 1 if obs_dtype == torch.float16 else 2) if typed16 else None
+            if symbol_ids:
+                self.channels = 1 + int(image_setting.includes_hist)
             oh, ow = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
-            self.obs = torch.empty((self.num_envs, self.channels, oh, ow), dtype=torch.float32, device=self.device)
+            self.obs = torch.empty((self.num_envs, self.channels, oh, ow), dtype=torch.uint8 if symbol_ids else obs_dtype if typed16 else torch.float32,
+                                   device=self.device)
             self.crop_center = None if crop is None else torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
             p = C.c_void_p()
             self._h.check(L.rg_reward(h, C.byref(p)))
@@ -105,6 +129,10 @@ class HipVecRogueEnv:
             self._h.check(L.rg_obs_crop(h, int(self._sym), self.crop[0], self.crop[1], self.image_setting.status.value, int(self.image_setting.includes_hist),
                                         C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.crop_center.data_ptr())))
             return self.obs
+        if self._typed is not None:
+            self._h.check(L.rg_obs_typed(h, self._typed[0], self._typed[1], self.image_setting.status.value, int(self.image_setting.includes_hist),
+                                         C.c_void_p(self.obs.data_ptr())))
+            return self.obs
         fn = L.rg_obs_symbol if self._sym else L.rg_obs_gray
         self._h.check(fn(h, self.image_setting.status.value, int(self.image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         return self.obs
@@ -125,7 +153,11 @@ class HipVecRogueEnv:
         if keys.dtype != self.torch.uint8 or keys.device != self.device or not keys.is_contiguous() or keys.numel() != self.num_envs:
             raise ValueError("step_keys needs a contiguous uint8 tensor of %d keys on %s, got %s %s on %s"
                              % (self.num_envs, self.device, tuple(keys.shape), keys.dtype, keys.device))
-        if self._sym or self.crop is not None:
+        if self._typed is not None:  # the step and the typed observation as one call (rg_step_obs_typed)
+            self._h.check(self._h.L.rg_step_obs_typed(self._h.h, C.c_void_p(keys.data_ptr()), 1, self._typed[0], self._typed[1], self.image_setting.status.value,
+                                                       int(self.image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
+            obs = self.obs
+        elif self._sym or self.crop is not None:
             self._h.check(self._h.L.rg_step(self._h.h, C.c_void_p(keys.data_ptr()), 1))
             obs = self._encode()
         else:  # the step and the gray observation as one call: fused into one kernel where the config allows it (rg_step_obs_gray)
