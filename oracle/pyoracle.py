@@ -145,6 +145,8 @@ def lib():
         L.orc_batch_env.restype = C.c_void_p
         L.orc_batch_env.argtypes = [C.c_void_p, C.c_int]
         L.orc_batch_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_batch_fetch.argtypes = [C.c_void_p] * 5
+        L.orc_batch_fetch.restype = None
         L.orc_config_default.argtypes = [C.POINTER(OrcConfig)]
         _lib = L
     return _lib
@@ -450,6 +452,14 @@ class OracleBatch:
         rc = self._L.orc_batch_step(self._b, keys.ctypes.data, None if obs is None else obs.ctypes.data)
         if rc:
             raise RuntimeError("oracle batch step error")
+
+    def fetch(self, screen=True, hist=True, status=True, flags=True):
+        """(screen u8 [n,H,W], hist u8 [n,H,W], status u32 [n,10], flags u32 [n,5]) of every env in one call, copied out by the batch's threads;
+        flags columns in the order of orc_flags: is_terminal, message, steps, dead, symbols.  A part that is not asked for is None."""
+        out = (np.empty((self.n, self.h, self.w), np.uint8) if screen else None, np.empty((self.n, self.h, self.w), np.uint8) if hist else None,
+               np.empty((self.n, 10), np.uint32) if status else None, np.empty((self.n, 5), np.uint32) if flags else None)
+        self._L.orc_batch_fetch(self._b, *(None if a is None else a.ctypes.data for a in out))
+        return out
 
     def env(self, i):
         e = OracleEnv.__new__(OracleEnv)

@@ -1442,12 +1442,21 @@ struct orc_batch {
     pthread_t *threads;
     pthread_barrier_t bar_start, bar_end;
     const uint8_t *keys; float *obs; int stop; int err;
+    int fetch; uint8_t *f_screen, *f_hist; uint32_t *f_status, *f_flags; /* fetch != 0: the round copies state out (orc_batch_fetch), it does not step */
     struct orc_worker { struct orc_batch *b; int tid; } *workers;
 };
 static void batch_work(orc_batch *b, int tid) {
     int lo = (int)((int64_t)b->n * tid / b->n_threads), hi = (int)((int64_t)b->n * (tid + 1) / b->n_threads);
     for (int i = lo; i < hi; i++) {
         orc_env *e = b->envs[i];
+        if (b->fetch) {
+            size_t hw = (size_t)e->H * e->W;
+            if (b->f_screen) orc_screen(e, b->f_screen + i * hw);
+            if (b->f_hist) orc_hist(e, b->f_hist + i * hw);
+            if (b->f_status) orc_status(e, b->f_status + (size_t)i * 10);
+            if (b->f_flags) orc_flags(e, b->f_flags + (size_t)i * 5);
+            continue;
+        }
         if (orc_step_autoreset(e, b->keys[i])) b->err = 1;
         if (b->obs) orc_gray_image(e->screen, e->H, e->W, e->symbols, e->status, 0, NULL, b->obs + (size_t)i * e->H * e->W);
     }
@@ -1488,9 +1497,17 @@ void orc_batch_free(orc_batch *b) {
     free(b->envs); free(b);
 }
 orc_env *orc_batch_env(orc_batch *b, int i) { return b->envs[i]; }
-int orc_batch_step(orc_batch *b, const uint8_t *keys, float *obs) {
-    b->keys = keys; b->obs = obs; b->err = 0;
+static void batch_round(orc_batch *b) {
     if (b->n_threads > 1) { pthread_barrier_wait(&b->bar_start); batch_work(b, 0); pthread_barrier_wait(&b->bar_end); }
     else batch_work(b, 0);
+}
+int orc_batch_step(orc_batch *b, const uint8_t *keys, float *obs) {
+    b->keys = keys; b->obs = obs; b->err = 0; b->fetch = 0;
+    batch_round(b);
     return b->err;
+}
+void orc_batch_fetch(orc_batch *b, uint8_t *screen, uint8_t *hist, uint32_t *status, uint32_t *flags) {
+    b->f_screen = screen; b->f_hist = hist; b->f_status = status; b->f_flags = flags; b->fetch = 1;
+    batch_round(b);
+    b->fetch = 0;
 }

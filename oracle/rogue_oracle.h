@@ -153,6 +153,9 @@ void orc_batch_free(orc_batch *b);
 orc_env *orc_batch_env(orc_batch *b, int i);
 /* lock-step ThreadConductor::step over all envs + gray obs encode into obs [n,1,H,W] (may be NULL) */
 int orc_batch_step(orc_batch *b, const uint8_t *keys, float *obs);
+/* the mirrors of every env in one call, copied out by the batch's thread pool: screen and hist u8 [n][H][W] (every env of the batch has env 0's
+ * size), status u32 [n][10], flags u32 [n][5] in the order of orc_flags.  Any pointer may be NULL. */
+void orc_batch_fetch(orc_batch *b, uint8_t *screen, uint8_t *hist, uint32_t *status, uint32_t *flags);
 
 #ifdef __cplusplus
 }

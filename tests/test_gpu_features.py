@@ -509,12 +509,17 @@ def test_index_order_mapping_without_stair_waves_is_bit_exact(goldens):
     {"ROGUE_GYM_HIP_WAVE_REGEN": "1"},
     {"DEV": "1", "ROGUE_GYM_HIP_LANE_WAVES": "3", "ROGUE_GYM_HIP_LANE_EVERY": "3"},
     {"ROGUE_GYM_HIP_SP_SLOTS": "1"},
+    {"ROGUE_GYM_HIP_EPW": "64"},
+    {"ROGUE_GYM_HIP_EPW": "33"},
 ], ids=["dev build: round-2/3 generator scheduling", "dev build: sparse generator launches", "24 envs per step wave", "spares one level per wave (k_regen)",
-        "dev build: three level-per-lane waves every third step", "one spare per env"])
+        "dev build: three level-per-lane waves every third step", "one spare per env", "64 envs per step wave: full waves", "33 envs per step wave"])
 def test_results_do_not_depend_on_where_the_background_generator_runs(knobs):
     """When and where the spare levels are regenerated (behind which kernel, how often, at which priority, how many envs per generator wave) and how many
     envs a step wave holds decide only whether an auto-reset finds its spare or generates inline -- never what the env looks like afterwards: the
-    lock-step parity tests again, in processes with the scheduling knobs turned the other way.  The generator placements that were measured and
+    lock-step parity tests again, in processes with the scheduling knobs turned the other way.  With 64 and with 33 envs per wave (what the step
+    kernels get at the benchmarked batch sizes; a batch of these tests' size gets 16) the run-key and stair-seeker suites run too: fights, deaths and
+    level-ups on every lane of full waves (mini with 384 and 512 envs, 80x24 with 192 and 256), state compared with the oracle env by env; the
+    12-env 80x24 chasers then share one wave.  The generator placements that were measured and
     rejected are compiled into the DEVELOPMENT library only (-DRG_DEV_KNOBS, built next to the product by __graft_entry__.build()); the product
     reads ROGUE_GYM_HIP_EPW / _NO_SPARES / _NO_STAIR_WAVES / _KEEP_SPARES / _FULL_BFS and nothing else."""
     import os
@@ -527,8 +532,10 @@ def test_results_do_not_depend_on_where_the_background_generator_runs(knobs):
         knobs["ROGUE_GYM_HIP_LIB"] = dev
     env = dict(os.environ, **knobs)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q", "-k",
-                        "lockstep_random_policy or frequent_descents or inline_generation or full_size_invariants"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    select = "lockstep_random_policy or frequent_descents or inline_generation or full_size_invariants"
+    if knobs.get("ROGUE_GYM_HIP_EPW") in ("64", "33"):
+        select += " or lockstep_run_keys or stair_seekers"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q", "-k", select], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
     assert " passed" in r.stdout
 

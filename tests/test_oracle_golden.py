@@ -179,3 +179,31 @@ def test_inclusive_edges_kat(goldens):
     k = goldens["expect"]["inclusive_edges"]
     for d in ("Down", "Up", "Left", "Right"):
         assert kat_edges(k["range"]["x"], k["range"]["y"], d, True) == k[d], d
+
+
+def test_batch_fetch_equals_the_per_env_getters(goldens):
+    """OracleBatch.fetch() after 120 steps of 64 mini envs (run keys, '>' and 30-step episodes: auto-resets, deaths and messages in the batch)
+    equals screen(), hist(), status_arr() and flags() of every env, with a pool of 1 and of 4 threads; a part not asked for is left out."""
+    mini = goldens["configs"]["mini"]
+    table = np.frombuffer(b"hjklyubnHJKLYUBN>>s.", np.uint8)
+    got = {}
+    for n_threads in (1, 4):
+        ob = OracleBatch([dict(mini, seed=i) for i in range(64)], max_steps=30, n_threads=n_threads)
+        rng = np.random.RandomState(5)
+        for _ in range(120):
+            ob.step(table[rng.randint(0, len(table), 64)])
+        screen, hist, status, flags = got[n_threads] = ob.fetch()
+        assert (screen.shape, hist.shape, status.shape, flags.shape) == ((64, 16, 32), (64, 16, 32), (64, 10), (64, 5))
+        assert (screen.dtype, hist.dtype, status.dtype, flags.dtype) == (np.uint8, np.uint8, np.uint32, np.uint32)
+        for i in range(64):
+            o = ob.env(i)
+            assert np.array_equal(screen[i], o.screen()), "threads %d env %d screen" % (n_threads, i)
+            assert np.array_equal(hist[i], o.hist()), "threads %d env %d hist" % (n_threads, i)
+            assert np.array_equal(status[i], o.status_arr()), "threads %d env %d status" % (n_threads, i)
+            f = o.flags()
+            assert [int(v) for v in flags[i]] == [int(f["is_terminal"]), f["message"], f["steps"], int(f["dead"]), f["symbols"]], "threads %d env %d flags" % (n_threads, i)
+        assert len(set(flags[:, 2].tolist())) > 1, "no env died: every env is at the same step of its episode"
+        only = ob.fetch(screen=False, hist=False, flags=False)
+        assert only[0] is None and only[1] is None and only[3] is None and np.array_equal(only[2], status)
+    for a, b in zip(got[1], got[4]):
+        assert np.array_equal(a, b)

@@ -2,7 +2,10 @@
 geometric maximum, every dungeon / gold / enemy / player rate, random packs, random monster subsets) played in lock step by the HIP stepper and the C
 oracle on random keys.  Mirrors are compared after every step, the internal state (tiles, doors, gold, monsters, every RNG word) at intervals.
 
-    python tools/fuzz_parity.py [--configs 40] [--envs 48] [--steps 150] [--seed 1] [--minutes 0]
+    python tools/fuzz_parity.py [--configs 40] [--envs 48] [--steps 150] [--seed 1] [--minutes 0] [--epw 0]
+
+--epw N (16..64) sets ROGUE_GYM_HIP_EPW before the library loads: with --epw 64 --envs 512 every step wave is full, where the default gives a batch that
+small 16 envs per wave.
 
 Needs a GPU.  Prints one line per config; a failing config is printed as JSON (and appended to gpurun_out/fuzz_failures.jsonl) so that it can be turned
 into a regression test.  Exit code 1 if anything differed.  Development / soak tool: tests/test_gpu_fuzz.py runs a small fixed-seed slice of it."""
@@ -184,7 +187,12 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-rooms", type=int, default=0, help="cap rooms per level (0 = no cap)")
     ap.add_argument("--minutes", type=float, default=0.0, help="keep drawing configs until this much time has passed (overrides --configs)")
+    ap.add_argument("--epw", type=int, default=0, help="envs per step wave, 16..64 (ROGUE_GYM_HIP_EPW; 0 = the library's own choice)")
     args = ap.parse_args()
+    if args.epw:
+        if not 16 <= args.epw <= 64:
+            ap.error("--epw must be in 16..64")  # (the library ignores a value outside that range: refuse it here instead of soaking the default)
+        os.environ["ROGUE_GYM_HIP_EPW"] = str(args.epw)  # read once, at the library's first step
     from parity_util import lockstep
     from rogue_gym_python import _rogue_gym as inner
 
@@ -223,7 +231,8 @@ def main():
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "fuzz_failures.jsonl"), "a") as f:
                 f.write(json.dumps({"config": cfg, "error": str(e)[:2000], "fuzz_seed": args.seed, "index": done}) + "\n")
-    print("fuzz: %d configs, %d failed, %d invalid draws skipped, %.0f s" % (done, failed, skipped, time.time() - t0))
+    print("fuzz: %d configs of %d envs%s, %d failed, %d invalid draws skipped, %.0f s"
+          % (done, args.envs, ", %d envs per step wave" % args.epw if args.epw else "", failed, skipped, time.time() - t0))
     return 1 if failed else 0
 
 
