@@ -84,4 +84,9 @@ venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=I
 obs, reward, done = venv.step(actions[0, :4096])
 table = torch.randn(venv.symbols, 8, device=venv.device)
 print("HipVecRogueEnv(symbol_ids=True): obs %s %s -> embedded %s" % (tuple(obs.shape), obs.dtype, tuple(table[obs[:, 0].long()].shape)))
+
+# 3d. restart the lanes of your choice -- here the ones that reached level 2, from a mask that never leaves the device -- under any observation mode ----
+obs = venv.reset_envs(mask=venv.status[:, 0] >= 2)
+obs = venv.reset_envs(env_ids=[17, 4011], seeds=[7, 8])   # ... or by index, on seeds of your choice
+print("HipVecRogueEnv.reset_envs: envs 17 and 4011 restarted on level %s" % venv.status[[17, 4011], 0].tolist())
 venv.close()

@@ -80,6 +80,20 @@ int rg_set_stream(rg_t *h, void *hip_stream);
 int rg_seed(rg_t *h, const uint64_t *seed_lo, const uint64_t *seed_hi, int n);
 /* GameState::reset / ParallelGameState::reset: rebuild every env from its config (+ seed). */
 int rg_reset(rg_t *h);
+/* Reset the envs the caller picks (Isaac Gym's reset_idx, EnvPool's reset(env_ids), Gymnasium's reset_mask).  Each chosen env is rebuilt exactly as rg_reset
+ * rebuilds it: GameConfig::build from its seed (a `seed: None` env draws a fresh build ticket), level 1, steps 0, reward 0, done 0, flags REDRAW | HIST_DIRTY,
+ * an empty dist cache, its next-level structure dropped, its key log rolled (the cut-off episode becomes the "previous" one).  Every other env keeps every
+ * byte of its state.  The spares are not consulted and stay valid: a fixed-seed env's spare was built from the same seed, a reseeding env's ticket is its own.
+ * rg_reset_envs: k env ids, host (range-checked, duplicates refused, nothing launched on a refusal) or device i32 (ids_on_device != 0: the caller's
+ *   responsibility; an id out of range is skipped and raises RG_FLAG_ERR_INTERNAL at the next rg_sync).  env_ids NULL = every env (k is ignored).
+ * rg_reset_mask: mask_dev = u8 [n_env] on the device, non-zero = rebuild.  The mask is compacted into a list on the device: no host round trip.
+ * Both are asynchronous on the handle's stream; an empty list / all-zero mask is a valid no-op.  Mirrors are redrawn at the next read, and a bound
+ * observation tensor (rg_obs_bind) encodes every env at its next call.  Not for handles with config groups.
+ * rg_seed_envs: rg_seed for chosen envs (host pointers; seed_hi may be NULL): the seeds are used at those envs' next reset of any kind, rg_dump_config
+ *   reports them, and exactly those envs' spares are dropped and regenerated. */
+int rg_reset_envs(rg_t *h, const int32_t *env_ids, int k, int ids_on_device);
+int rg_reset_mask(rg_t *h, const uint8_t *mask_dev);
+int rg_seed_envs(rg_t *h, const int32_t *env_ids, const uint64_t *seed_lo, const uint64_t *seed_hi, int k);
 /* GameState::react / ParallelGameState::step (python/src/lib.rs:241-243,315-321 ->
  * state_impls.rs:51-79, thread_impls.rs:61-81): one key byte per env.  `keys` is a device pointer
  * when keys_on_device != 0, else a host pointer (copied H2D on the stream). */
@@ -317,8 +331,9 @@ int rg_config_schema(char *buf, size_t cap, size_t *needed);
  * What a record does NOT carry, deliberately: what decides the env's FUTURE episodes -- seed, seed range, build counter, the pre-generated spare levels and
  * the previous episode's key log -- belongs to the destination slot.  A restored env plays out the saved episode; when that episode ends it resets from
  * its OWN seed, as rg_reset would.  Nor the generator's scratch (corridor records, maze stack: dead once a level is complete) and the handle-local flag bits
- * (RG_FLAG_SCR_CHANGED, the error bits: cleared in the record).  Records are canonical: padding, the key log past its length and the words of
- * empty slots (a dead monster's hp / exp, an absent gold's amount) are zero, so equal states give equal bytes.
+ * (RG_FLAG_SCR_CHANGED, the error bits: cleared in the record).  Records are canonical: padding, the key log past its length, the words of
+ * empty slots (a dead monster's hp / exp, an absent gold's amount) and the dist-cache slots outside the cache's ring (maps, keys, saved masks: what an
+ * earlier episode left behind) are zero, so equal states give equal bytes -- a rebuilt env's record equals that of a newly created one.
  * rg_state_save: flushes the pending render (records hold drawn mirrors), then writes k records to out_dev = u8 [k][R] (16-byte aligned), env_ids[i]'s
  *   state in record i; env_ids NULL = all n_env envs in order (k is then ignored).
  * rg_state_load: k records of rec_bytes each (R of the SAVING handle: it may differ from this handle's only in the key-log section; as many logged keys are

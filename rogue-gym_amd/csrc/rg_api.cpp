@@ -54,6 +54,9 @@ int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, 
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
+void rgk_state_stairs(const RgState *S, const RgIoLayout *L, uint8_t *mark, hipStream_t st);
+void rgk_reset_compact(const uint8_t *mask, int n, int32_t *list, uint32_t *cnt, hipStream_t st);
+void rgk_build_list(const RgState *S, const RgConfig *c, const int32_t *list, const uint32_t *cnt, uint8_t *mark, hipStream_t st);
 }
 
 #define RG_TIMED_KERNELS 5   // k_step, k_render, k_obs (or the unfused encode), k_build, k_regen
@@ -124,7 +127,10 @@ struct rg_handle {
     uint32_t io_words = 0;
     int32_t *io_ids = nullptr; size_t io_ids_cap = 0;  // host-side env ids, uploaded
     uint8_t *io_ok = nullptr; size_t io_ok_cap = 0;    // per record of a load: its header fitted
-    uint8_t *io_mark = nullptr;                        // [n] per env: restored by the load in flight (k_state_stairs clears it)
+    uint8_t *io_mark = nullptr;                        // [n] per env: restored by the load / rebuilt by the partial reset in flight (k_state_stairs clears it)
+    // partial reset (rg_reset_envs / rg_reset_mask): the envs to rebuild, device-resident
+    int32_t *reset_list = nullptr;                     // [n]
+    uint32_t *reset_cnt = nullptr;                     // [1] entries of reset_list
 };
 
 #define RG_TIMING_MAX 4096
@@ -686,7 +692,7 @@ int rg_sync(rg_t *h) {
     if (h->side) { HIPCHK(h, hipStreamSynchronize(h->side)); HIPCHK(h, hipStreamSynchronize(h->side2)); HIPCHK(h, hipStreamSynchronize(h->side3)); }
     if (err) {
         HIPCHK(h, hipMemsetAsync(h->d_err, 0, 4, h->stream));
-        if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config)";
+        if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config), or rg_reset_envs was given a device-side env id out of range";
         else if (err & RG_FLAG_ERR_STATE) h->err = "state record refused: it does not fit this env (magic / version / config fingerprint / geometry), the env is unchanged";
         else if (err & RG_FLAG_ERR_KEY) h->err = "Invalid input (key is not in the ai keymap)";
         else if (err & RG_FLAG_ERR_DEAD) h->err = "Ignored input (action while the player is dead)";
@@ -918,7 +924,7 @@ int rg_step_fetch(rg_t *h, const uint8_t *keys_host, int n_keys, uint8_t *screen
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const uint32_t err = h->pin_err[0];
     if (err) {
-        if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config)";
+        if (err & RG_FLAG_ERR_INTERNAL) h->err = "internal capacity guard of the HIP stepper tripped (please report the config), or rg_reset_envs was given a device-side env id out of range";
         else if (err & RG_FLAG_ERR_STATE) h->err = "state record refused: it does not fit this env (magic / version / config fingerprint / geometry), the env is unchanged";
         else if (err & RG_FLAG_ERR_KEY) h->err = "Invalid input (key is not in the ai keymap)";
         else if (err & RG_FLAG_ERR_DEAD) h->err = "Ignored input (action while the player is dead)";
@@ -1463,6 +1469,7 @@ static int state_prepare(rg_handle *h) {
     add(S.p_pos, 1, 1); add(S.p_hp, 2, 1); add(S.p_hpmax, 2, 1); add(S.p_lvl, 2, 1); add(S.p_exp, 2, 1); add(S.food, 2, 1); add(S.quiet, 2, 1);
     add(S.pack_gold, 2, 1); add(S.dlevel, 2, 1); add(S.steps, 2, 1); add(S.flags, 2, 1, true); add(S.reward, 2, 1); add(S.done, 0, 1);
     add(S.rng, 2, 12); add(S.mon_cnt, 2, 1);
+    const size_t i_dk = d.size();
     add(S.dc_key, 1, RG_DIST_SLOTS); add(S.dc_head, 0, 1); add(S.dc_len, 0, 1); add(S.dc_part, 1, 1); add(S.dc_own, 1, 1);
     add(S.room_rect, 2, nr); add(S.room_meta, 0, nr);
     const size_t i_w0 = d.size(); add(S.mon_w0, 2, nr);
@@ -1473,6 +1480,8 @@ static int state_prepare(rg_handle *h) {
     // the words of an EMPTY slot are stale (whatever the generator's tables held there): a dead monster's hp / exp and an absent gold's amount are
     // written as 0, on save and on load, so that equal states give equal records
     std::vector<uint32_t> g(d.size(), 0u);
+    for (int sl = 0; sl < RG_DIST_SLOTS; sl++)  // a dist-cache key outside the ring (dc_head and dc_len follow the keys)
+        g[i_dk + sl] = (uint32_t)(i_dk + RG_DIST_SLOTS + 1) | ((uint32_t)sl << RG_IO_GUARD_SHIFT) | RG_IO_GUARD_RING;
     for (int r = 0; r < nr; r++) {
         g[i_hp + r] = g[i_hp + nr + r] = (uint32_t)(i_w0 + r + 1) | (24u << RG_IO_GUARD_SHIFT);  // MF_ALIVE: bit 0 of the flag byte
         g[i_ga + r] = (uint32_t)(i_gp + r + 1) | (16u << RG_IO_GUARD_SHIFT);                       // gold present: 0x10000
@@ -1566,6 +1575,92 @@ int rg_state_load(rg_t *h, const uint8_t *rec_dev, size_t rec_bytes, const int32
     rgk_state_load(&h->S, &L, h->io_desc, h->io_guard, ids, k, rec_dev, (uint32_t)rec_bytes, h->io_ok, h->io_mark, h->stream);
     HIPCHK(h, hipGetLastError());
     h->bound_valid = false;  // the bound observation tensor does not show the restored screens: its next call encodes every env
+    return 0;
+}
+
+// ---- partial reset: the envs a caller picks (rg_kernels.hip k_reset_compact / k_build_list) ----
+static int reset_prepare(rg_handle *h) {
+    if (!h->io_mark && !dev_alloc(h, &h->io_mark, (size_t)h->S.n)) return 1;
+    if (!h->reset_list && !dev_alloc(h, &h->reset_list, (size_t)h->S.n)) return 1;
+    if (!h->reset_cnt && !dev_alloc(h, &h->reset_cnt, 4)) return 1;
+    return 0;
+}
+
+// reset_list[0 .. reset_cnt[0]) is on its way on the stream: rebuild those envs, then produce the stair set of the next k_step
+static int reset_listed(rg_handle *h) {
+    RgIoLayout L;
+    state_layout(h, &L);
+    // The build moves players: like a load it PRODUCES the stair set (rg_state.h), rebuilt envs from their new cell, all others carried forward.  The spares
+    // are not consulted: a fixed-seed env's spare was built from the same seed and stays valid, a reseeding env takes its own build ticket (atomic, so safe
+    // beside a k_regen in flight) -- stream order is enough, nothing is drained.
+    h->S.stair_gen = h->stair_gen++;
+    { TimedLaunch t(h, 3); rgk_build_list(&h->S, &h->cfg, h->reset_list, h->reset_cnt, h->io_mark, h->stream); }
+    rgk_state_stairs(&h->S, &L, h->io_mark, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->render_pending = true;
+    h->bound_valid = false;  // (as rg_reset: the bound observation tensor's next call encodes every env)
+    return 0;
+}
+
+int rg_reset_envs(rg_t *h, const int32_t *env_ids, int k, int ids_on_device) {
+    if (!h->sub.empty()) { h->err = "rg_reset_envs: not for a handle with config groups (one handle per config)"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!env_ids) return rg_reset(h);  // every env: the list would be 0 .. n - 1
+    if (k < 0 || k > h->S.n) { h->err = "rg_reset_envs: k = " + std::to_string(k) + " env_ids for " + std::to_string(h->S.n) + " envs"; return 1; }
+    if (!ids_on_device) {  // checked before anything is launched
+        std::vector<uint8_t> seen((size_t)h->S.n, 0);
+        for (int i = 0; i < k; i++) {
+            const int32_t e = env_ids[i];
+            if (e < 0 || e >= h->S.n) { h->err = "rg_reset_envs: env_ids[" + std::to_string(i) + "] = " + std::to_string(e) + " out of range [0, " + std::to_string(h->S.n) + ")"; return 1; }
+            if (seen[e]) { h->err = "rg_reset_envs: env_ids holds " + std::to_string(e) + " twice"; return 1; }
+            seen[e] = 1;
+        }
+    }
+    if (reset_prepare(h)) return 1;
+    const uint32_t cnt = (uint32_t)k;
+    HIPCHK(h, hipMemcpyAsync(h->reset_cnt, &cnt, 4, hipMemcpyHostToDevice, h->stream));  // (pageable sources: staged before the call returns)
+    if (k) HIPCHK(h, hipMemcpyAsync(h->reset_list, env_ids, (size_t)k * 4, ids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    return reset_listed(h);
+}
+
+int rg_reset_mask(rg_t *h, const uint8_t *mask_dev) {
+    if (!h->sub.empty()) { h->err = "rg_reset_mask: not for a handle with config groups (one handle per config)"; return 1; }
+    if (!mask_dev) { h->err = "rg_reset_mask: mask_dev is NULL"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (reset_prepare(h)) return 1;
+    rgk_reset_compact(mask_dev, h->S.n, h->reset_list, h->reset_cnt, h->stream);  // the mask never reaches the host
+    return reset_listed(h);
+}
+
+int rg_seed_envs(rg_t *h, const int32_t *env_ids, const uint64_t *seed_lo, const uint64_t *seed_hi, int k) {
+    if (!h->sub.empty()) { h->err = "rg_seed_envs: not for a handle with config groups (one handle per config)"; return 1; }
+    if (k < 0 || (k > 0 && (!env_ids || !seed_lo))) { h->err = "rg_seed_envs: env_ids and seed_lo must hold k >= 0 entries"; return 1; }
+    for (int i = 0; i < k; i++)
+        if (env_ids[i] < 0 || env_ids[i] >= h->S.n) { h->err = "rg_seed_envs: env_ids[" + std::to_string(i) + "] = " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(h->S.n) + ")"; return 1; }
+    if (k == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->spares) {  // rg_seed's rule, for exactly these envs: their spares were generated from the old seeds
+        HIPCHK(h, hipStreamSynchronize(h->side));
+        HIPCHK(h, hipStreamSynchronize(h->side2));
+        HIPCHK(h, hipStreamSynchronize(h->side3));
+    }
+    size_t lo = (size_t)h->S.n, hi = 0;
+    for (int i = 0; i < k; i++) {  // (a repeated id: the last seed wins)
+        const size_t e = (size_t)env_ids[i];
+        h->seed_lo[e] = seed_lo[i]; h->seed_hi[e] = seed_hi ? seed_hi[i] : 0; h->reseed[e] = 0;
+        lo = e < lo ? e : lo; hi = e > hi ? e : hi;
+        if (h->spares)
+            for (int sl = 0; sl < h->S.sp_slots; sl++) HIPCHK(h, hipMemsetAsync(h->S.sp_ready + (size_t)sl * h->S.n + e, 0, 4, h->stream));
+    }
+    // only the span that holds the touched envs travels (the envs between them get the values the device already has: the host copies are what was
+    // uploaded last, and a `seed: None` env's copy is the base of its per-build hash, which never changes on the device)
+    HIPCHK(h, hipMemcpyAsync(h->S.seed_lo + lo, h->seed_lo.data() + lo, (hi - lo + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->S.seed_hi + lo, h->seed_hi.data() + lo, (hi - lo + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->S.reseed + lo, h->reseed.data() + lo, hi - lo + 1, hipMemcpyHostToDevice, h->stream));
+    if (h->spares) {
+        if (h->regen_idle_after >= 0) h->regen_idle_after = 2;  // rebuild the dropped spares, then idle again
+        h->regen_bulk = 2;
+    }
     return 0;
 }
 

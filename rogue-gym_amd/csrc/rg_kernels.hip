@@ -1146,6 +1146,56 @@ __global__ void __launch_bounds__(WAVE) k_build(RgState S, RgConfig c) {
     klog_new_episode(S, e);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Partial reset (rg_reset_envs / rg_reset_mask): rebuild the envs of a device-resident list
+// ---------------------------------------------------------------------------------------------
+// k_reset_compact: mask -> list.  One coalesced byte per lane, a ballot, one atomic per wave that has any; the order of the list is whatever the atomics
+// give (envs are independent, a reseeding env's build ticket is its own).  cnt[0] was zeroed on the stream before this launch.
+#define COMPACT_THREADS 256
+__global__ void __launch_bounds__(COMPACT_THREADS) k_reset_compact(const uint8_t *__restrict__ mask, int n, int32_t *__restrict__ list, uint32_t *__restrict__ cnt) {
+    const int e = blockIdx.x * COMPACT_THREADS + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
+    const bool on = e < n && mask[e] != 0;
+    const uint64_t m = __ballot(on);
+    if (!m) return;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&cnt[0], (uint32_t)__popcll(m));
+    base = uni(base);
+    if (on) list[base + lanes_below(m)] = e;
+}
+
+// k_build_list: k_build with e = list[i].  The grid is sized for the worst case (every env listed) and the count lives on the device: a wave beyond the
+// list leaves after one scalar load.  BUILD_EPB envs per wave, as k_build.  The stair set cannot be published from here -- the bytes of the envs that are
+// NOT rebuilt have to be carried forward as well -- so a rebuilt env is marked and k_state_stairs (rg_state_io.hip) produces the set behind this launch,
+// as it does for a load; it also drops the env's next-level structure.  An id out of range (a device-side list is the caller's to get right) is skipped.
+template <int GM>
+__global__ void __launch_bounds__(WAVE) k_build_list(RgState S, RgConfig c, const int32_t *__restrict__ list, const uint32_t *__restrict__ cnt, uint8_t *__restrict__ mark) {
+    const int lane = threadIdx.x;
+    const uint32_t k = uni(cnt[0]);
+    const uint32_t i0 = blockIdx.x * BUILD_EPB;
+    if (i0 >= k) return;
+    bool valid = lane < BUILD_EPB && i0 + lane < k;
+    int e = valid ? list[i0 + lane] : 0;
+    if (valid && (e < 0 || e >= S.n)) { atomicOr(S.err_any, RG_FLAG_ERR_INTERNAL); valid = false; e = 0; }
+    Env E;
+    E.e = e; E.n = S.n; E.cell = E.gcell = S.cell + (size_t)E.e * S.hw; E.err = 0; E.mc = nullptr;
+    Prof pf; pf.start(nullptr);
+    E.on_stairs = 0;
+    gen_service<GM>(S, c, E, lane, e, valid, true, reinterpret_cast<uint16_t *>(g_smem), pf);
+    if (!valid) return;
+    store_env(S, E);
+    write_status(S, c, E);
+    if (S.obs_rec) { const int nr = c.room_num_x * c.room_num_y; S.obs_rec[(size_t)e * RG_OBS_REC_WORDS(nr) + nr] = POS(E.px, E.py); }  // (the rest of the record: gen_service)
+    if (S.ovl) S.ovl[(size_t)(c.room_num_x * c.room_num_y) * S.n + e] = (uint16_t)(POS(E.px, E.py) | 0x40u);  // (| OVL_UNKNOWN)
+    S.dc_len[e] = 0; S.dc_head[e] = 0; S.dc_part[e] = 0; S.dc_own[e] = 0;  // a rebuilt RunTime owns a fresh DistCache
+    S.steps[e] = 0;
+    S.flags[e] = RG_FLAG_REDRAW | RG_FLAG_HIST_DIRTY | E.err;
+    if (E.err) atomicOr(S.err_any, E.err);
+    S.reward[e] = 0.f;
+    S.done[e] = 0;
+    klog_new_episode(S, e);
+    mark[e] = 1;
+}
+
 // Parity / property-test hook (rg_debug_descend): every env takes Dungeon::new_level + actions::new_level's player placement as if it had
 // pressed '>' on the stairs, without the turn around it -- the descent path of k_step (gen_service, is_build = false) on its own, so tests
 // can look at levels 2..30 of thousands of seeds without walking there.
@@ -3056,6 +3106,22 @@ void rgk_build(const RgState *S, const RgConfig *c, hipStream_t st) {
     case 0: hipLaunchKernelGGL(k_build<0>, grid, dim3(WAVE), smem, st, *S, *c); break;
     case 1: hipLaunchKernelGGL(k_build<1>, grid, dim3(WAVE), smem, st, *S, *c); break;
     default: hipLaunchKernelGGL(k_build<2>, grid, dim3(WAVE), smem, st, *S, *c);
+    }
+}
+// rg_reset_mask: cnt[0] = 0, then the envs whose mask byte is set are appended to list (u32 cnt[1], i32 list[n]: the handle's)
+void rgk_reset_compact(const uint8_t *mask, int n, int32_t *list, uint32_t *cnt, hipStream_t st) {
+    (void)hipMemsetAsync(cnt, 0, 4, st);
+    hipLaunchKernelGGL(k_reset_compact, dim3((n + COMPACT_THREADS - 1) / COMPACT_THREADS), dim3(COMPACT_THREADS), 0, st, mask, n, list, cnt);
+}
+// the envs list[0 .. cnt[0]) rebuilt as by rgk_build and marked for k_state_stairs; the grid covers a list of all n envs (it is not capped: no stride loop)
+void rgk_build_list(const RgState *S, const RgConfig *c, const int32_t *list, const uint32_t *cnt, uint8_t *mark, hipStream_t st) {
+    int hw = c->width * c->height;
+    size_t smem = GEN_SLOT_BYTES(hw, c->room_num_x * c->room_num_y);
+    const dim3 grid((S->n + BUILD_EPB - 1) / BUILD_EPB);
+    switch (gen_mode_of(c)) {
+    case 0: hipLaunchKernelGGL(k_build_list<0>, grid, dim3(WAVE), smem, st, *S, *c, list, cnt, mark); break;
+    case 1: hipLaunchKernelGGL(k_build_list<1>, grid, dim3(WAVE), smem, st, *S, *c, list, cnt, mark); break;
+    default: hipLaunchKernelGGL(k_build_list<2>, grid, dim3(WAVE), smem, st, *S, *c, list, cnt, mark);
     }
 }
 // envs per index-order wave of k_step.  A batch below 64 x 1024 envs is spread over more, emptier waves (less divergence per wave, no idle SIMDs);

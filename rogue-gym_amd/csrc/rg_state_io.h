@@ -4,8 +4,8 @@
 //   [0, 64)            header: u32 words {magic, RG_STATE_VERSION, R, H | W << 16, rooms, sections, fingerprint lo, fingerprint hi, klog cap, klog len, 0 ...}
 //   o_cell             cell    u16 [H*W]
 //   o_screen, o_hist   screen / history mirrors u8 [H*W]
-//   o_dcmap            dist maps u16 [RG_DIST_SLOTS][H*W]                     (configs with enemies)
-//   o_dcwalk           saved walkable masks u32 [RG_DIST_SLOTS][H][walk words]   (the partial-map grid class)
+//   o_dcmap            dist maps u16 [RG_DIST_SLOTS][H*W]                     (configs with enemies; zero for a slot outside the cache's ring)
+//   o_dcwalk           saved walkable masks u32 [RG_DIST_SLOTS][H][walk words]   (the partial-map grid class; zero for a slot without a saved mask)
 //   o_status           status mirror i32 [10]
 //   o_obsrec           observation record u32 [RG_OBS_REC_WORDS(rooms)]        (grids the fused observation pass handles)
 //   o_words            the env's words of the SoA arrays, one u32 each (narrow fields zero-extended), in the order of the descriptor table
@@ -36,6 +36,9 @@
 // word guard (u32, one per word; 0 = none): (index of the guard word + 1) | bit << RG_IO_GUARD_SHIFT -- the word is stored as 0 unless that bit of the guard
 // word is set (the hp / exp of a dead monster's slot, the amount of an absent gold: stale values that are not state)
 #define RG_IO_GUARD_SHIFT 24
+// ring guard (a dist-cache key): (index of the dc_head word + 1) | slot << RG_IO_GUARD_SHIFT | RG_IO_GUARD_RING -- the word is stored as 0 unless the slot is one of
+// the dc_len (the word after dc_head) slots of the FIFO ring that starts at dc_head: a slot outside the ring holds whatever an earlier episode left there
+#define RG_IO_GUARD_RING 0x80000000u
 
 struct RgIoLayout {
     uint32_t R;         // record bytes of this handle

@@ -39,6 +39,19 @@ __device__ __forceinline__ void io_copy(uint8_t *__restrict__ dst, const uint8_t
     for (uint32_t i = bytes + lane; i < pad_to; i += WAVE) dst[i] = 0;
 }
 
+// the dist cache's slot sections, slot by slot: a slot that holds no state (`live` bit clear) is written as zeros, whatever an earlier episode left in it
+__device__ __forceinline__ void io_copy_slots(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t bytes, uint32_t live, int lane) {
+    const uint32_t sb = bytes / RG_DIST_SLOTS;
+    for (uint32_t s = 0; s < RG_DIST_SLOTS; s++) {
+        if ((live >> s) & 1u) io_copy(dst + s * sb, src + s * sb, sb, sb, lane);
+        else if (((uintptr_t)(dst + s * sb) & 15) == 0) {
+            for (uint32_t i = lane; i < (sb >> 4); i += WAVE) reinterpret_cast<uint4 *>(dst + s * sb)[i] = make_uint4(0, 0, 0, 0);
+            for (uint32_t i = (sb & ~15u) + lane; i < sb; i += WAVE) dst[s * sb + i] = 0;
+        } else io_copy(dst + s * sb, src, 0, sb, lane);
+    }
+    for (uint32_t i = bytes + lane; i < RG_STATE_PAD16(bytes); i += WAVE) dst[i] = 0;
+}
+
 __device__ __forceinline__ uint32_t io_ld(uint64_t d, int e) {
     const uintptr_t p = (uintptr_t)(d & RG_IO_DESC_PTR_MASK);
     const uint32_t lg = (uint32_t)(d >> RG_IO_DESC_LG_SHIFT) & 3u;
@@ -79,8 +92,14 @@ __global__ void __launch_bounds__(WAVE * IO_RPB) k_state_rec_save(RgState S, RgI
     io_copy(rec + L.o_cell, reinterpret_cast<const uint8_t *>(S.cell + (size_t)e * hw), L.hw * 2, RG_STATE_PAD16(L.hw * 2), lane);
     io_copy(rec + L.o_screen, S.screen + (size_t)e * hw, L.hw, RG_STATE_PAD16(L.hw), lane);
     io_copy(rec + L.o_hist, S.hist + (size_t)e * hw, L.hw, RG_STATE_PAD16(L.hw), lane);
-    if (L.sections & RG_SEC_DCMAP) io_copy(rec + L.o_dcmap, reinterpret_cast<const uint8_t *>(S.dc_map) + (size_t)e * L.b_dcmap, L.b_dcmap, RG_STATE_PAD16(L.b_dcmap), lane);
-    if (L.sections & RG_SEC_DCWALK) io_copy(rec + L.o_dcwalk, reinterpret_cast<const uint8_t *>(S.dc_walk) + (size_t)e * L.b_dcwalk, L.b_dcwalk, RG_STATE_PAD16(L.b_dcwalk), lane);
+    // (canonical records: only the slots of the dist cache's ring, and of those only the saved masks, are state -- a rebuilt env's cache is empty)
+    uint32_t ring = 0;
+    {
+        const uint32_t head = S.dc_head[e], len = S.dc_len[e];
+        for (uint32_t s = 0; s < RG_DIST_SLOTS; s++) ring |= ((s >= head ? s - head : s + RG_DIST_SLOTS - head) < len ? 1u : 0u) << s;
+    }
+    if (L.sections & RG_SEC_DCMAP) io_copy_slots(rec + L.o_dcmap, reinterpret_cast<const uint8_t *>(S.dc_map) + (size_t)e * L.b_dcmap, L.b_dcmap, ring, lane);
+    if (L.sections & RG_SEC_DCWALK) io_copy_slots(rec + L.o_dcwalk, reinterpret_cast<const uint8_t *>(S.dc_walk) + (size_t)e * L.b_dcwalk, L.b_dcwalk, ring & S.dc_own[e], lane);
     io_copy(rec + L.o_status, reinterpret_cast<const uint8_t *>(S.status + (size_t)e * 10), 40, 48, lane);
     if (L.sections & RG_SEC_OBSREC) io_copy(rec + L.o_obsrec, reinterpret_cast<const uint8_t *>(S.obs_rec) + (size_t)e * L.b_obsrec, L.b_obsrec, RG_STATE_PAD16(L.b_obsrec), lane);
     for (uint32_t i = L.o_words + 4 * L.n_words + lane; i < L.base; i += WAVE) rec[i] = 0;  // (the word section's padding; the words: k_state_words_save)
@@ -110,7 +129,10 @@ __global__ void __launch_bounds__(IO_THREADS) k_state_words_save(int n, RgIoLayo
                 v = io_ld(d, e);
                 if (d & RG_IO_DESC_FLAGS) v &= ~(RG_FLAG_SCR_CHANGED | RG_FLAG_ERR_MASK);  // handle-local bits
                 const uint32_t gd = guard[c0 + w];
-                if (gd && !((io_ld(desc[(gd & 0xffffffu) - 1], e) >> (gd >> RG_IO_GUARD_SHIFT)) & 1u)) v = 0;  // an empty slot's stale word
+                if (gd & RG_IO_GUARD_RING) {  // a dist-cache key outside the ring
+                    const uint32_t head = io_ld(desc[(gd & 0xffffffu) - 1], e), len = io_ld(desc[gd & 0xffffffu], e), sl = (gd >> RG_IO_GUARD_SHIFT) & 15u;
+                    if ((sl >= head ? sl - head : sl + RG_DIST_SLOTS - head) >= len) v = 0;
+                } else if (gd && !((io_ld(desc[(gd & 0xffffffu) - 1], e) >> (gd >> RG_IO_GUARD_SHIFT)) & 1u)) v = 0;  // an empty slot's stale word
             }
             tile[l * (IO_CH + 1) + w] = v;
         }
@@ -179,7 +201,7 @@ __global__ void __launch_bounds__(IO_THREADS) k_state_words_load(int n, RgIoLayo
                 const uint32_t *rw = reinterpret_cast<const uint32_t *>(recs + (size_t)(r0 + l) * rec_bytes + L.o_words);
                 const uint32_t gd = guard[c0 + w];
                 uint32_t v = rw[c0 + w];
-                if (gd && !((rw[(gd & 0xffffffu) - 1] >> (gd >> RG_IO_GUARD_SHIFT)) & 1u)) v = 0;  // an empty slot's stale word
+                if (gd && !(gd & RG_IO_GUARD_RING) && !((rw[(gd & 0xffffffu) - 1] >> (gd >> RG_IO_GUARD_SHIFT)) & 1u)) v = 0;  // an empty slot's stale word
                 tile[l * (IO_CH + 1) + w] = v;
             }
         }
@@ -240,6 +262,10 @@ void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc,
         hipLaunchKernelGGL(k_state_rec_load, dim3((k + IO_RPB - 1) / IO_RPB), dim3(WAVE * IO_RPB), 0, st, *S, *L, ids, k, recs, rec_bytes, ok, mark);
         if (L->n_words) hipLaunchKernelGGL(k_state_words_load, dim3((k + IO_WPB - 1) / IO_WPB), dim3(IO_THREADS), 0, st, S->n, *L, desc, guard, ids, k, recs, rec_bytes, ok);
     }
+    hipLaunchKernelGGL(k_state_stairs, dim3((S->n + IO_THREADS - 1) / IO_THREADS), dim3(IO_THREADS), 0, st, *S, *L, mark);
+}
+// the stair set behind any other partial writer of player positions that marked its envs (the list-driven build of rg_reset_envs / rg_reset_mask)
+void rgk_state_stairs(const RgState *S, const RgIoLayout *L, uint8_t *mark, hipStream_t st) {
     hipLaunchKernelGGL(k_state_stairs, dim3((S->n + IO_THREADS - 1) / IO_THREADS), dim3(IO_THREADS), 0, st, *S, *L, mark);
 }
 }

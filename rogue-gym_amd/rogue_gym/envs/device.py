@@ -141,6 +141,42 @@ class HipVecRogueEnv:
         self._h.check(self._h.L.rg_reset(self._h.h))
         return self._encode()
 
+    def reset_envs(self, env_ids=None, mask=None, seeds=None):
+        """Rebuild the chosen envs as reset() rebuilds every env (rg_reset_envs / rg_reset_mask) and return the observation batch, re-encoded; every
+        other env keeps its state.  Exactly one of env_ids (a list, a numpy array or a device tensor of env indices, without duplicates) and mask (a
+        bool / uint8 device tensor [num_envs], True = rebuild; it never reaches the host) is given.  seeds (optional, with host env_ids only): one
+        int of up to 128 bits per id, given to those envs first (rg_seed_envs) -- they restart on it now and at every later reset."""
+        torch = self.torch
+        if (env_ids is None) == (mask is None):
+            raise ValueError("reset_envs needs exactly one of env_ids and mask")
+        L, h = self._h.L, self._h.h
+        if mask is not None:
+            if seeds is not None:
+                raise ValueError("reset_envs: seeds go with host env_ids, not with a mask")
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,):
+                raise ValueError("reset_envs: mask must be a bool / uint8 tensor [%d] on %s, got %s" % (
+                    self.num_envs, self.device, "%s %s on %s" % (tuple(mask.shape), mask.dtype, mask.device) if isinstance(mask, torch.Tensor) else type(mask).__name__))
+            mask = mask.contiguous()
+            self._h.check(L.rg_reset_mask(h, C.c_void_p(mask.data_ptr())))  # (a bool tensor is one byte per element, 0 / 1)
+            return self._encode()
+        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
+        if on_dev and torch.unique(_keep).numel() != k:
+            raise ValueError("reset_envs: duplicate env_ids")
+        if seeds is not None:
+            if on_dev:
+                raise ValueError("reset_envs: seeds go with host env_ids, not with a device tensor")
+            seeds = [int(s) for s in seeds]
+            if len(seeds) != k or any(s < 0 or s >> 128 for s in seeds):
+                raise ValueError("reset_envs: seeds must be %d ints in [0, 2**128), one per env id" % k)
+            lo = (C.c_uint64 * k)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
+            hi = (C.c_uint64 * k)(*[s >> 64 for s in seeds])
+            self._h.check(L.rg_seed_envs(h, ptr, lo, hi, k))
+        if k == 0:  # (an empty device tensor has no address, and a NULL list means every env)
+            _keep = np.zeros(1, np.int32)
+            ptr, on_dev = C.c_void_p(_keep.ctypes.data), 0
+        self._h.check(L.rg_reset_envs(h, ptr, k, on_dev))
+        return self._encode()
+
     def seed(self, seeds):
         seeds = [int(s) for s in seeds]
         n = len(seeds)
@@ -391,3 +427,19 @@ class HipVecStairReward(HipVecRogueEnv):
         super().__init__(*args, **kwargs)
         self.stair_reward = float(stair_reward)
         self._h.check(self._h.L.rg_set_stair_reward(self._h.h, self.stair_reward))
+
+
+class HipVecFirstFloor(HipVecStairReward):
+    """FirstFloorEnv (python/rogue_gym/envs/wrappers.py:35-43) on device tensors, with the auto-reset convention of ThreadConductor::step: an env that reports
+    dungeon level 2 after a step has finished its episode -- it is rebuilt at once (rg_reset_mask; the mask is computed on the device, nothing synchronises)
+    and the step returns its post-reset observation with `done` true and the step's reward, stair bonus included.  The bonus rule lives in the step kernel and
+    pays only in a step that descends, so a rebuilt env (level 1 again) is not paid twice.  `reward` and `done` are new tensors here: the handle's own are
+    rewritten by the rebuild (reward 0, done 0)."""
+
+    def step_keys(self, keys):
+        _, reward, done = super().step_keys(keys)
+        reached = (self.status[:, 0] >= 2) & ~done
+        reward = reward.clone()
+        done = done | reached
+        obs = self.reset_envs(mask=reached)
+        return obs, reward, done
