@@ -140,6 +140,12 @@ int rg_done(rg_t *h, uint8_t **dev);
  * The bonus is part of the reward mirror and of the compact record (rg_pack_compact / rg_allgather_compact).  0 (the default) = off. */
 int rg_set_stair_reward(rg_t *h, float bonus);
 
+/* rg_step_obs_gray on the plain f32 gray image of a 512-cell grid stepped by the capped W <= 32 kernel (no status planes, no history plane, no config
+ * groups, no bound tensor) lets the step waves that finish early write their envs' images themselves and a residual pass the rest (DESIGN.md section 4:
+ * the tail encode).  on = 0: the step kernel and the full observation pass one after the other, as on every other handle -- the same bits either way (A/B
+ * runs, twin-handle tests).  Default: on.  The Python binding calls it with 0 for a handle created while ROGUE_GYM_HIP_NO_TAIL_ENCODE=1 is set. */
+int rg_tail_encode(rg_t *h, int on);
+
 /* PlayerState::gray_image[_with_hist] / symbol_image[_with_hist] for the whole batch
  * (python/src/lib.rs:72-111,162-205; flags.rs:88-115; symbol.rs:17-71), written straight into
  * out_dev = f32 [n_env][C][H][W] with C = 1 (gray) or `symbols` (one-hot) + popcount(status_flag)

@@ -47,6 +47,9 @@ void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int
 void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st);
 int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, int kind, float *out, uint32_t *err_any, int planes_sym, int bound, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st);
+int rgk_obs_tail_capable(const RgState *S, const RgConfig *c);
+int rgk_step_tail_capable(const RgConfig *c);
+void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any, hipStream_t st, hipEvent_t ev0,
                   hipEvent_t ev1);
 int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
@@ -59,6 +62,10 @@ void rgk_reset_compact(const uint8_t *mask, int n, int32_t *list, uint32_t *cnt,
 void rgk_build_list(const RgState *S, const RgConfig *c, const int32_t *list, const uint32_t *cnt, uint8_t *mark, hipStream_t st);
 }
 
+// RgState::enc_cut: step waves that reach their tail within 40 us of their start encode their envs' images there, later ones leave them to k_obs_resid.
+// On the headline batch the first waves end at ~33 us, half of them by ~41 us and the last at ~55 us; the stream of the early ones runs beside the turns of
+// the late ones, the rest of it beside the residual pass's Redraw chains.  Swept on one box, 27 .. 52 us and none: profiles/r09_experiments.txt.
+#define RG_ENC_CUT_TICKS 4000u
 #define RG_TIMED_KERNELS 5   // k_step, k_render, k_obs (or the unfused encode), k_build, k_regen
 struct rg_handle {
     RgParsed parsed;             // config of env 0 (all envs agree except for the seed)
@@ -87,6 +94,9 @@ struct rg_handle {
     // rg_obs_bind: the caller's standing observation tensor and whether its contents are the current screens of every env up to the SCR_CHANGED / REDRAW flags
     float *bound_out = nullptr; int bound_kind = 0; bool bound_valid = false;
     int32_t *obs_list_mem = nullptr; uint32_t *obs_cnt_mem = nullptr; float *gray_lut_mem = nullptr;
+    // the tail encode (rg_state.h enc_out): rg_step_obs_gray's step launch writes the images of the envs it leaves without a Redraw itself, the pass behind it the rest.
+    // Whether it applies is decided when the handle is created (the grid and step-kernel class); rg_tail_encode(h, 0) keeps the two full passes; armed per call.
+    bool tail_enc = false, tail_enc_off = false;
     int bound_steps = 0;   // k_step launches since the bound tensor was last written: its in-place pass works from the list of exactly ONE
     int stair_gen = 0;           // producers of the stair set launched so far (k_build, k_step, the debug descent; rg_state.h)
     float *obs_scratch = nullptr;  // rg_obs_host: device-side observation buffer, kept between calls
@@ -223,6 +233,7 @@ static void destroy_handle(rg_handle *h);  // (synchronises and destroys the bac
 // what differs between the envs of one config group: the seed, or the range a fresh seed is drawn from
 struct EnvSeed { bool has_seed, has_range; uint64_t lo, hi; unsigned __int128 r0, r1; };
 
+static int ensure_gray_lut(rg_handle *h);
 static int create_homog(const RgParsed &parsed, const EnvSeed *seeds, int n_env, uint64_t max_steps, int device, int auto_reset, rg_handle **out) {
     *out = nullptr;
     rg_handle *h = new rg_handle();
@@ -292,6 +303,14 @@ static int create_homog(const RgParsed &parsed, const EnvSeed *seeds, int n_env,
     if (ok && nr <= RG_OBS_MAX_ROOMS) ok = dev_alloc(h, &S.obs_rec, n * (size_t)RG_OBS_REC_WORDS(nr));
     if (ok && nr <= RG_OVL_MAX && getenv("ROGUE_GYM_HIP_NO_MIRROR_UPDATE") == nullptr)  // (the A side: every Redraw drawn from the tiles by the observation pass)
         ok = dev_alloc(h, &S.ovl, (nr + 1) * n) && hipMemset(S.ovl, 0xff, (nr + 1) * n * 2) == hipSuccess;
+    {   // the tail encode: the capped W <= 32 step kernel on a grid of exactly 512 cells (rg_kernels.hip rgk_step_tail_capable) whose Redraws the turn and the stream pass handle
+        if (ok && rgk_step_tail_capable(&h->cfg) && S.ovl && S.obs_rec) {
+            ok = dev_alloc(h, &S.enc_stamp, n) && ensure_gray_lut(h) == 0;
+            h->tail_enc = ok;
+            S.enc_cut = RG_ENC_CUT_TICKS;
+            if (const char *ev = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_CUT")) S.enc_cut = (uint32_t)atoi(ev);  // (development: the sweep; 0 = every wave leaves its envs to the pass)
+        }
+    }
     h->spares = auto_reset != 0 && getenv("ROGUE_GYM_HIP_NO_SPARES") == nullptr;
     // which producer refills the consumed spares: one level per LANE (rg_regen_lanes.hip; two spares per env, rg_state.h sp_slots) where it applies,
     // else -- or with ROGUE_GYM_HIP_WAVE_REGEN=1 -- one level per wave (k_regen, one spare per env)
@@ -593,7 +612,29 @@ int rg_reset(rg_t *h) {
 static int obs_common(rg_t *h, uint32_t status_flag, int with_hist, int kind, float *out_dev);
 int rg_step(rg_t *h, const uint8_t *keys, int keys_on_device) { return rg_step_prefix(h, keys, h->S.n, keys_on_device); }
 int rg_step_obs_gray(rg_t *h, const uint8_t *keys, int keys_on_device, uint32_t status_flag, int with_hist, float *out_dev) {
-    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : obs_common(h, status_flag, with_hist, 0, out_dev);
+    // The tail encode: the plain f32 gray image of an ordinary handle without a bound tensor, where rgk_obs would stream it (k_obs_stream) and the step is the
+    // capped W <= 32 kernel's -- this launch's waves write the images of the envs they leave without a Redraw, k_obs_resid the others.  Armed for this launch
+    // only: rg_step alone, and every observation call on its own, are what they were.
+    const bool enc = h->tail_enc && !h->tail_enc_off && h->sub.empty() && (status_flag & 0x1ffu) == 0 && !with_hist && !h->bound_out && out_dev && rgk_obs_tail_capable(&h->S, &h->cfg);
+    if (enc) {
+        h->S.enc_out = out_dev;
+        h->S.enc_step = (uint32_t)(h->step_count % 0xffffffffull) + 1u;  // (never 0.  step_count only grows -- rg_reset and rg_state_load leave it -- so an env's older stamps are older
+                                                                          // launches' and differ from this one; the value comes round again after 2^32 - 1 launches, by when the env would
+                                                                          // have to have gone unstamped for every one of them)
+    }
+    const int rc = rg_step_prefix(h, keys, h->S.n, keys_on_device);
+    h->S.enc_out = nullptr;
+    if (rc) return 1;
+    if (!enc) return obs_common(h, status_flag, with_hist, 0, out_dev);
+    {
+        TimedLaunch t(h, 2, true);
+        rgk_obs_resid(&h->S, &h->cfg, out_dev, h->stream, t.start_ev(), t.stop_ev());
+    }
+    HIPCHK(h, hipGetLastError());
+    h->render_pending = false;
+    h->bound_valid = false;
+    h->bound_steps = 0;
+    return 0;
 }
 
 int rg_step_prefix(rg_t *h, const uint8_t *keys, int n_keys, int keys_on_device) {
@@ -717,6 +758,12 @@ int rg_set_stair_reward(rg_t *h, float bonus) {
     return 0;
 }
 
+int rg_tail_encode(rg_t *h, int on) {
+    h->tail_enc_off = on == 0;  // (a handle the tail encode does not apply to takes the two passes either way)
+    for (rg_handle *sh : h->sub) sh->tail_enc_off = on == 0;
+    return 0;
+}
+
 int rg_obs_channels(const rg_t *h, int symbol, uint32_t status_flag, int with_hist) {
     return (symbol ? h->planes_sym : 1) + __builtin_popcount(status_flag & 0x1ffu) + (with_hist ? 1 : 0);
 }
@@ -767,6 +814,18 @@ static uint32_t host_tile_to_sym(uint32_t t) {
     default: return (t >= 'A' && t <= 'Z') ? t - 'A' + 17 : 255u;
     }
 }
+// RgState::gray_lut: the value the observation pass encodes a glyph to (rg_obs.hip `lutf`: the same single IEEE division), for the step kernels that write
+// gray pixels themselves (a bound gray tensor's mirror update, the tail encode)
+static int ensure_gray_lut(rg_handle *h) {
+    if (!h->gray_lut_mem) {
+        float lut[128];
+        for (uint32_t g = 0; g < 128; g++) lut[g] = (float)(uint8_t)host_tile_to_sym(g) / (float)(uint8_t)h->cfg.symbols;
+        if (!dev_alloc(h, &h->gray_lut_mem, 128)) return 1;
+        HIPCHK(h, hipMemcpy(h->gray_lut_mem, lut, sizeof lut, hipMemcpyHostToDevice));
+    }
+    h->S.gray_lut = h->gray_lut_mem;
+    return 0;
+}
 int rg_obs_bind(rg_t *h, int kind, uint32_t status_flag, int with_hist, float *out_dev) {
     if (!h->sub.empty()) { h->err = "rg_obs_bind: not for a handle with config groups"; return 1; }
     if (out_dev && ((status_flag & 0x1ffu) || with_hist || (kind != 0 && kind != 1))) { h->err = "rg_obs_bind: gray or symbol image without status planes and history plane"; return 1; }
@@ -779,13 +838,7 @@ int rg_obs_bind(rg_t *h, int kind, uint32_t status_flag, int with_hist, float *o
     if (out_dev) HIPCHK(h, hipMemsetAsync(h->obs_cnt_mem, 0, 8, h->stream));
     h->S.obs_list = out_dev ? h->obs_list_mem : nullptr; h->S.obs_cnt = out_dev ? h->obs_cnt_mem : nullptr;
     h->S.bound_gray = (out_dev && kind == 0) ? out_dev : nullptr;  // (k_step's mirror update writes a gray image's changed pixels itself)
-    if (h->S.bound_gray && !h->gray_lut_mem) {  // ... through this table: the value k_obs encodes a glyph to (rg_obs.hip `lutf`: the same single IEEE division)
-        float lut[128];
-        for (uint32_t g = 0; g < 128; g++) lut[g] = (float)(uint8_t)host_tile_to_sym(g) / (float)(uint8_t)h->cfg.symbols;
-        if (!dev_alloc(h, &h->gray_lut_mem, 128)) return 1;
-        HIPCHK(h, hipMemcpy(h->gray_lut_mem, lut, sizeof lut, hipMemcpyHostToDevice));
-    }
-    h->S.gray_lut = h->gray_lut_mem;
+    if (h->S.bound_gray && ensure_gray_lut(h)) return 1;  // ... through this table
     h->bound_out = out_dev; h->bound_kind = kind; h->bound_valid = false; h->bound_steps = 0;
     return 0;
 }

@@ -2604,15 +2604,85 @@ __device__ __forceinline__ void take_spares(const RgState &S, const RgState *__r
     if (taken && !(S.keep_spares && S.reseed[e] == 0)) __hip_atomic_store(&S.sp_ready[es], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The tail encode (k_step_w32<false, true>; rg_state.h enc_out): the wave writes the f32 gray images of its own envs at the very end of its turn, while
+// slower waves are still playing -- the observation pass's 134 MB stream starts when the first waves end instead of when the last one does.  Lane `encl`:
+// the env played this key and its final flag word has no pending Redraw, so its screen mirror is current (mirror_update); everything else is left to
+// the pass behind the launch (rg_obs.hip k_obs_resid), which goes by the stamp alone.  Per env exactly k_obs_stream's work: mirror words `lane` and
+// `lane + 64`, glyph -> gray value through the wave's LDS table, two whole-line non-temporal float4 stores -- the same bits.
+// The wave is alone on its SIMD by now, so nothing but its own queue hides latency: envs go in batches of ENC_BATCH (all loads of a batch, then all its
+// stores), the loads of batch b + 1 issued BEFORE the stores of batch b.  vmcnt retires in order, so the wait for batch b + 1's words leaves batch b's stores in
+// flight.  The first batch is peeled: with the loop entered straight from the loads the compiler's wait insertion merges "loads only" with the back edge's
+// "loads, then stores" and falls back to vmcnt(0) once per iteration (profiles/r09_experiments.txt).  The env of a slot is a scalar (the set bits of the
+// ballot in turn); the slots past the last env repeat it -- the same bytes to the same address -- so there is no branch inside a batch.
+#ifndef ENC_BATCH
+#define ENC_BATCH 8
+#endif
+// A wave that reaches its tail later than S.enc_cut after its own start encodes nothing and stamps nothing: its envs are streamed by the pass behind the
+// launch.  The launch is as long as its last wave, and an encode costs a wave 10-20 us while the memory system is busy with everybody else's: the waves
+// whose turn ends late would end the launch that much later, while the pass behind it has its Redraw chains to wait for anyway and streams beside them
+// (rg_api.cpp RG_ENC_CUT_TICKS; profiles/r09_experiments.txt: the sweep).  Which waves are late changes from run to run; the images do not.
+__device__ __forceinline__ void tail_encode(const RgState &S, const int lane, const int e, const bool encl) {
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const uint64_t em = __ballot(encl);
+    if (encl) S.enc_stamp[e] = S.enc_step;
+    if (!em) return;
+    const int ebase = __builtin_amdgcn_readfirstlane(e - lane);  // (an index-order wave: lane i holds env ebase + i; a stair wave: lane 0 alone)
+    // the mirror bytes this wave's lanes wrote in mirror_update are read by OTHER lanes below: drained first, and read with loads no stale L1 line can serve
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const __attribute__((address_space(3))) float *lut = (const __attribute__((address_space(3))) float *)(g_smem + STEP_LDS_LUT);
+    const uint32_t *mir = reinterpret_cast<const uint32_t *>(S.screen) + lane;
+    f4v *img = reinterpret_cast<f4v *>(S.enc_out) + lane;
+    uint64_t rem = em;
+    int last = 0;
+    struct Batch { int env[ENC_BATCH]; uint32_t w0[ENC_BATCH], w1[ENC_BATCH]; };
+    auto load = [&](Batch &b) {
+#pragma unroll
+        for (int k = 0; k < ENC_BATCH; k++) {
+            last = rem ? __builtin_ctzll(rem) : last;
+            rem &= rem - (rem ? 1ull : 0ull);
+            b.env[k] = ebase + last;
+            const uint32_t *m = mir + (size_t)b.env[k] * 128;
+            b.w0[k] = __hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            b.w1[k] = __hip_atomic_load(m + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    auto gray4 = [&](uint32_t w) {
+        w &= 0x7f7f7f7fu;
+        f4v v = {lut[w & 0xff], lut[(w >> 8) & 0xff], lut[(w >> 16) & 0xff], lut[w >> 24]};
+        return v;
+    };
+    auto store = [&](const Batch &b) {
+#pragma unroll
+        for (int k = 0; k < ENC_BATCH; k++) {
+            f4v *o = img + (size_t)b.env[k] * 128;
+            __builtin_nontemporal_store(gray4(b.w0[k]), o);
+            __builtin_nontemporal_store(gray4(b.w1[k]), o + WAVE);
+        }
+    };
+    const int nb = (__popcll(em) + ENC_BATCH - 1) / ENC_BATCH;
+    Batch cur, nxt;
+    load(cur);
+    load(nxt);  // (past the last env: its words again, loads only)
+    store(cur);
+#pragma nounroll
+    for (int b = 1; b < nb; b++) {
+        cur = nxt;
+        load(nxt);
+        store(cur);
+    }
+}
+
 // One wave's share of a step: lane i plays the key of env `e` (any env index -- the lanes of a wave need not hold consecutive envs), `valid`
 // lanes only; the other lanes still take part in the wave-cooperative services.
-template <int BW, int GM, bool BND = false>
+// ENC: the instance that ends in the tail encode (k_step_w32 only: the handle armed it for this launch, rgk_step) -- the others carry none of it.
+template <int BW, int GM, bool BND = false, bool ENC = false>
 __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__restrict__ SPd, const RgConfig &c, const uint8_t *__restrict__ keys, int use_spares, int stage_off,
                                           const int e, const bool valid_in, const int stair_role) {
     // stair_role: 0 = no stair isolation, 1 = this wave serves listed (on-stairs) envs, 2 = index-order wave: listed envs are somebody else's
     uint16_t *lds_grid = reinterpret_cast<uint16_t *>(g_smem + stage_off);  // (behind the per-lane columns: STEP_LDS_*)
     const int lane = threadIdx.x;
     Prof pf; pf.start(S.prof);
+    const unsigned long long enc_t0 = ENC ? __builtin_amdgcn_s_memrealtime() : 0ull;  // (tail_encode: S.enc_cut)
     Env E;
     E.err = 0; E.on_stairs = 0;
     uint32_t react = 0, err = 0, old_flags = 0, steps = 0, flags = 0;
@@ -2687,7 +2757,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     // Redraw (S.ovl) -- parked here from the first load round to the incremental mirror update at the end of the turn
     lds_u32 *ovl_l = (lds_u32 *)(g_smem + STEP_LDS_OVL) + lane;
     ovl_l[0] = 0;
-    if (BND && S.bound_gray) {
+    if ((BND && S.bound_gray) || ENC) {  // (ENC: the table of the tail encode, the same one)
         // glyph -> gray value as the observation pass encodes it (rg_obs.hip k_obs `lutf`, python/src/lib.rs:84), for the pixels mirror_update writes into the bound
         // tensor: the host's table straight into LDS (computed per wave -- two tile_to_sym + two IEEE divisions per lane -- it cost every wave 1.1 us)
         typedef const __attribute__((address_space(1))) void *gptr;
@@ -2905,6 +2975,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     // end: its return value is first needed behind all the stores of the tail, and vmcnt being in order it is there by then (asked for at the end, the wave
     // waited 2.6 us for it: it returns behind every store issued before it).
     bool pend = false; uint64_t pm = 0; uint32_t lbase = 0;
+    bool encl = false;  // ENC: this lane's env gets its image from the tail encode
     if (BND && S.obs_list) {
         const uint32_t fw = (live ? ((terminal && c.auto_reset) ? RG_FLAG_REDRAW : flags) : old_flags);
         pend = valid && (fw & (RG_FLAG_REDRAW | RG_FLAG_SCR_CHANGED));
@@ -2951,6 +3022,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
         if (!taken) store_env(S, E);  // (a taken env's live scalars are the spare's: copied below)
         S.steps[et] = steps;
         S.flags[et] = flags;
+        if (ENC) encl = !(flags & RG_FLAG_REDRAW);  // (this branch: the env played its key)
         S.done[et] = terminal ? 1 : 0;
         // The env's observation record (rg_state.h obs_rec; rg_obs.hip ObsTabs): the fused observation pass overlays a Redraw from these words -- one line
         // per env instead of the env's column of the [slot][env] tables.  Here: the monsters as they stand after their turn (the wave's LDS table) and the
@@ -3022,6 +3094,11 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     take_spares(S, SPd, c, lane, et, taken, on_next);
     stair_publish(S, lane, et, valid, on_next);
     pf.mark(7);
+    if constexpr (ENC) {
+        const bool late = __builtin_amdgcn_s_memrealtime() - enc_t0 > (unsigned long long)S.enc_cut;  // (wave-uniform)
+        tail_encode(S, lane, et, encl && !late);
+        pf.mark(31);
+    }
     pf.finish();
 }
 
@@ -3041,7 +3118,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
 
 // (the body is spelled out twice -- below for the capped W <= 32 instance -- rather than shared through a device function: routing the template through
 // one more inlined call changed the allocation of the wider instances for the worse, 141 -> 153 us on the default 80x24 dungeon)
-#define RG_STEP_BLOCK_BODY(BWV, GMV, BNDV) \
+#define RG_STEP_BLOCK_BODY(BWV, GMV, BNDV, ENCV) \
     __builtin_amdgcn_s_setprio(3); \
     const int lane = threadIdx.x; \
     if (blockIdx.x == 0 && lane == 0) { \
@@ -3058,7 +3135,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
         bool v; int e; \
         if (stair) { e = list[i0]; v = lane == 0 && e < S.n_keys && keys[e] == '>'; } \
         else { v = lane < epw && i0 + lane < items; e = v ? i0 + lane : 0; } \
-        if (!stair || __any(v)) step_wave<BWV, GMV, BNDV>(S, SPd, c, keys, use_spares, stage_off, e, v, parity >= 0 ? (stair ? 1 : 2) : 0); \
+        if (!stair || __any(v)) step_wave<BWV, GMV, BNDV, ENCV>(S, SPd, c, keys, use_spares, stage_off, e, v, parity >= 0 ? (stair ? 1 : 2) : 0); \
         if (!stair || items <= STAIR_BLOCKS) break; \
         __syncthreads(); \
         uint32_t t = 0; \
@@ -3072,7 +3149,7 @@ __global__ void __launch_bounds__(WAVE) k_step(RgState S, const RgState *__restr
     // STAIR_BLOCKS are handed out one at a time through a counter, so that a block busy with a descent (60 us) never has a second one queued behind
     // it while its neighbours sit idle.  An entry whose env does not press '>' stays with its index-order wave (step_wave's rule, applied here before
     // anything else of the env is loaded: such a block is gone in ~2 us).
-    RG_STEP_BLOCK_BODY(BW, (BW != 0 ? 1 : 0), BND)
+    RG_STEP_BLOCK_BODY(BW, (BW != 0 ? 1 : 0), BND, false)
 }
 // The W <= 32 instance with the register allocation capped for TWO waves per SIMD (256 VGPRs).  With the 5x5 window in LDS it needs ~250: told to,
 // the allocator fits it without a spill (left alone it lands on either side of the line from build to build).  Every block of a 65 536-env launch
@@ -3080,16 +3157,17 @@ __global__ void __launch_bounds__(WAVE) k_step(RgState S, const RgState *__restr
 // for the whole launch, as many index-order blocks started only when the first waves ended (33-38 us) and finished last (84 us against 57-67 us
 // for every other wave).  The wider instances spill under the cap (15-136 VGPRs: a measured loss) and keep their natural allocation.
 // (BND: the instance for handles with a bound observation tensor, rg_obs_bind -- the list of redrawn envs, the gray pixels of the incremental mirror update)
-template <bool BND>
+// (ENC: the instance that ends every wave in the tail encode of its envs' gray images -- tail_encode; armed per launch by rg_step_obs_gray)
+template <bool BND, bool ENC = false>
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_step_w32(RgState S, const RgState *__restrict__ SPd, RgConfig c, const uint8_t *__restrict__ keys, int use_spares, int stage_off, int epw, int parity) {
-    RG_STEP_BLOCK_BODY(0, 0, BND)
+    RG_STEP_BLOCK_BODY(0, 0, BND, ENC)
 }
 // More than 64 rooms (only possible on wide grids: 65 rooms need W >= 65): the generic row-width class with the 384-room generator.  Its LDS
 // monster table (a column of `rooms` words per lane) exceeds the 64 KB default, see rgk_step.
 __global__ void __launch_bounds__(WAVE) k_step_huge(RgState S, const RgState *__restrict__ SPd, RgConfig c, const uint8_t *__restrict__ keys, int use_spares, int stage_off,
                                                     int epw, int parity) {
-    RG_STEP_BLOCK_BODY(4, 2, false)
+    RG_STEP_BLOCK_BODY(4, 2, false, false)
 }
 #undef RG_STEP_BLOCK_BODY
 
@@ -3161,6 +3239,10 @@ int rgk_step_bound_capable(const RgConfig *c) {
     if (c->width <= 32 && gen_mode_of(c) == 0) return 1;
     return (c->width <= 96 && hw <= 4096 && c->width > 64) ? 1 : 0;
 }
+// whether rgk_step launches the instance that ends its waves in the tail encode when S->enc_out is set: the capped W <= 32 class -- the very test of the
+// dispatch below -- on a grid of exactly 512 cells (tail_encode: two mirror words per lane).  rg_api.cpp arms the encode only where this holds, so a
+// launch with enc_out set never takes another class's kernel and leaves every env to the residual pass.
+int rgk_step_tail_capable(const RgConfig *c) { return (c->width <= 32 && gen_mode_of(c) == 0 && c->width * c->height == 512) ? 1 : 0; }
 int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const bool bnd = S->obs_list != nullptr && rgk_step_bound_capable(c);
     int hw = c->width * c->height;
@@ -3184,7 +3266,7 @@ int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const u
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_step_huge), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess && dev >= 0 && dev < 64) raised[dev] = smem;
         }
         RG_LAUNCH_STEP(k_step_huge);
-    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) RG_LAUNCH_STEP(k_step_w32<true>); else RG_LAUNCH_STEP(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
+    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) RG_LAUNCH_STEP(k_step_w32<true>); else if (S->enc_out) RG_LAUNCH_STEP((k_step_w32<false, true>)); else RG_LAUNCH_STEP(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
     else if (n32 && c->width <= 64) RG_LAUNCH_STEP(k_step<1>);                        // ... a 32-column grid with 33..64 rooms (e.g. 32x48 with 8x5) steps here
     else if (n32) { if (bnd) RG_LAUNCH_STEP((k_step<2, true>)); else RG_LAUNCH_STEP(k_step<2>); }
     else if (c->width <= 128) RG_LAUNCH_STEP(k_step<3>);

@@ -456,6 +456,48 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs(RgState S, RgConfig c, uint
     }
 }
 
+// The Redraw service of k_obs_stream and k_obs_resid: one env with a pending Redraw, drawn from its tiles by the whole wave (the staged path of k_obs: LDS
+// draw, overlays, mirror write-back, encode, flag word; the barriers are the wave's own).  ONE text for both kernels, so that they cannot drift apart -- a macro
+// and not a function, like RG_STEP_BLOCK_BODY: k_obs_stream's registers are pinned (tests/test_obs_typed_resources.py), and as an inlined function the same
+// statements cost it one more.  It reads the caller's S, c, out, lane, W, HW, Q4, Q8, nrooms, rec_words, gray4 and LDS arrays (scr, tb, mtile), and e, fle, v,
+// t_rec: the env, its flag word, and its tile words and observation record, loaded ahead of time.
+#define RG_OBS_REDRAW_ENV() \
+    lds_barrier();  /* the previous Redraw's LDS reads done */                                                                                                           \
+    if (lane < rec_words) tb.w[lane] = t_rec;                                                                                                                            \
+    /* the history plane is rewritten only when the visited set changed since it was last written (k_step: HIST_DIRTY), never on a stale Redraw */                       \
+    const bool upd_hist = !(fle & RG_FLAG_HIST_STALE) && (fle & RG_FLAG_HIST_DIRTY);                                                                                     \
+    if (lane < Q8) {                                                                                                                                                     \
+        uint32_t g[2], hb[2];                                                                                                                                            \
+        draw_cells8(v, lane, W, HW, g, hb);                                                                                                                              \
+        reinterpret_cast<uint2 *>(scr)[lane] = make_uint2(g[0], g[1]);                                                                                                   \
+        if (upd_hist) reinterpret_cast<uint2 *>(S.hist + (size_t)e * HW)[lane] = make_uint2(hb[0], hb[1]);                                                               \
+    }                                                                                                                                                                    \
+    lds_barrier();                                                                                                                                                       \
+    /* entity overlays; draw priority monster < gold < player (core/src/lib.rs:271-283), as in k_obs */                                                                  \
+    const uint32_t ppos = tb.w[nrooms];                                                                                                                                  \
+    const int px = POS_X(ppos), py = POS_Y(ppos);                                                                                                                        \
+    if (lane < nrooms) {                                                                                                                                                 \
+        const uint32_t mw = tb.w[lane];                                                                                                                                  \
+        if ((mw >> 24) & MF_ALIVE) {                                                                                                                                     \
+            const int x = POS_X(mw), y = POS_Y(mw);                                                                                                                      \
+            const uint32_t under = scr[y * W + x];                                                                                                                       \
+            if (monster_shown(c, &tb, nrooms, px, py, x, y) && (under & 0x80u) && under != (0x80u | '*')) scr[y * W + x] = (uint8_t)(0x80u | mtile[(mw >> 16) & 0xff]);  \
+        }                                                                                                                                                                \
+    }                                                                                                                                                                    \
+    lds_barrier();                                                                                                                                                       \
+    if (lane == 0 && (scr[py * W + px] & 0x80u)) scr[py * W + px] = (uint8_t)(0x80u | '@');                                                                              \
+    lds_barrier();                                                                                                                                                       \
+    uint32_t *m4 = reinterpret_cast<uint32_t *>(S.screen + (size_t)e * HW);                                                                                              \
+    float4 *oe = reinterpret_cast<float4 *>(out) + (size_t)e * Q4;                                                                                                       \
+    for (int q = lane; q < Q4; q += WAVE) {                                                                                                                              \
+        const uint32_t g = reinterpret_cast<const uint32_t *>(scr)[q] & 0x7f7f7f7fu;                                                                                     \
+        m4[q] = g;                                                                                                                                                       \
+        store_obs(&oe[q], gray4(g));                                                                                                                                     \
+    }                                                                                                                                                                    \
+    if (lane == 0)  /* (rg_obs.hip k_obs: a stale Redraw leaves the history mirror one level behind) */                                                                  \
+        S.flags[e] = (fle & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fle & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY))) |                        \
+                     ((fle & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u);
+
 // ---------------------------------------------------------------------------------------------
 // k_obs_stream: the gray image without status / history planes, no config groups, not bound, on grids of at most 512 cells (the headline workload:
 // 65 536 mini envs).  Same bits, flags and mirrors as k_obs<0, false>.
@@ -539,43 +581,93 @@ __global__ void __launch_bounds__(WAVE) k_obs_stream(RgState S, RgConfig c, floa
             const uint4 v = tv;
             const uint32_t t_rec = trec;
             if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);
-            lds_barrier();  // the previous Redraw's LDS reads done
-            if (lane < rec_words) tb.w[lane] = t_rec;
-            // the history plane is rewritten only when the visited set changed since it was last written (k_step: HIST_DIRTY), never on a stale Redraw
-            const bool upd_hist = !(fle & RG_FLAG_HIST_STALE) && (fle & RG_FLAG_HIST_DIRTY);
-            if (lane < Q8) {
-                uint32_t g[2], hb[2];
-                draw_cells8(v, lane, W, HW, g, hb);
-                reinterpret_cast<uint2 *>(scr)[lane] = make_uint2(g[0], g[1]);
-                if (upd_hist) reinterpret_cast<uint2 *>(S.hist + (size_t)e * HW)[lane] = make_uint2(hb[0], hb[1]);
-            }
-            lds_barrier();
-            // entity overlays; draw priority monster < gold < player (core/src/lib.rs:271-283), as in k_obs
-            const uint32_t ppos = tb.w[nrooms];
-            const int px = POS_X(ppos), py = POS_Y(ppos);
-            if (lane < nrooms) {
-                const uint32_t mw = tb.w[lane];
-                if ((mw >> 24) & MF_ALIVE) {
-                    const int x = POS_X(mw), y = POS_Y(mw);
-                    const uint32_t under = scr[y * W + x];
-                    if (monster_shown(c, &tb, nrooms, px, py, x, y) && (under & 0x80u) && under != (0x80u | '*')) scr[y * W + x] = (uint8_t)(0x80u | mtile[(mw >> 16) & 0xff]);
-                }
-            }
-            lds_barrier();
-            if (lane == 0 && (scr[py * W + px] & 0x80u)) scr[py * W + px] = (uint8_t)(0x80u | '@');
-            lds_barrier();
-            uint32_t *m4 = reinterpret_cast<uint32_t *>(S.screen + (size_t)e * HW);
-            float4 *oe = reinterpret_cast<float4 *>(out) + (size_t)e * Q4;
-            for (int q = lane; q < Q4; q += WAVE) {
-                const uint32_t g = reinterpret_cast<const uint32_t *>(scr)[q] & 0x7f7f7f7fu;
-                m4[q] = g;
-                store_obs(&oe[q], gray4(g));
-            }
-            if (lane == 0)  // (rg_obs.hip k_obs: a stale Redraw leaves the history mirror one level behind)
-                S.flags[e] = (fle & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | ((fle & RG_FLAG_HIST_STALE) ? 0u : RG_FLAG_HIST_DIRTY))) |
-                             ((fle & RG_FLAG_HIST_STALE) ? RG_FLAG_HIST_LAG : 0u);
+            RG_OBS_REDRAW_ENV();
         }
         cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_obs_resid: the observation pass behind a step launch that encoded in its waves' tails (rg_kernels.hip tail_encode; RgState::enc_stamp).  It serves the
+// envs the tails left -- stamp != this launch's enc_step -- and nothing else: a stamped env costs its share of one coalesced load of flag words and stamps.
+// The stamp alone says "already encoded": an unstamped env with a pending Redraw is drawn from the tiles exactly as k_obs_stream draws it (mirror
+// write-back, history plane, flag word); an unstamped env without one (its wave ended late and left the stream to this pass, no key, an error) is streamed
+// from its mirror as k_obs_stream streams it.  Same bits as k_obs_stream.
+// ---------------------------------------------------------------------------------------------
+// One wave owns a run of OBS_RESID_RUN consecutive envs, persistent and one run ahead with the flag words and stamps (lane i: env i of the run).  The mirror
+// words of the run's unstamped envs are requested together once those are known, then stored; then the run's Redraw envs, one at a time.
+#ifndef OBS_RESID_RUN
+#define OBS_RESID_RUN 4
+#endif
+#ifndef OBS_RESID_WAVES
+#define OBS_RESID_WAVES 16384
+#endif
+__global__ void __launch_bounds__(WAVE) k_obs_resid(RgState S, RgConfig c, float *__restrict__ out) {
+    __shared__ float lutf[128];                              // glyph -> gray value
+    __shared__ uint8_t mtile[RG_MAX_ENEMY_KINDS + 6];        // monster type -> glyph
+    __shared__ __align__(16) uint8_t scr[512];               // the staged screen of a Redraw env (HW = 512: rgk_obs_tail_capable)
+    __shared__ ObsTabs tb;                                   // its observation record
+    const int lane = threadIdx.x, W = c.width, HW = W * c.height, Q4 = HW >> 2, Q8 = HW >> 3, n = S.n;
+    const int nrooms = c.room_num_x * c.room_num_y, rec_words = RG_OBS_REC_WORDS(nrooms);
+    const int nruns = (n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
+    // a run's flag words and stamps; a lane past the run or the batch holds this launch's stamp: nothing to serve
+    auto load_run = [&](int r, uint32_t &fl, uint32_t &stamp) {
+        const int base = r * OBS_RESID_RUN;
+        const bool in = r < nruns && lane < OBS_RESID_RUN && base + lane < n;
+        fl = in ? S.flags[base + lane] : 0u;
+        stamp = in ? S.enc_stamp[base + lane] : S.enc_step;
+    };
+    uint32_t fl_cur, st_cur;
+    load_run(blockIdx.x, fl_cur, st_cur);
+    // the table the step kernel's tails encoded with (RgState::gray_lut: the host's, the same single division as k_obs_stream's)
+    lutf[lane] = S.gray_lut[lane];
+    lutf[lane + WAVE] = S.gray_lut[lane + WAVE];
+    for (int g = lane; g < RG_MAX_ENEMY_KINDS + 6; g += WAVE) mtile[g] = c.mon[g].tile;
+    lds_barrier();
+    auto gray4 = [&](uint32_t w) {
+        w &= 0x7f7f7f7fu;
+        float4 v; v.x = lutf[w & 0xff]; v.y = lutf[(w >> 8) & 0xff]; v.z = lutf[(w >> 16) & 0xff]; v.w = lutf[w >> 24];
+        return v;
+    };
+    auto load_tiles = [&](int e, uint4 &v, uint32_t &rec) {
+        v = lane < Q8 ? reinterpret_cast<const uint4 *>(S.cell + (size_t)e * HW)[lane] : make_uint4(0, 0, 0, 0);
+        rec = lane < rec_words ? S.obs_rec[(size_t)e * rec_words + lane] : 0u;
+    };
+    for (int r = blockIdx.x; r < nruns; r += gridDim.x) {
+        const int base = r * OBS_RESID_RUN;
+        const uint32_t fl = fl_cur;
+        const bool need = st_cur != S.enc_step;
+        load_run(r + gridDim.x, fl_cur, st_cur);
+        uint64_t rmask = __ballot(need && (fl & RG_FLAG_REDRAW));
+        const uint64_t smask = __ballot(need && !(fl & RG_FLAG_REDRAW));
+        if (!(rmask | smask)) continue;
+        uint4 tv = make_uint4(0, 0, 0, 0);
+        uint32_t trec = 0;
+        if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);  // in flight while the mirror-streamed envs are served
+        const uint32_t *m = reinterpret_cast<const uint32_t *>(S.screen) + (size_t)base * Q4;
+        float4 *o = reinterpret_cast<float4 *>(out) + (size_t)base * Q4;
+        uint32_t w0[OBS_RESID_RUN], w1[OBS_RESID_RUN];
+#pragma unroll
+        for (int i = 0; i < OBS_RESID_RUN; i++) {  // (run-uniform branches)
+            w0[i] = w1[i] = 0u;
+            if ((smask >> i) & 1) { w0[i] = m[i * Q4 + lane]; w1[i] = m[i * Q4 + lane + WAVE]; }
+        }
+#pragma unroll
+        for (int i = 0; i < OBS_RESID_RUN; i++) {
+            if (!((smask >> i) & 1)) continue;
+            store_obs(&o[i * Q4 + lane], gray4(w0[i]));
+            store_obs(&o[i * Q4 + lane + WAVE], gray4(w1[i]));
+        }
+        while (rmask) {  // (k_obs_stream's Redraw service)
+            const int i = __builtin_ctzll(rmask);
+            rmask &= rmask - 1;
+            const int e = base + i;
+            const uint32_t fle = __builtin_amdgcn_readlane(fl, i);
+            const uint4 v = tv;
+            const uint32_t t_rec = trec;
+            if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);
+            RG_OBS_REDRAW_ENV();
+        }
     }
 }
 
@@ -1099,6 +1191,24 @@ int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, 
     else RG_LAUNCH_OBS(k_obs<1, true>);
 #undef RG_LAUNCH_OBS
     return 1;
+}
+// whether rgk_obs serves this handle's plain gray image (no status planes, no history plane, not bound) with k_obs_stream -- of the conditions under which
+// rg_step_obs_gray arms the tail encode, the ones that are this file's -- on a grid of exactly 512 cells (two mirror words per lane)
+int rgk_obs_tail_capable(const RgState *S, const RgConfig *c) {
+    const int hw = c->width * c->height, nr = c->room_num_x * c->room_num_y;
+    if (hw != 512 || nr > RG_OBS_MAX_ROOMS || !S->obs_rec || !S->ovl || S->ext) return 0;
+    if (RG_OBS_REC_WORDS(nr) > WAVE) return 0;
+#ifdef RG_DEV_KNOBS
+    if (const char *ev = getenv("RG_OBS_STREAM")) if (atoi(ev) == 0) return 0;
+#endif
+    return 1;
+}
+// the observation pass behind a step launch that encoded in its tails (S->enc_stamp / enc_step are that launch's): the envs it left
+void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    int blocks = (S->n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
+    if (blocks > OBS_RESID_WAVES) blocks = OBS_RESID_WAVES;
+    if (ev0 || ev1) hipExtLaunchKernelGGL(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, 0, *S, *c, out);
+    else hipLaunchKernelGGL(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, *S, *c, out);
 }
 void rgk_encode(const uint8_t *screen, const uint8_t *hist, const int32_t *status, uint32_t *flags, uint32_t *err_any, int n, int hw, size_t rs, size_t rst,
                 int symbols, int planes_sym, uint32_t sflag, int with_hist, int kind, float *out, const int32_t *ext, hipStream_t st) {

@@ -137,6 +137,13 @@ struct RgState {
     float *bound_gray;   // the bound tensor itself when it is a GRAY image [n][1][H][W]: the turn's incremental mirror update writes the pixels it changes straight
                          // into it (k_step mirror_update), so such an env needs no observation pass at all; NULL otherwise
     const float *gray_lut;  // [128] glyph -> gray value as the observation pass encodes it (rg_obs_bind fills it on the host: symbol id / symbols, one IEEE division)
+    // The tail encode (rg_step_obs_gray on an eligible handle; rg_kernels.hip tail_encode): a step wave that has finished its turn writes the f32 gray image of
+    // each of its envs that played and is left without a pending Redraw into enc_out, from the screen mirror, and stamps the env with enc_step; the
+    // observation pass behind it (rg_obs.hip k_obs_resid) serves exactly the envs whose stamp is not this launch's.  enc_out == NULL: the launch encodes nothing.
+    float *enc_out;      // this step's observation tensor [n][1][H][W], H * W = 512
+    uint32_t *enc_stamp; // [n] the enc_step of the last launch whose tail wrote the env's image
+    uint32_t enc_step;   // this launch's stamp, never 0 (the stamps start at 0)
+    uint32_t enc_cut;    // a wave that reaches its tail later than this after its own start (ticks of the chip-wide 100 MHz clock) encodes and stamps nothing
     int32_t *obs_list;   // [2][n]
     uint32_t *obs_cnt;   // [2]
     int32_t obs_par;     // which half this launch writes (set by the host before every k_step)

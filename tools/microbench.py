@@ -60,7 +60,7 @@ if __name__ == "__main__":
 
 
 PHASES = {0: "load", 26: "window load", 1: "pre-gen/post-loop", 2: "gen_service", 28: "player action", 29: "turn_passed", 30: "mon prepass", 3: "dist lookup",
-          27: "fill+flush", 4: "bfs", 5: "monsters", 6: "tail", 7: "stores + spare take"}
+          27: "fill+flush", 4: "bfs", 5: "monsters", 6: "tail", 7: "stores + spare take", 31: "tail encode"}
 GEN_PHASES = {8: "g.clear", 9: "g.rooms", 10: "g.paint", 11: "g.passages", 12: "g.corridors", 13: "g.gold", 14: "g.stair", 15: "g.monsters", 17: "g.reveal", 18: "g.place",
               19: "g.hand-back", 21: "g.barrier", 16: "g.copy-out", 23: "g.barrier2", 20: "g.total",
               # -DRG_FINE_PROF builds only: inside connect_rooms (40 = everything between two connects) and the monster loop
@@ -84,8 +84,14 @@ def prof(name, cfg, keys_table, n=65536, launches=20, max_steps=1000, do_reset=F
         bound = torch.empty((n, 1, h.height, h.width), dtype=torch.float32, device=dev)
         h.check(L.rg_obs_bind(h.h, 0, 0, 0, C.c_void_p(bound.data_ptr())))
         h.check(L.rg_obs_gray(h.h, 0, 0, C.c_void_p(bound.data_ptr())))
+    fused = None
+    if os.environ.get("RG_PROF_FUSED"):  # the step and the gray observation as one call (rg_step_obs_gray): the step-kernel instance that encodes in its waves' tails
+        fused = torch.empty((n, 1, h.height, h.width), dtype=torch.float32, device=dev)
+        L_step = lambda hh, k, on_dev: L.rg_step_obs_gray(hh, k, on_dev, 0, 0, C.c_void_p(fused.data_ptr()))
+    else:
+        L_step = L.rg_step
     for t in range(warm):
-        L.rg_step(h.h, C.c_void_p(keys[t % 64].data_ptr()), 1)
+        L_step(h.h, C.c_void_p(keys[t % 64].data_ptr()), 1)
         if bound is not None:
             L.rg_obs_gray(h.h, 0, 0, C.c_void_p(bound.data_ptr()))
     nw = (n + 15) // 16  # rows: one per wave of the launch (16..64 envs per wave); unused rows stay zero
@@ -98,7 +104,7 @@ def prof(name, cfg, keys_table, n=65536, launches=20, max_steps=1000, do_reset=F
         if do_reset:
             L.rg_reset(h.h)
         else:
-            L.rg_step(h.h, C.c_void_p(keys[t % 64].data_ptr()), 1)
+            L_step(h.h, C.c_void_p(keys[t % 64].data_ptr()), 1)
             if bound is not None:
                 L.rg_obs_gray(h.h, 0, 0, C.c_void_p(bound.data_ptr()))
         L.rg_prof(h.h, 1, buf.ctypes.data_as(C.c_void_p))
@@ -124,6 +130,8 @@ def prof(name, cfg, keys_table, n=65536, launches=20, max_steps=1000, do_reset=F
     kidx = 3 if do_reset else 0
     print("%s: kernel (HIP events) %.1f us; slowest wave avg %.1f us, mean wave %.1f us" %
           (name, ms[kidx] / max(cnt[kidx], 1) * 1e3, np.mean([t.max() for t in totals]) * TICK_US, tot.mean() * TICK_US))
+    if fused is not None:
+        print("   observation pass behind it (HIP events) %.1f us" % (ms[2] / max(cnt[2], 1) * 1e3))
     names = GEN_PHASES if do_reset else PHASES
     for pid, nm in names.items():
         if pid in sums:
