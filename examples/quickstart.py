@@ -90,3 +90,10 @@ obs = venv.reset_envs(mask=venv.status[:, 0] >= 2)
 obs = venv.reset_envs(env_ids=[17, 4011], seeds=[7, 8])   # ... or by index, on seeds of your choice
 print("HipVecRogueEnv.reset_envs: envs 17 and 4011 restarted on level %s" % venv.status[[17, 4011], 0].tolist())
 venv.close()
+
+# 3e. the full map plus an egocentric 11x11 window of symbol ids beside it (NLE's chars_crop: 121 bytes per env), both refreshed by every step ----------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0)
+view = venv.add_crop(5, image_setting=ImageSetting(DungeonType.SYMBOL, StatusFlag.EMPTY, False), symbol_ids=True)
+obs, reward, done = venv.step(actions[0, :4096])
+print("HipVecRogueEnv.add_crop: obs %s %s beside a view %s %s centred on %s" % (tuple(obs.shape), obs.dtype, tuple(view.obs.shape), view.obs.dtype, view.center[0].tolist()))
+venv.close()

@@ -185,7 +185,7 @@ int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_f
  * and there are NO fallback kernels for other grids); handles with config groups or mixed sizes (as rg_obs_bind).  A refused call launches nothing.
  * rg_step_obs_typed = rg_step + rg_obs_typed in one trip through the binding (what rg_step_obs_gray is for f32); a refused call does not step.
  * rg_obs_dtype_bytes: the element size, 4 / 2 / 2 / 1, or -1 for anything else; stateless, needs no device.
- * Not typed (f32 only): the crop (rg_obs_crop), the bound tensor (rg_obs_bind), rg_expand_compact, rg_obs_host, rg_encode_host[_batch]. */
+ * The typed crop is rg_obs_crop_typed below.  Not typed (f32 only): the bound tensor (rg_obs_bind), rg_expand_compact, rg_obs_host, rg_encode_host[_batch]. */
 #define RG_OBS_F32  0
 #define RG_OBS_F16  1   /* IEEE binary16 */
 #define RG_OBS_BF16 2
@@ -193,6 +193,25 @@ int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_f
 int rg_obs_dtype_bytes(int dtype);
 int rg_obs_typed(rg_t *h, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev);
 int rg_step_obs_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev);
+
+/* TYPED player-centred crop: the window of rg_obs_crop in the element types of rg_obs_typed, and NLE's `chars_crop` -- the window as symbol ids.
+ *   kind 0 / 1, dtype RG_OBS_F16 / RG_OBS_BF16: out_dev = T [n_env][C][2*radius_y+1][2*radius_x+1], every element the one rg_obs_crop would write,
+ *     rounded to nearest even (F16 overflows to infinity): bit-identical to f32_crop.to(T).  dtype RG_OBS_F32 is exactly the rg_obs_crop call.
+ *   kind 2, dtype RG_OBS_U8 only: out_dev = u8 [n_env][1 + with_hist][2*radius_y+1][2*radius_x+1].  Plane 0 is Symbol::from_tile of each window cell on
+ *     the screen (255 for a glyph without a symbol) and 0, the id of ' ', outside it; the history plane is 0 / 1, and 0 outside the screen.  status_flag
+ *     must be 0.  An 11 x 11 window is 121 bytes per env.
+ * centers_dev (nullable) as rg_obs_crop.  InvalidTileError by rg_obs_crop's rule -- raised at the next rg_sync, only for a cell inside the window; kind 2:
+ * an id >= symbols - 1, the byte written is still the id.  Handles with config groups and mixed-size batches are served for every kind: kind 1 refuses a
+ * group with more symbols than env 0's, as rg_obs_crop does; kind 2 has no channel count and judges each env by its own group's `symbols`.  There is no
+ * condition on H*W (the crop stages cells).  Side effects are those of rg_obs_crop: pending Redraws are drawn first, history stale / lag rules unchanged,
+ * a bound tensor is re-encoded in full by its next call -- a handle that makes only these calls has the same mirrors and flag words, step for step, as
+ * one that makes only rg_obs_crop calls.
+ * Refused, non-zero with a message naming the entry point and the argument, nothing launched: an unknown kind or dtype; kind 2 with another dtype;
+ * RG_OBS_U8 with kinds 0 / 1; status planes with kind 2; radii outside rg_obs_crop's range; out_dev null or not 16-byte aligned.
+ * rg_step_obs_crop_typed = rg_step + rg_obs_crop_typed in one trip through the binding; a refused call does not step. */
+int rg_obs_crop_typed(rg_t *h, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev);
+int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist,
+                           void *out_dev, int32_t *centers_dev);
 
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);

@@ -54,6 +54,8 @@ int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint
                   hipEvent_t ev1);
 int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
                  uint32_t *err_any, hipStream_t st);
+int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, void *out, int32_t *centers,
+                   uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -920,6 +922,54 @@ int rg_obs_typed(rg_t *h, int kind, int dtype, uint32_t status_flag, int with_hi
 int rg_step_obs_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, uint32_t status_flag, int with_hist, void *out_dev) {
     if (typed_check(h, "rg_step_obs_typed", kind, dtype, status_flag, out_dev)) return 1;
     return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : obs_typed_checked(h, kind, dtype, status_flag, with_hist, out_dev);
+}
+// The typed crop (rg_crop_typed.hip).  crop_typed_check: every refusal, before anything is launched (or stepped).
+static int crop_typed_check(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, const void *out_dev) {
+    const std::string w = std::string(what) + ": ";
+    if (kind < 0 || kind > 2) { h->err = w + "kind must be 0 (gray), 1 (symbol) or 2 (symbol ids), got " + std::to_string(kind); return 1; }
+    if (rg_obs_dtype_bytes(dtype) < 0) { h->err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1), RG_OBS_BF16 (2) or RG_OBS_U8 (3), got " + std::to_string(dtype); return 1; }
+    if (kind == 2 && dtype != RG_OBS_U8) { h->err = w + "kind 2 (symbol ids) takes dtype RG_OBS_U8 only, got dtype " + std::to_string(dtype); return 1; }
+    if (kind != 2 && dtype == RG_OBS_U8) { h->err = w + "dtype RG_OBS_U8 is for kind 2 (symbol ids) only, got kind " + std::to_string(kind); return 1; }
+    if (kind == 2 && (status_flag & 0x1ffu)) { h->err = w + "status_flag must be 0 for kind 2 (status values do not fit a byte; read the status mirror)"; return 1; }
+    if (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1) {
+        h->err = w + "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) + ", got (" +
+                 std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
+        return 1;
+    }
+    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    if (kind == 1)  // (kind 2 has no channel count: each env is judged by its own group's symbols)
+        for (rg_handle *sh : h->sub)
+            if (sh->cfg.symbols > h->planes_sym) {
+                h->err = w + "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
+                         "), which sets the channel count (python/src/lib.rs:281-285)";
+                return 1;
+            }
+    return 0;
+}
+static int crop_typed_checked(rg_t *h, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
+    if (dtype == RG_OBS_F32) return rg_obs_crop(h, kind, radius_y, radius_x, status_flag, with_hist, static_cast<float *>(out_dev), centers_dev);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group crops its envs straight into the handle's tensor (RgState::ext), as rg_obs_crop
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, crop_typed_checked(sh, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev));
+        return 0;
+    }
+    if (flush_render(h)) return 1;  // (rg_obs_crop's rule: pending Redraws drawn by k_render, a bound observation tensor re-encoded in full by its next call)
+    if (!rgk_crop_typed(&h->S, &h->cfg, kind, dtype, radius_y, radius_x, status_flag & 0x1ffu, with_hist ? 1 : 0, h->planes_sym, out_dev, centers_dev, h->d_err, h->stream,
+                        nullptr, nullptr)) {
+        h->err = "rg_obs_crop_typed: window too large";
+        return 1;
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_obs_crop_typed(rg_t *h, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
+    if (crop_typed_check(h, "rg_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
+    return crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
+}
+int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist,
+                           void *out_dev, int32_t *centers_dev) {
+    if (crop_typed_check(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
+    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }

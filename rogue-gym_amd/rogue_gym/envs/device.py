@@ -23,6 +23,15 @@ class _DevArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
+class CropView:
+    """A player-centred window kept beside an env's main observation (HipVecRogueEnv.add_crop): `obs` [N, C, 2ry+1, 2rx+1] in the view's element
+    type and `center` i32 [N, 2], the (y, x) of each window's centre.  Both are rewritten in place whenever the env refreshes its own `obs`."""
+
+    def __init__(self, crop, image_setting, call, obs, center):
+        self.crop, self.image_setting, self.obs, self.center = crop, image_setting, obs, center
+        self._call = call  # (kind, RG_OBS_* dtype) of rg_obs_crop_typed
+
+
 class HipVecRogueEnv:
     ACTIONS = RogueEnv.ACTIONS
 
@@ -43,7 +52,7 @@ class HipVecRogueEnv:
         symbol_ids (needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype None): `self.obs` is uint8 [N, 1 + hist, H, W] -- plane 0 holds each cell's symbol
         id (the one-hot image's argmax(1); ' ' is 0), what an embedding layer indexes with -- instead of the one-hot image.
 
-        Neither with crop or persistent_obs (those are f32 only)."""
+        Neither with crop or persistent_obs (those are f32 only); a typed window BESIDE `obs` is a crop view: add_crop()."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -60,15 +69,9 @@ class HipVecRogueEnv:
         if crop is not None:
             if persistent_obs:
                 raise ValueError("crop and persistent_obs cannot be combined: the bound observation tensor is the whole screen")
-            try:
-                ry, rx = (crop, crop) if not isinstance(crop, (tuple, list)) else crop
-                ry, rx = operator.index(ry), operator.index(rx)
-            except (TypeError, ValueError):
-                ry = rx = -1
-            if ry < 0 or rx < 0:
-                raise ValueError("crop must be None, an int >= 0 or a pair (ry, rx) of ints >= 0, got %r" % (crop,))
-            crop = (ry, rx)
+            crop = self._crop_radii(crop)
         self.crop = crop
+        self._views = []
 
         self.torch = torch
         cfgs = [d if isinstance(d, str) else json.dumps(d) for d in config_dicts]
@@ -110,6 +113,67 @@ class HipVecRogueEnv:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         self._encode()
 
+    @staticmethod
+    def _crop_radii(crop):
+        try:
+            ry, rx = (crop, crop) if not isinstance(crop, (tuple, list)) else crop
+            ry, rx = operator.index(ry), operator.index(rx)
+        except (TypeError, ValueError):
+            ry = rx = -1
+        if ry < 0 or rx < 0:
+            raise ValueError("crop must be None, an int >= 0 or a pair (ry, rx) of ints >= 0, got %r" % (crop,))
+        return ry, rx
+
+    def add_crop(self, crop, image_setting: Optional[ImageSetting] = None, obs_dtype=None, symbol_ids: bool = False):
+        """Add a crop VIEW: a player-centred window (r or (ry, rx), as the constructor's `crop`) kept beside `self.obs`, for models that read the full map
+        and an egocentric crop in the same step.  Returns an object with `.obs` [N, C, 2ry+1, 2rx+1] and `.center` i32 [N, 2]; `self.crops` is the
+        tuple of the views added so far.  image_setting defaults to the env's.  obs_dtype (None, torch.float32, torch.float16 or torch.bfloat16) is the
+        view's element type; symbol_ids=True (needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype None, as in the constructor) makes it the uint8
+        window of symbol ids [N, 1 + hist, 2ry+1, 2rx+1] -- NLE's `chars_crop`, 121 bytes per env at 11 x 11 (rg_obs_crop_typed).  The view is encoded
+        now, and again after `obs` by everything that refreshes `obs`: reset, reset_envs, step_keys / step, load_state and clone_state.  It works on
+        every env this class builds -- typed, bound (persistent_obs), cropped, config groups, mixed sizes -- and leaves `obs` as it is without views.
+        A learner that wants only the small window: HipVecRogueEnv(cfgs, crop=0) plus add_crop(4, ImageSetting(DungeonType.SYMBOL, ...), symbol_ids=True)."""
+        torch = self.torch
+        if crop is None:
+            raise ValueError("crop must be an int >= 0 or a pair (ry, rx) of ints >= 0, got None")
+        ry, rx = self._crop_radii(crop)
+        st = self.image_setting if image_setting is None else image_setting
+        if not isinstance(st, ImageSetting):
+            raise ValueError("image_setting must be an ImageSetting or None, got %r" % (image_setting,))
+        if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("obs_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (obs_dtype,))
+        sym = st.dungeon == DungeonType.SYMBOL
+        if symbol_ids:
+            if not sym or st.status.value != 0 or obs_dtype is not None:
+                raise ValueError("symbol_ids=True needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype=None (the ids are uint8), got %s, status %r, obs_dtype %r"
+                                 % (st.dungeon, st.status, obs_dtype))
+            call, channels, dtype = (2, 3), 1 + int(st.includes_hist), torch.uint8
+        else:
+            call = (int(sym), 1 if obs_dtype == torch.float16 else 2 if obs_dtype == torch.bfloat16 else 0)
+            channels = self._h.L.rg_obs_channels(self._h.h, int(sym), st.status.value, int(st.includes_hist))
+            dtype = torch.float32 if obs_dtype is None else obs_dtype
+        with torch.cuda.device(self.device):
+            view = CropView((ry, rx), st, call, torch.empty((self.num_envs, channels, 2 * ry + 1, 2 * rx + 1), dtype=dtype, device=self.device),
+                            torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device))
+        self._encode_view(view)  # (a refused setting -- a config group with more symbols than env 0's under the one-hot kind -- raises here, before the view is kept)
+        self._views.append(view)
+        return view
+
+    @property
+    def crops(self):
+        """The crop views added so far (add_crop), in order."""
+        return tuple(self._views)
+
+    def _encode_view(self, v):
+        st = v.image_setting
+        self._h.check(self._h.L.rg_obs_crop_typed(self._h.h, v._call[0], v._call[1], v.crop[0], v.crop[1], st.status.value, int(st.includes_hist),
+                                                  C.c_void_p(v.obs.data_ptr()), C.c_void_p(v.center.data_ptr())))
+
+    def _refresh_views(self):
+        """After `obs` was refreshed: nothing is pending then, so the crop passes only read the mirrors (and a bound `obs` stays valid)."""
+        for v in self._views:
+            self._encode_view(v)
+
     @property
     def screen(self):
         """u8 [num_envs, H, W] glyph mirror (PlayerState.map of every env).  Reading it flushes the pending render (a batch with several
@@ -124,6 +188,12 @@ class HipVecRogueEnv:
         return self._screen
 
     def _encode(self):
+        """Re-encode `obs`, then the crop views."""
+        obs = self._encode_obs()
+        self._refresh_views()
+        return obs
+
+    def _encode_obs(self):
         L, h = self._h.L, self._h.h
         if self.crop is not None:
             self._h.check(L.rg_obs_crop(h, int(self._sym), self.crop[0], self.crop[1], self.image_setting.status.value, int(self.image_setting.includes_hist),
@@ -186,6 +256,12 @@ class HipVecRogueEnv:
 
     def step_keys(self, keys):
         """keys: uint8 CUDA tensor [num_envs] of key bytes (KeyMap::ai), contiguous, on this env's device."""
+        out = self._step_keys(keys)
+        self._refresh_views()
+        return out
+
+    def _step_keys(self, keys):
+        """The step and the refresh of `obs`, without the crop views."""
         if keys.dtype != self.torch.uint8 or keys.device != self.device or not keys.is_contiguous() or keys.numel() != self.num_envs:
             raise ValueError("step_keys needs a contiguous uint8 tensor of %d keys on %s, got %s %s on %s"
                              % (self.num_envs, self.device, tuple(keys.shape), keys.dtype, keys.device))
@@ -195,7 +271,7 @@ class HipVecRogueEnv:
             obs = self.obs
         elif self._sym or self.crop is not None:
             self._h.check(self._h.L.rg_step(self._h.h, C.c_void_p(keys.data_ptr()), 1))
-            obs = self._encode()
+            obs = self._encode_obs()
         else:  # the step and the gray observation as one call: fused into one kernel where the config allows it (rg_step_obs_gray)
             self._h.check(self._h.L.rg_step_obs_gray(self._h.h, C.c_void_p(keys.data_ptr()), 1, self.image_setting.status.value, int(self.image_setting.includes_hist),
                                                       C.c_void_p(self.obs.data_ptr())))
@@ -437,7 +513,7 @@ class HipVecFirstFloor(HipVecStairReward):
     rewritten by the rebuild (reward 0, done 0)."""
 
     def step_keys(self, keys):
-        _, reward, done = super().step_keys(keys)
+        _, reward, done = self._step_keys(keys)  # (the crop views are encoded once, after the rebuild)
         reached = (self.status[:, 0] >= 2) & ~done
         reward = reward.clone()
         done = done | reached

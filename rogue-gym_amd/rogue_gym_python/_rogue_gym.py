@@ -46,6 +46,7 @@ _INT_FUNCS = (
     "rg_host_alloc", "rg_dev_alloc", "rg_snapshot_take", "rg_dev_read", "rg_dev_read_rows", "rg_compact_record_bytes", "rg_pack_compact", "rg_expand_compact", "rg_comm_unique_id", "rg_comm_init", "rg_comm_destroy", "rg_comm_count", "rg_allgather_compact", "rg_status_vec", "rg_history_enable", "rg_history_keys",
     "rg_dump_history", "rg_counters", "rg_counters_ex", "rg_probe_sclk", "rg_dump_config", "rg_config_canonical", "rg_config_resolved", "rg_config_schema", "rg_debug_fetch", "rg_debug_descend", "rg_timing_enable", "rg_timing_read", "rg_timing_read_all", "rg_timing_read_samples",
     "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed", "rg_step_obs_typed",
+    "rg_obs_crop_typed", "rg_step_obs_crop_typed",
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode",
 )
 
@@ -107,13 +108,14 @@ def load_library():
         "rg_state_record_bytes": [vp], "rg_state_save": [vp, vp, i32, i32, vp], "rg_state_load": [vp, vp, sz, vp, i32, i32],
         "rg_obs_crop": [vp, i32, i32, i32, u32, i32, vp, vp],
         "rg_obs_dtype_bytes": [i32], "rg_obs_typed": [vp, i32, i32, u32, i32, vp], "rg_step_obs_typed": [vp, vp, i32, i32, i32, u32, i32, vp],
+        "rg_obs_crop_typed": [vp, i32, i32, i32, i32, u32, i32, vp, vp], "rg_step_obs_crop_typed": [vp, vp, i32, i32, i32, i32, i32, u32, i32, vp, vp],
         "rg_reset_envs": [vp, vp, i32, i32], "rg_reset_mask": [vp, vp], "rg_seed_envs": [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i32],
         "rg_tail_encode": [vp, i32],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
-                "rg_step_obs_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
