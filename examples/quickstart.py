@@ -33,6 +33,7 @@ for key in "hjklyubn>s" * 3:
         state = env.reset()
 print("RogueEnv: obs", env.image_setting.expand(state).shape, "gold so far", total)
 print(env)                                           # the screen, like the reference's __repr__
+print("RogueEnv.action_mask: keys that would do something now:", "".join(k for k, ok in zip(env.ACTIONS, env.action_mask()) if ok))
 
 # 2. many games, value objects -------------------------------------------------------------------------------------------------------------
 n = 1024
@@ -96,4 +97,15 @@ venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=I
 view = venv.add_crop(5, image_setting=ImageSetting(DungeonType.SYMBOL, StatusFlag.EMPTY, False), symbol_ids=True)
 obs, reward, done = venv.step(actions[0, :4096])
 print("HipVecRogueEnv.add_crop: obs %s %s beside a view %s %s centred on %s" % (tuple(obs.shape), obs.dtype, tuple(view.obs.shape), view.obs.dtype, view.center[0].tolist()))
+venv.close()
+
+# 3f. a masked random rollout: every env plays a key drawn among the keys that do something for it now (the engine's own move test, on the device:
+#     no "can't move" turns), and `action_mask` is the bool [N, 11] tensor a masked policy would consume ------------------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, action_mask=True)
+gold = torch.zeros(4096, device=venv.device)
+for t in range(200):
+    obs, reward, done = venv.step_keys(venv.sample_keys())
+    gold += reward
+print("HipVecRogueEnv(action_mask=True): mask %s %s, %.1f legal keys per env, %.0f gold per env in 200 masked random steps"
+      % (tuple(venv.action_mask.shape), venv.action_mask.dtype, venv.action_mask.sum(1).float().mean().item(), gold.mean().item()))
 venv.close()

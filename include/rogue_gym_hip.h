@@ -213,6 +213,39 @@ int rg_obs_crop_typed(rg_t *h, int kind, int dtype, int radius_y, int radius_x, 
 int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist,
                            void *out_dev, int32_t *centers_dev);
 
+/* LEGAL-ACTION MASKS: which keys would do anything for each env right now, and one key per env drawn uniformly among those, on the device.
+ * The rule is the reference's own test, which neither its Python surface nor the screen mirror gives away: Dungeon::can_move_player
+ * (core/src/dungeon/mod.rs:79) -> Floor::can_move_impl as the player (floor.rs:169-182), which move_player asks before anything else (actions.rs:168-231).
+ *   '.' and 's': 1.
+ *   h j k l y u b n (KeyMap::ai, input.rs:73-100: j is down, k is up) and the run keys H J K L Y U B N, judged by their first move: 1 iff the target cell is
+ *     inside the grid, its surface can be walked on (not wall-x, wall-y or none), its attr has neither HIDDEN nor LOCKED, and -- for a diagonal -- both
+ *     orthogonal neighbours (x+dx, y) and (x, y+dy) are inside the grid and walkable (surface only: their HIDDEN / LOCKED bits are not consulted, as in the
+ *     reference).  A monster on the target changes nothing: the move is an attack and is legal.
+ *   '>': 1 iff the surface of the player's own cell is the stairs (actions.rs:16-65).
+ *   An env in the Grave modal (RG_FLAG_DEAD; handles without auto-reset only): every key 0 -- the reference answers every key, '.' included, with IgnoredInput.
+ * So 0 means exactly: the reference would answer the key with CantMove, with "no downstairs" or with IgnoredInput.
+ * rg_action_mask: `keys` = host list of n_keys key bytes, duplicates allowed; NULL = the 11 of RG_ACTION_KEYS (n_keys is then ignored).  mask_dev (nullable)
+ *   = u8 [n_env][n_keys], 0 / 1, in the handle's env order.  sample_dev (nullable) = u8 [n_env]: for env e with `count` legal keys the key at the position of
+ *   the (rg_sample_index(seed, e, draw, count) + 1)-th set entry of its row, keys[0] when count == 0 -- a key byte for rg_step.  The call is stateless: the
+ *   caller varies `draw` (a step counter) between calls, and the same arguments on the same states give the same bytes.  Asynchronous on the handle's stream.
+ *   It reads game state only (the player's cell, the flag word, the cell grid): the pending render is not flushed, the mirrors, every flag bit and a bound
+ *   observation tensor are left alone.  Config groups and mixed-size batches are served (a row has one size for every env; each group writes its envs' rows).
+ *   Refused, non-zero with a message naming the argument, nothing launched: n_keys < 1 or > RG_MASK_MAX_KEYS; a key outside KeyMap::ai (the message names
+ *   the byte and its position); both outputs NULL; mask_dev not 16-byte aligned.
+ * rg_sample_index (stateless, needs no device), all arithmetic mod 2^64:
+ *     z = seed + 0x9E3779B97F4A7C15 * (env + 1) + 0xD1B54A32D192ED03 * draw
+ *     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *     return count ? (uint32_t)(((z >> 32) * count) >> 32) : 0
+ * rg_action_mask_host (stateless, needs no device): the same rule for ONE env given as a host grid `cells` = u16 [height][width] in rg_debug_fetch's layout,
+ *   the player's cell (px, py) and the dead bit; out = u8 [n_keys].  Key rules and refusals as rg_action_mask; the message is read through
+ *   rg_last_error(NULL). */
+#define RG_ACTION_KEYS ".hjklnbuy>s"   /* RogueEnv.ACTIONS in index order */
+#define RG_MASK_MAX_KEYS 32
+int rg_action_mask(rg_t *h, const uint8_t *keys, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw);
+int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, int py, int dead,
+                        const uint8_t *keys, int n_keys, uint8_t *out);
+uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

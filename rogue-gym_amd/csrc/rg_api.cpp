@@ -15,6 +15,7 @@
 #include "../../include/rogue_gym_hip.h"
 #include "rg_state.h"
 #include "rg_state_io.h"
+#include "rg_action_mask.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -56,6 +57,8 @@ int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, 
                  uint32_t *err_any, hipStream_t st);
 int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, void *out, int32_t *centers,
                    uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
+                     hipEvent_t ev0, hipEvent_t ev1);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -971,6 +974,55 @@ int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int
     if (crop_typed_check(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
     return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
 }
+// Legal-action masks (rg_action_mask.hip; the rule: rg_action_mask.h).  mask_keys_check: the key list of a call, every refusal before anything is launched;
+// on success `list` holds the n_keys keys the call judges.
+static int mask_keys_check(std::string &err, const char *what, const uint8_t *keys, int &n_keys, uint8_t list[RG_MASK_MAX_KEYS]) {
+    const std::string w = std::string(what) + ": ";
+    if (!keys) { keys = reinterpret_cast<const uint8_t *>(RG_ACTION_KEYS); n_keys = (int)(sizeof(RG_ACTION_KEYS) - 1); }
+    if (n_keys < 1 || n_keys > RG_MASK_MAX_KEYS) { err = w + "n_keys must satisfy 1 <= n_keys <= " + std::to_string(RG_MASK_MAX_KEYS) + ", got " + std::to_string(n_keys); return 1; }
+    for (int k = 0; k < n_keys; k++) {
+        if (rg_key_bit(keys[k]) == RG_LB_NONE) {
+            char hex[8];
+            snprintf(hex, sizeof hex, "0x%02x", keys[k]);
+            err = w + "keys[" + std::to_string(k) + "] = " + hex + (keys[k] >= 0x20 && keys[k] < 0x7f ? " ('" + std::string(1, (char)keys[k]) + "')" : std::string()) +
+                  " is not a key of KeyMap::ai (input.rs:73-100)";
+            return 1;
+        }
+        list[k] = keys[k];
+    }
+    return 0;
+}
+static int action_mask_checked(rg_t *h, const uint8_t *list, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, action_mask_checked(sh, list, n_keys, mask_dev, sample_dev, seed, draw));
+        return 0;
+    }
+    // game state only: the pending render is not flushed, mirrors, flag words and a bound observation tensor stay as they are
+    rgk_action_mask(&h->S, &h->cfg, list, n_keys, mask_dev, sample_dev, seed, draw, h->stream, nullptr, nullptr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_action_mask(rg_t *h, const uint8_t *keys, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
+    uint8_t list[RG_MASK_MAX_KEYS];
+    if (mask_keys_check(h->err, "rg_action_mask", keys, n_keys, list)) return 1;
+    if (!mask_dev && !sample_dev) { h->err = "rg_action_mask: mask_dev and sample_dev are both NULL"; return 1; }
+    if ((uintptr_t)mask_dev & 15) { h->err = "rg_action_mask: mask_dev must be a 16-byte aligned device pointer"; return 1; }
+    return action_mask_checked(h, list, n_keys, mask_dev, sample_dev, seed, draw);
+}
+int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys, uint8_t *out) {
+    uint8_t list[RG_MASK_MAX_KEYS];
+    if (mask_keys_check(g_create_err, "rg_action_mask_host", keys, n_keys, list)) return 1;
+    if (!cells || !out) { g_create_err = "rg_action_mask_host: cells and out must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || px < 0 || py < 0 || px >= width || py >= height) {
+        g_create_err = "rg_action_mask_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+                       std::to_string(height) + " grid";
+        return 1;
+    }
+    for (int k = 0; k < n_keys; k++) out[k] = (uint8_t)rg_key_legal(cells, height, width, px, py, dead, list[k]);
+    return 0;
+}
+uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count) { return rg_sample_index_of(seed, env, draw, count); }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }
 

@@ -37,7 +37,7 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False):
+                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -52,7 +52,12 @@ class HipVecRogueEnv:
         symbol_ids (needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype None): `self.obs` is uint8 [N, 1 + hist, H, W] -- plane 0 holds each cell's symbol
         id (the one-hot image's argmax(1); ' ' is 0), what an embedding layer indexes with -- instead of the one-hot image.
 
-        Neither with crop or persistent_obs (those are f32 only); a typed window BESIDE `obs` is a crop view: add_crop()."""
+        Neither with crop or persistent_obs (those are f32 only); a typed window BESIDE `obs` is a crop view: add_crop().
+
+        action_mask (opt-in): `self.action_mask` is a bool tensor [N, len(ACTIONS)] on the device -- entry [i, a] says whether ACTIONS[a] would do anything
+        for env i now (rg_action_mask: the engine's own move test; False = "can't move", "no downstairs") -- rewritten in place by everything that
+        refreshes `obs`.  One small launch more per step, no host trip; it works on every env this class builds.  False: `self.action_mask` is None and
+        nothing is added to any call.  legal_mask() and sample_keys() work either way."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -108,6 +113,9 @@ class HipVecRogueEnv:
             if crop is None:  # (with a crop the batch may mix screen sizes: no screen tensor then, `screen` raises)
                 self._screen_view()
         self._scratch = {}
+        self._draw = 0  # sample_keys: the draw counter of calls that give none
+        self._mask_u8 = torch.zeros((self.num_envs, len(self.ACTIONS)), dtype=torch.uint8, device=self.device) if action_mask else None
+        self.action_mask = None if self._mask_u8 is None else self._mask_u8.view(torch.bool)
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
@@ -173,6 +181,41 @@ class HipVecRogueEnv:
         """After `obs` was refreshed: nothing is pending then, so the crop passes only read the mirrors (and a bound `obs` stays valid)."""
         for v in self._views:
             self._encode_view(v)
+        if self._mask_u8 is not None:
+            self._h.check(self._h.L.rg_action_mask(self._h.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0))
+
+    def _mask_call(self, keys, mask, sample, seed, draw):
+        kb, nk = inner._mask_keys(keys)
+        self._h.check(self._h.L.rg_action_mask(self._h.h, kb, nk, None if mask is None else C.c_void_p(mask.data_ptr()),
+                                               None if sample is None else C.c_void_p(sample.data_ptr()), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF))
+
+    def legal_mask(self, keys=None, out=None):
+        """bool [N, n_keys] on the device: entry [i, k] says whether keys[k] would do anything for env i now (rg_action_mask).  keys: bytes / str of keys of
+        KeyMap::ai, run keys included, checked by the library; None = ACTIONS in index order.  out (optional): a contiguous uint8 / bool tensor
+        [N, n_keys] on this env's device to write into.  No host trip; the states, mirrors and `obs` are left as they are."""
+        torch = self.torch
+        nk = inner._mask_keys(keys)[1]
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty((self.num_envs, nk), dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype not in (torch.uint8, torch.bool) or out.device != self.device or tuple(out.shape) != (self.num_envs, nk)
+              or not out.is_contiguous()):
+            raise ValueError("legal_mask: out must be a contiguous uint8 / bool tensor [%d, %d] on %s" % (self.num_envs, nk, self.device))
+        self._mask_call(keys, out, None, 0, 0)
+        return out if out.dtype == torch.bool else out.view(torch.bool)
+
+    def sample_keys(self, seed=0, draw=None, keys=None):
+        """uint8 [N] on the device: for each env one key byte of `keys` (None = ACTIONS) drawn uniformly among the keys that would do anything for it now --
+        what step_keys takes -- from the launch that computes the mask.  The draw is a stateless function of (seed, env index, draw) (rg_sample_index):
+        draw=None uses a counter kept by this env that advances by one per call; the same (seed, draw) on the same states gives the same keys.  With
+        action_mask=True and keys=None the call also rewrites `self.action_mask`, which it equals anyway."""
+        torch = self.torch
+        if draw is None:
+            draw, self._draw = self._draw, self._draw + 1
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
+        self._mask_call(keys, self._mask_u8 if keys is None else None, out, seed, draw)
+        return out
 
     @property
     def screen(self):

@@ -68,6 +68,10 @@ class ParallelRogueEnv:
         """[N, C, H, W] float32 image of every env under `image_setting` (default: the states of the last step)."""
         return self.image_setting.expand_batch(self.states if states is None else states)
 
+    def action_masks(self) -> np.ndarray:
+        """bool [N, ACTION_LEN]: entry [i, a] says whether ACTIONS[a] would do anything for env i now (RogueEnv.action_mask for the whole batch)."""
+        return self.game.action_masks()
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
         return batch

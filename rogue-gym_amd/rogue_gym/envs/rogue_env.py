@@ -200,6 +200,12 @@ class RogueEnv(Env):
         state = self.result = self.game.prev()
         return state
 
+    def action_mask(self) -> np.ndarray:
+        """bool [ACTION_LEN]: entry i says whether ACTIONS[i] would do anything now.  False = the game would answer the key with "can't move", with
+        "no downstairs", or -- after death -- ignore it.  The rule is the engine's own move test (walls, hidden and locked cells, the corner-cutting rule
+        for diagonals, the surface under the player for '>'), which the screen does not show completely."""
+        return self.game.action_mask()
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

@@ -47,7 +47,7 @@ _INT_FUNCS = (
     "rg_dump_history", "rg_counters", "rg_counters_ex", "rg_probe_sclk", "rg_dump_config", "rg_config_canonical", "rg_config_resolved", "rg_config_schema", "rg_debug_fetch", "rg_debug_descend", "rg_timing_enable", "rg_timing_read", "rg_timing_read_all", "rg_timing_read_samples",
     "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed", "rg_step_obs_typed",
     "rg_obs_crop_typed", "rg_step_obs_crop_typed",
-    "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode",
+    "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
 )
 
 
@@ -111,11 +111,14 @@ def load_library():
         "rg_obs_crop_typed": [vp, i32, i32, i32, i32, u32, i32, vp, vp], "rg_step_obs_crop_typed": [vp, vp, i32, i32, i32, i32, i32, u32, i32, vp, vp],
         "rg_reset_envs": [vp, vp, i32, i32], "rg_reset_mask": [vp, vp], "rg_seed_envs": [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i32],
         "rg_tail_encode": [vp, i32],
+        "rg_action_mask": [vp, vp, i32, vp, vp, C.c_uint64, C.c_uint64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
+        "rg_sample_index": [C.c_uint64, u32, C.c_uint64, u32],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
-                "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
+                "rg_sample_index"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -126,6 +129,8 @@ def load_library():
     L.rg_last_error.restype = C.c_char_p
     L.rg_build_id.restype = C.c_char_p
     L.rg_build_id.argtypes = []
+    if hasattr(L, "rg_sample_index"):
+        L.rg_sample_index.restype = C.c_uint32
     for name in _INT_FUNCS:
         if name in optional and not hasattr(L, name):
             continue
@@ -251,6 +256,21 @@ def _leased_many(pool, specs):
     return out
 
 
+N_ACTION_KEYS = 11  # RG_ACTION_KEYS
+
+
+def _mask_keys(keys):
+    """(pointer argument, n_keys) of a key list for rg_action_mask: None = the library's default list; bytes / str are passed on as they are (the
+    library checks them)."""
+    if keys is None:
+        return None, N_ACTION_KEYS
+    if isinstance(keys, str):
+        keys = keys.encode("latin-1")
+    if not isinstance(keys, (bytes, bytearray)):
+        raise TypeError("keys must be bytes, str or None, got %s" % type(keys).__name__)
+    return bytes(keys), len(keys)
+
+
 class _Handle:
     """Owns one rg_t."""
 
@@ -288,6 +308,7 @@ class _Handle:
         self.lazy = {}  # id -> weakref of the StateBatches whose screens still live only in their device snapshot (materialised before the handle goes)
         self.epoch = 0  # bumped by every call that changes the device-side states (a StateBatch remembers the epoch it was taken at)
         self.fast_step = True  # rg_step_fetch applies (cleared by the first refusal: a handle with config groups)
+        self._mask_dev = None  # action_mask: its device scratch (address, bytes), kept between calls
 
     def check(self, rc):
         if rc:
@@ -299,6 +320,9 @@ class _Handle:
                 b = ref()
                 if b is not None:
                     b._materialise()
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
             self.L.rg_destroy(self.h)
             self.h = None
             self.pool.close()
@@ -338,6 +362,24 @@ class _Handle:
         cells = np.empty((self.height, self.width), np.uint16)
         self.check(self.L.rg_debug_fetch(self.h, env, C.byref(out), cells.ctypes.data))
         return out, cells
+
+    def action_mask(self, keys=None):
+        """bool [n, n_keys]: which of `keys` (bytes / str; None = RG_ACTION_KEYS, RogueEnv.ACTIONS in index order) would do anything for each env now
+        (rg_action_mask into a device scratch buffer the handle keeps, one rg_dev_read)."""
+        kb, nk = _mask_keys(keys)
+        nbytes = self.n * nk
+        if self._mask_dev is None or self._mask_dev[1] < nbytes:
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._mask_dev = (p.value, nbytes)
+        self.check(self.L.rg_action_mask(self.h, kb, nk, C.c_void_p(self._mask_dev[0]), None, 0, 0))
+        out = np.empty((self.n, nk), np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(self._mask_dev[0]), out.ctypes.data, nbytes))
+        return out.view(np.bool_)
 
     def history_keys(self, env, previous=False):
         n = C.c_uint32()
@@ -734,6 +776,10 @@ class GameState:
     def dump_history(self):
         return self._h.dump_history(0)
 
+    def action_mask(self, keys=None):
+        """numpy bool [n_keys]: which keys would do anything now (not part of the reference's API; rg_action_mask)."""
+        return self._h.action_mask(keys)[0]
+
     def save_state(self):
         """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
         after a load_state dumps the saved episode's keys."""
@@ -793,6 +839,10 @@ class ParallelGameState:
         self._h.check(self._h.L.rg_reset(self._h.h))
         self._h.epoch += 1
         return self._h.snapshot()
+
+    def action_masks(self, keys=None):
+        """numpy bool [n, n_keys]: which keys would do anything for each env now (not part of the reference's API; rg_action_mask)."""
+        return self._h.action_mask(keys)
 
     def dump_config(self, env=0):
         buf = C.create_string_buffer(1 << 16)
