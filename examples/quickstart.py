@@ -109,3 +109,15 @@ for t in range(200):
 print("HipVecRogueEnv(action_mask=True): mask %s %s, %.1f legal keys per env, %.0f gold per env in 200 masked random steps"
       % (tuple(venv.action_mask.shape), venv.action_mask.dtype, venv.action_mask.sum(1).float().mean().item(), gold.mean().item()))
 venv.close()
+
+# 3g. a guided rollout: every env plays its teacher key -- one move closer to the stairs along the engine's own move graph, '>' on them, 's' (search) where
+#     no path is known to the engine yet.  PRIVILEGED: the guide sees stairs, gold and passages the player has not discovered -- a scripted expert for
+#     imitation data, or a shaping potential (guide_dist), not an observation -----------------------------------------------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, guide="stairs")
+start = venv.status[:, 0].clone()
+for t in range(200):
+    obs, reward, done = venv.step_keys(venv.guide_keys)
+print("HipVecRogueEnv(guide='stairs'): keys %s %s, dist %s %s; dungeon level %.2f -> %.2f per env in 200 guided steps, %.1f moves to the stairs now"
+      % (tuple(venv.guide_keys.shape), venv.guide_keys.dtype, tuple(venv.guide_dist.shape), venv.guide_dist.dtype, start.float().mean().item(),
+         venv.status[:, 0].float().mean().item(), venv.guide_dist[venv.guide_dist >= 0].float().mean().item()))
+venv.close()

@@ -246,6 +246,41 @@ int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, in
                         const uint8_t *keys, int n_keys, uint8_t *out);
 uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count);
 
+/* SHORTEST-PATH FIELDS AND TEACHER KEYS: for each env the number of moves from every cell to the nearest goal cell, that number at the player's cell, and the
+ * key that takes the player one move closer, on the device.  The moves are the engine's own: rg_action_mask's move test (Floor::can_move_impl as the player).
+ * The field is PRIVILEGED: it sees stairs, gold and passages the player has not discovered.  It is a teacher (imitation, DAgger), a shaping potential
+ * (distance to the stairs) or a critic input, not an observation the reference's player has.
+ *   Goals, the OR of: RG_GOAL_STAIRS every cell whose surface is the stairs; RG_GOAL_GOLD every cell that holds gold EXCEPT the player's own cell (gold is
+ *     taken by moving onto it, and the generator can put the player down on a gold cell); RG_GOAL_CELL one caller-given cell (y, x) per env -- a cell outside
+ *     the grid contributes nothing.
+ *   A cell is `ok` iff its surface can be walked on and its attr has neither HIDDEN nor LOCKED: what the move test demands of a target.
+ *   The field D = u16 [H][W]: 0 on every goal cell, whatever its own word.  For every other ok cell a, the least number of moves a -> ... -> goal, each move
+ *     legal from its source: the target inside the grid and ok; for a diagonal both orthogonal neighbours walkable by SURFACE only.  RG_PATH_UNREACHABLE
+ *     everywhere else: walls, bare cells, hidden / locked cells that are not goals, ok cells with no such path.  A goal cell that is not ok is not expanded
+ *     (nobody can step onto it).  Monsters are ignored: a move into one is an attack.
+ *   Distance i32: D at the player's cell, -1 for unreachable.
+ *   Teacher key u8, a key byte for rg_step: '.' for an env in the Grave modal (RG_FLAG_DEAD).  Else, D[player] == 0: '>' when the surface under the player is
+ *     the stairs and RG_GOAL_STAIRS is in the set, otherwise '.'.  Else, D[player] finite: the key of the FIRST direction in Direction-enum order (Up Down Left
+ *     Right LeftUp RightUp LeftDown RightDown = k j h l y u b n) whose move is legal and whose target has D[player] - 1; one always exists.  Else 's': Search
+ *     is what reveals hidden cells, and the caller mixes in exploration.
+ * rg_path: cells_dev = i32 [n_env][2] (y, x), read iff goals & RG_GOAL_CELL; field_dev (nullable) = u16 [n_env][H][W], 16-byte aligned; dist_dev (nullable)
+ *   = i32 [n_env]; key_dev (nullable) = u8 [n_env]; all in the handle's env order.  Without field_dev an env's search ends when it reaches the player's cell.
+ *   Asynchronous on the handle's stream.  It reads game state only (the player's cell, the flag word, the cell grid): the pending render is not flushed, the
+ *   mirrors, every flag bit, a bound observation tensor and the RNG streams are left alone.  Config groups and mixed-size batches are served for dist_dev /
+ *   key_dev / cells_dev; field_dev on such a handle is refused (there is no [n_env][H][W] tensor).  Refused, non-zero with a message naming the argument,
+ *   nothing launched: goals zero or with unknown bits; RG_GOAL_CELL without cells_dev; all outputs NULL; field_dev not 16-byte aligned.
+ * rg_path_host (stateless, needs no device): the same rule for ONE env given as a host grid `cells` = u16 [height][width] in rg_debug_fetch's layout, the
+ *   player's cell (px, py), the dead bit and the cell (cell_y, cell_x) of RG_GOAL_CELL; field_out = u16 [height][width], dist_out and key_out one value each,
+ *   any of them NULL but not all.  Refused, non-zero, nothing written, the message read through rg_last_error(NULL): goals as above; all outputs NULL;
+ *   cells NULL; the sizes or (px, py) out of range. */
+#define RG_GOAL_STAIRS 1u
+#define RG_GOAL_GOLD   2u
+#define RG_GOAL_CELL   4u
+#define RG_PATH_UNREACHABLE 0xFFFFu
+int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev);
+int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, int cell_y, int cell_x,
+                 uint16_t *field_out, int32_t *dist_out, uint8_t *key_out);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

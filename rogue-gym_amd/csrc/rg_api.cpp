@@ -16,6 +16,7 @@
 #include "rg_state.h"
 #include "rg_state_io.h"
 #include "rg_action_mask.h"
+#include "rg_path.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -59,6 +60,7 @@ int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int
                    uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
                      hipEvent_t ev0, hipEvent_t ev1);
+void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -1023,6 +1025,82 @@ int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, in
     return 0;
 }
 uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count) { return rg_sample_index_of(seed, env, draw, count); }
+// Shortest-path fields and teacher keys (rg_path.hip; the rule: rg_path.h).  path_goals_check: the goal set of a call, refused before anything is launched.
+static int path_goals_check(std::string &err, const char *what, uint32_t goals) {
+    if (goals == 0 || (goals & ~RG_PATH_GOALS_ALL)) {
+        err = std::string(what) + ": goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2) and RG_GOAL_CELL (4), got " + std::to_string(goals);
+        return 1;
+    }
+    return 0;
+}
+static int path_checked(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group writes its envs' entries straight into the handle's tensors (RgState::ext), as the masks do
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, path_checked(sh, goals, cells_dev, field_dev, dist_dev, key_dev));
+        return 0;
+    }
+    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
+    rgk_path(&h->S, &h->cfg, goals, cells_dev, field_dev, dist_dev, key_dev, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
+    if (path_goals_check(h->err, "rg_path", goals)) return 1;
+    if ((goals & RG_GOAL_CELL) && !cells_dev) { h->err = "rg_path: cells_dev is NULL and goals has RG_GOAL_CELL"; return 1; }
+    if (!field_dev && !dist_dev && !key_dev) { h->err = "rg_path: field_dev, dist_dev and key_dev are all NULL"; return 1; }
+    if ((uintptr_t)field_dev & 15) { h->err = "rg_path: field_dev must be a 16-byte aligned device pointer"; return 1; }
+    if (field_dev && !h->sub.empty()) { h->err = "rg_path: field_dev is refused on a handle with config groups (there is no [n_env][H][W] tensor); dist_dev and key_dev are served"; return 1; }
+    return path_checked(h, goals, cells_dev, field_dev, dist_dev, key_dev);
+}
+// A plain FIFO search from the goal cells over rg_path.h's pieces; the corner rule names the same two cells from either end of a move, so a predecessor of
+// cell b in direction d is the cell a = b - d with rg_can_move(a, d).
+int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, int cell_y, int cell_x, uint16_t *field_out, int32_t *dist_out,
+                 uint8_t *key_out) {
+    if (path_goals_check(g_create_err, "rg_path_host", goals)) return 1;
+    if (!field_out && !dist_out && !key_out) { g_create_err = "rg_path_host: field_out, dist_out and key_out are all NULL"; return 1; }
+    if (!cells) { g_create_err = "rg_path_host: cells must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        g_create_err = "rg_path_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
+                       std::to_string(height) + ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    if (px < 0 || py < 0 || px >= width || py >= height) {
+        g_create_err = "rg_path_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+                       std::to_string(height) + " grid";
+        return 1;
+    }
+    const int hw = height * width;
+    std::vector<uint16_t> D((size_t)hw, (uint16_t)RG_PATH_INF);
+    std::vector<int> fifo;
+    fifo.reserve((size_t)hw);
+    for (int i = 0; i < hw; i++) {
+        const int x = i % width, y = i / width;
+        if (rg_path_goal(cells[i], goals, x == px && y == py, x == cell_x && y == cell_y)) { D[i] = 0; fifo.push_back(i); }
+    }
+    for (size_t head = 0; head < fifo.size(); head++) {
+        const int b = fifo[head], bx = b % width, by = b / width;
+        if (!rg_path_ok(cells[b])) continue;  // nobody can step onto it: not expanded
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d), ax = bx - dx, ay = by - dy;
+            if (ax < 0 || ay < 0 || ax >= width || ay >= height) continue;
+            const int a = ay * width + ax;
+            if (D[a] != RG_PATH_INF || !rg_path_ok(cells[a]) || !rg_can_move(cells, height, width, ax, ay, dx, dy)) continue;
+            D[a] = (uint16_t)(D[b] + 1);
+            fifo.push_back(a);
+        }
+    }
+    const uint32_t dp = D[py * width + px];
+    uint32_t dirs = 0;
+    if (dp != 0 && dp != RG_PATH_INF)
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d);
+            if (rg_can_move(cells, height, width, px, py, dx, dy) && D[(py + dy) * width + px + dx] == dp - 1) dirs |= 1u << d;
+        }
+    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
+    if (dist_out) *dist_out = rg_path_dist(dp);
+    if (key_out) *key_out = rg_path_key(dead, dp, (goals & RG_GOAL_STAIRS) && (cells[py * width + px] & C_SURF_MASK) == S_STAIR, dirs);
+    return 0;
+}
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }
 

@@ -37,7 +37,7 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False):
+                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -57,7 +57,14 @@ class HipVecRogueEnv:
         action_mask (opt-in): `self.action_mask` is a bool tensor [N, len(ACTIONS)] on the device -- entry [i, a] says whether ACTIONS[a] would do anything
         for env i now (rg_action_mask: the engine's own move test; False = "can't move", "no downstairs") -- rewritten in place by everything that
         refreshes `obs`.  One small launch more per step, no host trip; it works on every env this class builds.  False: `self.action_mask` is None and
-        nothing is added to any call.  legal_mask() and sample_keys() work either way."""
+        nothing is added to any call.  legal_mask() and sample_keys() work either way.
+
+        guide (opt-in; "stairs", "gold" or "stairs+gold"): `self.guide_keys` is a uint8 tensor [N] on the device -- for each env the key that takes it one
+        move closer to the nearest goal cell, ready for step_keys: '>' on the stairs, 's' where no goal can be reached, '.' on a gold goal's own cell
+        or in the Grave modal -- and `self.guide_dist` an int32 tensor [N], the number of moves to that cell, -1 = unreachable (rg_path: the engine's own
+        move test, shortest paths from the goal cells).  Both are rewritten in place by everything that refreshes `obs`: one launch more per step, no
+        host trip.  The guide is PRIVILEGED: it sees stairs, gold and passages the player has not discovered -- a teacher, a shaping potential or a
+        critic input, not an observation.  None: both attributes are None and nothing is added to any call.  path() works either way."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -70,6 +77,9 @@ class HipVecRogueEnv:
         if (typed16 or symbol_ids) and (crop is not None or persistent_obs):
             raise ValueError("%s cannot be combined with %s: the crop and the bound observation tensor are float32 only"
                              % ("symbol_ids=True" if symbol_ids else "obs_dtype=%s" % (obs_dtype,), "crop" if crop is not None else "persistent_obs=True"))
+
+        if guide is not None and (not isinstance(guide, str) or guide not in inner.PATH_GOALS):
+            raise ValueError("guide must be None or one of %s, got %r" % (", ".join(repr(g) for g in inner.PATH_GOALS), guide))
 
         if crop is not None:
             if persistent_obs:
@@ -116,6 +126,10 @@ class HipVecRogueEnv:
         self._draw = 0  # sample_keys: the draw counter of calls that give none
         self._mask_u8 = torch.zeros((self.num_envs, len(self.ACTIONS)), dtype=torch.uint8, device=self.device) if action_mask else None
         self.action_mask = None if self._mask_u8 is None else self._mask_u8.view(torch.bool)
+        self.guide = guide
+        self._guide_goals = 0 if guide is None else inner.PATH_GOALS[guide]
+        self.guide_keys = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
+        self.guide_dist = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
@@ -183,6 +197,28 @@ class HipVecRogueEnv:
             self._encode_view(v)
         if self._mask_u8 is not None:
             self._h.check(self._h.L.rg_action_mask(self._h.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0))
+        if self._guide_goals:
+            self._h.check(self._h.L.rg_path(self._h.h, self._guide_goals, None, None, C.c_void_p(self.guide_dist.data_ptr()), C.c_void_p(self.guide_keys.data_ptr())))
+
+    def path(self, goal="stairs", cells=None, field=False):
+        """(keys, dist, field) on the device (rg_path): keys uint8 [N], the teacher key of every env towards its nearest goal cell, for step_keys; dist int32 [N],
+        the number of moves to it, -1 = unreachable; field uint16 [N, H, W], the number of moves from every cell (0xFFFF = unreachable), or None unless
+        field=True (not for batches that mix sizes or configs).  goal: "stairs", "gold", "stairs+gold", or None with `cells`.  cells (optional): an int32
+        tensor [N, 2] on this env's device, one cell (y, x) per env that is a goal too; a cell outside the grid adds nothing.  The answers are PRIVILEGED:
+        they see stairs, gold and passages the player has not discovered.  No host trip; the states, mirrors and `obs` are left as they are."""
+        torch = self.torch
+        goals = inner._path_goals(goal, cells is not None)
+        if cells is not None:
+            if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or cells.device != self.device or tuple(cells.shape) != (self.num_envs, 2):
+                raise ValueError("path: cells must be an int32 tensor [%d, 2] on %s" % (self.num_envs, self.device))
+            cells = cells.contiguous()
+        with torch.cuda.device(self.device):
+            keys = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
+            dist = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+            fld = torch.empty((self.num_envs, self.height, self.width), dtype=torch.uint16, device=self.device) if field else None
+        self._h.check(self._h.L.rg_path(self._h.h, goals, None if cells is None else C.c_void_p(cells.data_ptr()), None if fld is None else C.c_void_p(fld.data_ptr()),
+                                        C.c_void_p(dist.data_ptr()), C.c_void_p(keys.data_ptr())))
+        return keys, dist, fld
 
     def _mask_call(self, keys, mask, sample, seed, draw):
         kb, nk = inner._mask_keys(keys)

@@ -72,6 +72,10 @@ class ParallelRogueEnv:
         """bool [N, ACTION_LEN]: entry [i, a] says whether ACTIONS[a] would do anything for env i now (RogueEnv.action_mask for the whole batch)."""
         return self.game.action_masks()
 
+    def path_keys(self, goal: str = "stairs"):
+        """(keys uint8 [N], dist int32 [N]): RogueEnv.path_key for the whole batch, as key bytes and distances with -1 for unreachable."""
+        return self.game.path_keys(goal)
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
         return batch

@@ -206,6 +206,13 @@ class RogueEnv(Env):
         for diagonals, the surface under the player for '>'), which the screen does not show completely."""
         return self.game.action_mask()
 
+    def path_key(self, goal: str = "stairs"):
+        """(key, dist): the key of ACTIONS -- a str of length 1 -- that takes the player one move closer to the nearest goal cell ("stairs", "gold" or
+        "stairs+gold") and the number of moves to it, or ('s', None) when none can be reached; '>' on the stairs.  Shortest paths under the engine's
+        own move test.  PRIVILEGED: it sees stairs, gold and passages the player has not discovered -- a teacher, not an observation."""
+        key, dist = self.game.path_key(goal)
+        return key.decode("latin-1"), dist
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

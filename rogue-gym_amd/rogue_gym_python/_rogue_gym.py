@@ -48,6 +48,7 @@ _INT_FUNCS = (
     "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed", "rg_step_obs_typed",
     "rg_obs_crop_typed", "rg_step_obs_crop_typed",
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
+    "rg_path", "rg_path_host",
 )
 
 
@@ -113,12 +114,13 @@ def load_library():
         "rg_tail_encode": [vp, i32],
         "rg_action_mask": [vp, vp, i32, vp, vp, C.c_uint64, C.c_uint64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
         "rg_sample_index": [C.c_uint64, u32, C.c_uint64, u32],
+        "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-                "rg_sample_index"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_sample_index", "rg_path", "rg_path_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -271,6 +273,18 @@ def _mask_keys(keys):
     return bytes(keys), len(keys)
 
 
+PATH_GOALS = {"stairs": 1, "gold": 2, "stairs+gold": 3}  # RG_GOAL_STAIRS, RG_GOAL_GOLD; RG_GOAL_CELL (4) comes with a caller's cells
+
+
+def _path_goals(goal, with_cells=False):
+    """The goal bits of rg_path for a goal name (None = the caller's cells alone)."""
+    if goal is None and with_cells:
+        return 4
+    if not isinstance(goal, str) or goal not in PATH_GOALS:
+        raise ValueError("goal must be one of %s%s, got %r" % (", ".join(repr(g) for g in PATH_GOALS), " (or None with cells)" if with_cells else "", goal))
+    return PATH_GOALS[goal] | (4 if with_cells else 0)
+
+
 class _Handle:
     """Owns one rg_t."""
 
@@ -380,6 +394,25 @@ class _Handle:
         out = np.empty((self.n, nk), np.uint8)
         self.check(self.L.rg_dev_read(self.h, C.c_void_p(self._mask_dev[0]), out.ctypes.data, nbytes))
         return out.view(np.bool_)
+
+    def path_keys(self, goal="stairs"):
+        """(keys u8 [n], dist i32 [n]) towards `goal` ("stairs", "gold", "stairs+gold"): rg_path into the device scratch buffer the handle keeps, one
+        rg_dev_read.  dist -1 = unreachable."""
+        goals = _path_goals(goal)
+        nbytes = self.n * 5
+        if self._mask_dev is None or self._mask_dev[1] < nbytes:
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._mask_dev = (p.value, nbytes)
+        base = self._mask_dev[0]  # dist i32 [n], then keys u8 [n]
+        self.check(self.L.rg_path(self.h, goals, None, None, C.c_void_p(base), C.c_void_p(base + 4 * self.n)))
+        out = np.empty(nbytes, np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
+        return out[4 * self.n:].copy(), out[:4 * self.n].view(np.int32).copy()
 
     def history_keys(self, env, previous=False):
         n = C.c_uint32()
@@ -780,6 +813,12 @@ class GameState:
         """numpy bool [n_keys]: which keys would do anything now (not part of the reference's API; rg_action_mask)."""
         return self._h.action_mask(keys)[0]
 
+    def path_key(self, goal="stairs"):
+        """(key byte as bytes of length 1, distance or None): the key that takes the player one move closer to the nearest goal cell and the number of
+        moves to it (not part of the reference's API; rg_path -- privileged: it sees what the player has not discovered)."""
+        keys, dist = self._h.path_keys(goal)
+        return bytes(keys[:1]), (None if dist[0] < 0 else int(dist[0]))
+
     def save_state(self):
         """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
         after a load_state dumps the saved episode's keys."""
@@ -843,6 +882,10 @@ class ParallelGameState:
     def action_masks(self, keys=None):
         """numpy bool [n, n_keys]: which keys would do anything for each env now (not part of the reference's API; rg_action_mask)."""
         return self._h.action_mask(keys)
+
+    def path_keys(self, goal="stairs"):
+        """(keys numpy u8 [n], dist numpy i32 [n], -1 = unreachable) towards `goal` (not part of the reference's API; rg_path)."""
+        return self._h.path_keys(goal)
 
     def dump_config(self, env=0):
         buf = C.create_string_buffer(1 << 16)

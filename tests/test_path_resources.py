@@ -1,0 +1,22 @@
+"""The budget of the built path kernels (rogue-gym_amd/csrc/rg_path.hip), read from the code objects inside librogue_gym_hip.so: no scratch, no spills, no
+AGPRs, at most 128 registers per instance -- and no name that a resource test of another kernel family would count."""
+from test_kernel_resources import kernel_metadata
+
+
+def test_budget_of_every_path_kernel():
+    md = kernel_metadata()
+    path = {k: m for k, m in md.items() if "k_path" in k}
+    # per row-word count (1, 2, 3, 5), group size (16, 32, 64 lanes) and mode (keys / field)
+    assert len(path) == 24, sorted(path)
+    for wn in (1, 2, 3, 5):
+        for gs in (16, 32, 64):
+            for field in (0, 1):
+                assert any("k_pathILi%dELi%dELb%dE" % (wn, gs, field) in k for k in path), (wn, gs, field, sorted(path))
+    for k, m in sorted(path.items()):
+        print(k, m)
+        assert m["private_segment_fixed_size"] == 0, (k, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (k, m)
+        assert m["agpr_count"] == 0, (k, m)
+        assert m["vgpr_count"] <= 128, (k, m)
+        for other in ("k_obs", "k_step", "k_crop_typed", "k_regen", "k_action_mask"):
+            assert other not in k, (k, other)
