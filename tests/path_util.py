@@ -1,5 +1,6 @@
 """Helpers shared by the path tests: a numpy restatement of the shortest-path rule (include/rogue_gym_hip.h, rg_path) -- field, distance, teacher key and
-the own-cell gold exclusion -- on cell words in rg_debug_fetch's layout, and the call of the host entry."""
+the own-cell gold exclusion -- on cell words in rg_debug_fetch's layout, the call of the host entry, and the call of rg_path on a handle."""
+import ctypes as C
 from collections import deque
 
 import numpy as np
@@ -11,6 +12,7 @@ INF = 0xFFFF                                  # RG_PATH_UNREACHABLE
 DIR_KEYS = "kjhlyubn"                         # Direction enum order: Up Down Left Right LeftUp RightUp LeftDown RightDown
 DIR_VECS = [mu.DIRS[k] for k in DIR_KEYS]     # (dx, dy)
 C_GOLD = 0x0800
+SLACK = 64  # elements behind the last env of every output buffer of path_call: they keep their fill
 
 
 def split(cells):
@@ -120,3 +122,36 @@ def host(lib, cells, px, py, goals, dead=0, cell=(-1, -1), want=(True, True, Tru
                         d.ctypes.data if want[1] else None, k.ctypes.data if want[2] else None):
         raise RuntimeError(lib.rg_last_error(None).decode())
     return (f if want[0] else None), (int(d[0]) if want[1] else None), (int(k[0]) if want[2] else None)
+
+
+def ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def read(hd, t):
+    """Host copy of device tensor `t`, byte for byte, through the handle (rg_dev_read waits for the handle's stream)."""
+    out = np.empty(t.numel() * t.element_size(), np.uint8)
+    hd.check(hd.L.rg_dev_read(hd.h, ptr(t), out.ctypes.data, out.nbytes))
+    return out
+
+
+def path_call(hd, goals, cells=None, field=True, hw=None):
+    """rg_path on a raw handle into buffers pre-filled with 0xAA -> (field u16 [n][H][W] or None, dist i32 [n], keys u8 [n]); every byte behind the last
+    env must keep its fill."""
+    import torch
+    n, dev = hd.n, "cuda:%d" % hd.device
+    hw = hd.height * hd.width if hw is None else hw
+    f = torch.full((n * hw + SLACK,), 0xAAAA - 0x10000, dtype=torch.int16, device=dev) if field else None
+    d = torch.full((n + SLACK,), 0xAAAAAAAA - (1 << 32), dtype=torch.int32, device=dev)
+    k = torch.full((n + SLACK,), 0xAA, dtype=torch.uint8, device=dev)
+    c = None if cells is None else torch.as_tensor(np.ascontiguousarray(cells, np.int32), device=dev)
+    torch.cuda.synchronize()
+    hd.check(hd.L.rg_path(hd.h, goals, ptr(c), ptr(f), ptr(d), ptr(k)))
+    fo = None
+    if field:
+        fb = read(hd, f).view(np.uint16)
+        assert (fb[n * hw:] == 0xAAAA).all(), "the field pass wrote behind the last env"
+        fo = fb[:n * hw].reshape(n, hd.height, hd.width)
+    db, kb = read(hd, d).view(np.int32), read(hd, k)
+    assert (db[n:].view(np.uint32) == 0xAAAAAAAA).all() and (kb[n:] == 0xAA).all(), "a pass wrote behind the last env"
+    return fo, db[:n].copy(), kb[:n].copy()

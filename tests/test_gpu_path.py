@@ -1,6 +1,7 @@
 """rg_path on the GPU (rogue-gym_amd/csrc/rg_path.hip k_path): field, distance and teacher key against the host entry and the numpy rule on states reached by
-play -- every wave shape, row-word count and store alignment --, config groups and mixed sizes, no side effects, the teacher judged by what the step then
-does, the Python surface and the refusals."""
+play, config groups and mixed sizes, no side effects, the teacher judged by what the step then does, the Python surface and the refusals.  Play reaches
+seven grid shapes and walks of about a hundred moves; every wave shape, row-word count and store alignment, walkable borders and the high distance planes
+are reached by tests/test_gpu_constructed_grids.py, on grids of its own making."""
 import ctypes as C
 import json
 
@@ -10,11 +11,9 @@ import pytest
 import mask_util as mu
 import path_util as pu
 from parity_util import HipBatch
-from path_util import GOAL_CELL, GOAL_GOLD, GOAL_STAIRS
+from path_util import GOAL_CELL, GOAL_GOLD, GOAL_STAIRS, path_call, ptr
 
 pytestmark = pytest.mark.gpu
-
-SLACK = 64  # elements behind the last env of every output buffer: they keep their fill
 
 
 def torch_mod():
@@ -24,41 +23,8 @@ def torch_mod():
     return torch
 
 
-def ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def grid_cfg(w, h, rx, ry):
     return {"width": w, "height": h, "dungeon": {"style": "rogue", "room_num_x": rx, "room_num_y": ry, "min_room_size": {"x": 4, "y": 4}}}
-
-
-def read(hd, t):
-    """Host copy of device tensor `t`, byte for byte, through the handle (rg_dev_read waits for the handle's stream)."""
-    out = np.empty(t.numel() * t.element_size(), np.uint8)
-    hd.check(hd.L.rg_dev_read(hd.h, ptr(t), out.ctypes.data, out.nbytes))
-    return out
-
-
-def path_call(hd, goals, cells=None, field=True, hw=None):
-    """rg_path on a raw handle into buffers pre-filled with 0xAA -> (field u16 [n][H][W] or None, dist i32 [n], keys u8 [n]); every byte behind the last
-    env must keep its fill."""
-    torch = torch_mod()
-    n, dev = hd.n, "cuda:%d" % hd.device
-    hw = hd.height * hd.width if hw is None else hw
-    f = torch.full((n * hw + SLACK,), 0xAAAA - 0x10000, dtype=torch.int16, device=dev) if field else None
-    d = torch.full((n + SLACK,), 0xAAAAAAAA - (1 << 32), dtype=torch.int32, device=dev)
-    k = torch.full((n + SLACK,), 0xAA, dtype=torch.uint8, device=dev)
-    c = None if cells is None else torch.as_tensor(np.ascontiguousarray(cells, np.int32), device=dev)
-    torch.cuda.synchronize()
-    hd.check(hd.L.rg_path(hd.h, goals, ptr(c), ptr(f), ptr(d), ptr(k)))
-    fo = None
-    if field:
-        fb = read(hd, f).view(np.uint16)
-        assert (fb[n * hw:] == 0xAAAA).all(), "the field pass wrote behind the last env"
-        fo = fb[:n * hw].reshape(n, hd.height, hd.width)
-    db, kb = read(hd, d).view(np.int32), read(hd, k)
-    assert (db[n:].view(np.uint32) == 0xAAAAAAAA).all() and (kb[n:] == 0xAA).all(), "a pass wrote behind the last env"
-    return fo, db[:n].copy(), kb[:n].copy()
 
 
 def env_states(hd, dims=None):

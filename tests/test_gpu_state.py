@@ -7,6 +7,7 @@ import json
 import numpy as np
 import pytest
 
+from grid_util import record_offsets
 from oracle.pyoracle import OracleEnv
 from parity_util import ALL_KEYS, HipBatch, compare_internal, custom_enemy_config
 
@@ -35,28 +36,6 @@ def vec_env(cfg, seeds, **kw):
     from rogue_gym.envs.device import HipVecRogueEnv
 
     return HipVecRogueEnv(seeded(cfg, seeds), **kw)
-
-
-def pad16(b):
-    return (b + 15) & ~15
-
-
-def record_offsets(rec):
-    """(o_cell, o_words, H, W) of a record, from its header (the layout of include/rogue_gym_hip.h / rg_state_io.h)."""
-    hd = np.frombuffer(bytes(rec[:64]), "<u4")
-    H, W, nr, sec = int(hd[3] & 0xFFFF), int(hd[3] >> 16), int(hd[4]), int(hd[5])
-    hw = H * W
-    off = 64
-    o_cell = off
-    off += pad16(2 * hw) + 2 * pad16(hw)
-    if sec & 1:
-        off += pad16(2 * 9 * hw)
-    if sec & 2:
-        off += pad16(4 * 9 * H * (2 if W <= 64 else 3))
-    off += 48
-    if sec & 4:
-        off += pad16(4 * ((nr * 2 + 1 + (nr + 3) // 4 + 3) & ~3))
-    return o_cell, off, H, W
 
 
 def on_stairs(rec):
