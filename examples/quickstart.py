@@ -121,3 +121,14 @@ print("HipVecRogueEnv(guide='stairs'): keys %s %s, dist %s %s; dungeon level %.2
       % (tuple(venv.guide_keys.shape), venv.guide_keys.dtype, tuple(venv.guide_dist.shape), venv.guide_dist.dtype, start.float().mean().item(),
          venv.status[:, 0].float().mean().item(), venv.guide_dist[venv.guide_dist >= 0].float().mean().item()))
 venv.close()
+
+# 3h. the same teacher through secrets, and an explorer that does not cheat: guide_secrets plans THROUGH hidden passages and locked doors and searches
+#     beside them; guide="explore" plans on the player's own map only -- towards the stairs once they are on it, else towards the nearest known cell
+#     beside an unknown one -- and is not privileged: a baseline agent, or realistic exploration trajectories for imitation ---------------------------
+for kw in (dict(guide="stairs", guide_secrets=True), dict(guide="explore")):
+    venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, **kw)
+    for t in range(200):
+        obs, reward, done = venv.step_keys(venv.guide_keys)
+    print("HipVecRogueEnv(%s): dungeon level %.2f per env after 200 steps, %.1f %% of the envs without a route now"
+          % (", ".join("%s=%r" % kv for kv in kw.items()), venv.status[:, 0].float().mean().item(), 100 * (venv.guide_dist < 0).float().mean().item()))
+    venv.close()

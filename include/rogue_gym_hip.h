@@ -281,6 +281,42 @@ int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_d
 int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, int cell_y, int cell_x,
                  uint16_t *field_out, int32_t *dist_out, uint8_t *key_out);
 
+/* ROUTES THAT FINISH A LEVEL: rg_path's rule with two orthogonal mode bits, one more goal kind and a fallback goal set.  rg_path stops at the first secret (a
+ * hidden or locked cell is never a move's target) and all of its answers are privileged; rg_route plans through secrets and / or on the player's own map.
+ *   mode, the OR of: RG_ROUTE_SECRETS plan THROUGH hidden / locked cells and ask for 's' when the next cell is one (Search touches the eight cells around
+ *     the player, floor.rs:349-370); RG_ROUTE_KNOWN plan on the player's own map only -- with it nothing is privileged.
+ *   Per cell word c: walk = the surface can be walked on; secret = HIDDEN or LOCKED; known = DRAWN or VISIBLE, or the cell is the player's own;
+ *     K = not RG_ROUTE_KNOWN, or known; pass = K and (secret ? RG_ROUTE_SECRETS : walk): what a move of the search graph may end on -- a secret cell keeps the
+ *     surface it was dug into (a room's wall, bare rock) until Search finds it (floor.rs:93-100, 359-366), so its attr alone makes it a cell of the route;
+ *     corner = walk and K: what the corner rule of a diagonal asks of the two orthogonal neighbours, by the surface as it is now.
+ *   Goals: RG_GOAL_STAIRS and RG_GOAL_GOLD as in rg_path, but only where K; RG_GOAL_CELL as in rg_path, whatever the cell's own word; RG_GOAL_FRONTIER
+ *     (legal only together with RG_ROUTE_KNOWN) every pass cell that has an in-grid ORTHOGONAL neighbour which is not known.  Standing on a cell draws its
+ *     four orthogonal neighbours unless they are hidden, so a frontier cell is resolved by stepping onto it, and a player standing on one is next to a
+ *     hidden cell.
+ *   The field D and the distance are rg_path's with pass and corner in place of ok and walkable; a goal that is not pass is never expanded.
+ *   Tiers: an env whose player is not reached from `goals` (tier 0) is answered from `fallback_goals` (tier 1; 0 = none).  tier u8 = 0, 1, or 255 when
+ *     neither reached it (distance -1 then).
+ *   Key u8: '.' for an env in the Grave modal.  Else, D[player] == 0: '>' on the stairs when RG_GOAL_STAIRS is among the answering tier's goals; otherwise 's'
+ *     when RG_GOAL_FRONTIER is among them and the own cell is a frontier cell; otherwise '.'.  Else, D[player] finite: the key of the FIRST direction in
+ *     Direction-enum order whose move is legal in the search graph, whose target has D[player] - 1 AND whose target is not secret; if there is none, 's':
+ *     the next cell is a secret one of the eight neighbours.  Else 's'.  A move key is always legal by rg_action_mask's move test.
+ *   With mode 0, no RG_GOAL_FRONTIER and no fallback every byte equals rg_path's.
+ * rg_route: cells_dev, dist_dev, key_dev as rg_path's; tier_dev (nullable) = u8 [n_env].  There is no device field.  Asynchronous on the handle's stream.  It
+ *   reads game state only: the pending render is not flushed, the mirrors, every flag bit, a bound observation tensor and the RNG streams are left alone.
+ *   Config groups and mixed-size batches are served.  Refused, non-zero with a message naming the argument, nothing launched or written: unknown bits in goals,
+ *   fallback_goals or mode; goals zero; RG_GOAL_FRONTIER (in either word) without RG_ROUTE_KNOWN; RG_GOAL_CELL (in either word) without cells_dev; all
+ *   outputs NULL.
+ * rg_route_host (stateless, needs no device): the same rule for ONE env, arguments as rg_path_host's; field_out = the field of the tier that answered (of
+ *   the last tier searched when neither did).  Refusals as rg_route's, and cells NULL, the sizes or (px, py) out of range; the message is read through
+ *   rg_last_error(NULL). */
+#define RG_GOAL_FRONTIER  8u   /* accepted by rg_route only; rg_path keeps refusing it */
+#define RG_ROUTE_SECRETS  1u
+#define RG_ROUTE_KNOWN    2u
+int rg_route(rg_t *h, uint32_t goals, uint32_t fallback_goals, uint32_t mode, const int32_t *cells_dev,
+             int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev);
+int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, uint32_t fallback_goals,
+                  uint32_t mode, int cell_y, int cell_x, uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

@@ -17,6 +17,7 @@
 #include "rg_state_io.h"
 #include "rg_action_mask.h"
 #include "rg_path.h"
+#include "rg_route.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -61,6 +62,8 @@ int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int
 void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
                      hipEvent_t ev0, hipEvent_t ev1);
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
+void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
+               hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -1099,6 +1102,115 @@ int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, i
     if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
     if (dist_out) *dist_out = rg_path_dist(dp);
     if (key_out) *key_out = rg_path_key(dead, dp, (goals & RG_GOAL_STAIRS) && (cells[py * width + px] & C_SURF_MASK) == S_STAIR, dirs);
+    return 0;
+}
+// Search-aware and map-aware routes (rg_route.hip; the rule: rg_route.h).  route_args_check: the words of a call, refused before anything is launched.
+static int route_args_check(std::string &err, const char *what, uint32_t goals, uint32_t fallback, uint32_t mode, bool have_cells, const char *cells_name) {
+    const std::string w = std::string(what) + ": ";
+    if (goals == 0 || (goals & ~RG_ROUTE_GOALS_ALL)) {
+        err = w + "goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(goals);
+        return 1;
+    }
+    if (fallback & ~RG_ROUTE_GOALS_ALL) {
+        err = w + "fallback_goals must be 0 or an OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(fallback);
+        return 1;
+    }
+    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
+    if (((goals | fallback) & RG_GOAL_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
+        err = w + "RG_GOAL_FRONTIER in " + ((goals & RG_GOAL_FRONTIER) ? "goals" : "fallback_goals") + " needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " +
+              std::to_string(mode);
+        return 1;
+    }
+    if (((goals | fallback) & RG_GOAL_CELL) && !have_cells) {
+        err = w + cells_name + " is NULL and " + ((goals & RG_GOAL_CELL) ? "goals" : "fallback_goals") + " has RG_GOAL_CELL";
+        return 1;
+    }
+    return 0;
+}
+static int route_checked(rg_t *h, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group writes its envs' entries straight into the handle's tensors (RgState::ext), as rg_path does
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, route_checked(sh, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev));
+        return 0;
+    }
+    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
+    rgk_route(&h->S, &h->cfg, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_route(rg_t *h, uint32_t goals, uint32_t fallback_goals, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
+    if (route_args_check(h->err, "rg_route", goals, fallback_goals, mode, cells_dev != nullptr, "cells_dev")) return 1;
+    if (!dist_dev && !key_dev && !tier_dev) { h->err = "rg_route: dist_dev, key_dev and tier_dev are all NULL"; return 1; }
+    return route_checked(h, goals, fallback_goals, mode, cells_dev, dist_dev, key_dev, tier_dev);
+}
+// One FIFO search per tier over rg_route.h's pieces, as rg_path_host's: a predecessor of cell b in direction d is the cell a = b - d, itself pass, with the
+// two corner cells of a diagonal asked for `corner`.
+int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, uint32_t fallback_goals, uint32_t mode, int cell_y, int cell_x,
+                  uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out) {
+    if (route_args_check(g_create_err, "rg_route_host", goals, fallback_goals, mode, true, "cells")) return 1;
+    if (!field_out && !dist_out && !key_out && !tier_out) { g_create_err = "rg_route_host: field_out, dist_out, key_out and tier_out are all NULL"; return 1; }
+    if (!cells) { g_create_err = "rg_route_host: cells must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        g_create_err = "rg_route_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
+                       std::to_string(height) + ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    if (px < 0 || py < 0 || px >= width || py >= height) {
+        g_create_err = "rg_route_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+                       std::to_string(height) + " grid";
+        return 1;
+    }
+    const int hw = height * width, pi = py * width + px;
+    auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < width && y < height && !rg_route_known(cells[y * width + x], y * width + x == pi); };
+    auto frontier_at = [&](int i) {
+        const int x = i % width, y = i / width;
+        return rg_route_frontier(cells[i], mode, i == pi, unknown_at(x - 1, y) || unknown_at(x + 1, y) || unknown_at(x, y - 1) || unknown_at(x, y + 1));
+    };
+    std::vector<uint16_t> D;
+    std::vector<int> fifo;
+    fifo.reserve((size_t)hw);
+    uint32_t dp = RG_PATH_INF, tier = RG_ROUTE_NO_TIER, gw = goals;
+    for (uint32_t t = 0; t < 2 && tier == RG_ROUTE_NO_TIER; t++) {
+        if (t && !fallback_goals) break;
+        gw = t ? fallback_goals : goals;
+        D.assign((size_t)hw, (uint16_t)RG_PATH_INF);
+        fifo.clear();
+        for (int i = 0; i < hw; i++) {
+            const int x = i % width, y = i / width;
+            if (rg_route_goal(cells[i], gw, mode, i == pi, x == cell_x && y == cell_y) || ((gw & RG_GOAL_FRONTIER) && frontier_at(i))) { D[i] = 0; fifo.push_back(i); }
+        }
+        // (without field_out the search ends once the player's cell has its distance: every cell one move closer has its own by then)
+        for (size_t head = 0; head < fifo.size() && (field_out || D[pi] == RG_PATH_INF); head++) {
+            const int b = fifo[head], bx = b % width, by = b / width;
+            if (!rg_route_pass(cells[b], mode, b == pi)) continue;  // nobody can step onto it: not expanded
+            for (int d = 0; d < 8; d++) {
+                const int dx = rg_path_dx(d), dy = rg_path_dy(d), ax = bx - dx, ay = by - dy;
+                if (ax < 0 || ay < 0 || ax >= width || ay >= height) continue;
+                const int a = ay * width + ax;
+                if (D[a] != RG_PATH_INF || !rg_route_pass(cells[a], mode, a == pi)) continue;
+                if (dx != 0 && dy != 0 && !(rg_route_corner(cells[ay * width + bx], mode, ay * width + bx == pi) && rg_route_corner(cells[by * width + ax], mode, by * width + ax == pi)))
+                    continue;
+                D[a] = (uint16_t)(D[b] + 1);
+                fifo.push_back(a);
+            }
+        }
+        dp = D[pi];
+        if (dp != RG_PATH_INF) tier = t;
+    }
+    uint32_t dirs = 0;
+    if (dp != 0 && dp != RG_PATH_INF)
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d), x = px + dx, y = py + dy;
+            if (x < 0 || y < 0 || x >= width || y >= height) continue;
+            const uint32_t t = cells[y * width + x];
+            bool ok = rg_route_pass(t, mode, false) && !rg_route_secret(t) && D[y * width + x] == dp - 1;
+            if (dx != 0 && dy != 0) ok = ok && rg_route_corner(cells[py * width + x], mode, false) && rg_route_corner(cells[y * width + px], mode, false);
+            dirs |= (uint32_t)ok << d;
+        }
+    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
+    if (dist_out) *dist_out = rg_path_dist(dp);
+    if (key_out) *key_out = rg_route_key(dead, dp, gw, (cells[pi] & C_SURF_MASK) == S_STAIR, (gw & RG_GOAL_FRONTIER) && frontier_at(pi), dirs);
+    if (tier_out) *tier_out = (uint8_t)tier;
     return 0;
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }

@@ -37,7 +37,7 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None):
+                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -64,7 +64,16 @@ class HipVecRogueEnv:
         or in the Grave modal -- and `self.guide_dist` an int32 tensor [N], the number of moves to that cell, -1 = unreachable (rg_path: the engine's own
         move test, shortest paths from the goal cells).  Both are rewritten in place by everything that refreshes `obs`: one launch more per step, no
         host trip.  The guide is PRIVILEGED: it sees stairs, gold and passages the player has not discovered -- a teacher, a shaping potential or a
-        critic input, not an observation.  None: both attributes are None and nothing is added to any call.  path() works either way."""
+        critic input, not an observation.  None: both attributes are None and nothing is added to any call.  path() works either way.
+
+        guide_secrets (with a guide): the guide plans THROUGH hidden and locked cells and answers 's' when the next cell of the route is one (rg_route with
+        RG_ROUTE_SECRETS in place of rg_path), so an env whose stairs lie behind a secret searches in the right place instead of where it stands.  False:
+        the guide is rg_path's, byte for byte and launch for launch.
+
+        guide="explore" is the explorer that is NOT privileged: it plans on the player's own map only (the cells that are drawn or in view), towards the
+        stairs once they are on it, else towards the nearest known cell beside an unknown one, and searches when it stands on such a cell -- a hidden
+        passage cell is what stays unknown beside it (rg_route: goals stairs, fallback frontier, mode known).  `self.guide_tier` is a uint8
+        tensor [N]: 0 = the stairs answered, 1 = the frontier, 255 = neither (the key is 's' then); None for every other guide."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -78,8 +87,10 @@ class HipVecRogueEnv:
             raise ValueError("%s cannot be combined with %s: the crop and the bound observation tensor are float32 only"
                              % ("symbol_ids=True" if symbol_ids else "obs_dtype=%s" % (obs_dtype,), "crop" if crop is not None else "persistent_obs=True"))
 
-        if guide is not None and (not isinstance(guide, str) or guide not in inner.PATH_GOALS):
-            raise ValueError("guide must be None or one of %s, got %r" % (", ".join(repr(g) for g in inner.PATH_GOALS), guide))
+        if guide is not None and (not isinstance(guide, str) or (guide not in inner.PATH_GOALS and guide != "explore")):
+            raise ValueError("guide must be None or one of %s, 'explore', got %r" % (", ".join(repr(g) for g in inner.PATH_GOALS), guide))
+        if guide_secrets and guide is None:
+            raise ValueError("guide_secrets=True needs a guide")
 
         if crop is not None:
             if persistent_obs:
@@ -127,7 +138,11 @@ class HipVecRogueEnv:
         self._mask_u8 = torch.zeros((self.num_envs, len(self.ACTIONS)), dtype=torch.uint8, device=self.device) if action_mask else None
         self.action_mask = None if self._mask_u8 is None else self._mask_u8.view(torch.bool)
         self.guide = guide
-        self._guide_goals = 0 if guide is None else inner.PATH_GOALS[guide]
+        self._guide_goals = 0 if guide is None or guide == "explore" or guide_secrets else inner.PATH_GOALS[guide]  # rg_path's goals, 0 = rg_path is not called
+        # (goals, fallback_goals, mode) of rg_route, None = rg_route is not called
+        self._guide_route = inner._route_args(*inner.EXPLORE) if guide == "explore" else inner._route_args(guide, None, True, False) if guide_secrets else None
+        self.guide_secrets = bool(guide_secrets)
+        self.guide_tier = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device) if guide == "explore" else None
         self.guide_keys = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
         self.guide_dist = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
         self.persistent_obs = bool(persistent_obs)
@@ -199,6 +214,30 @@ class HipVecRogueEnv:
             self._h.check(self._h.L.rg_action_mask(self._h.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0))
         if self._guide_goals:
             self._h.check(self._h.L.rg_path(self._h.h, self._guide_goals, None, None, C.c_void_p(self.guide_dist.data_ptr()), C.c_void_p(self.guide_keys.data_ptr())))
+        if self._guide_route is not None:
+            self._h.check(self._h.L.rg_route(self._h.h, self._guide_route[0], self._guide_route[1], self._guide_route[2], None, C.c_void_p(self.guide_dist.data_ptr()),
+                                             C.c_void_p(self.guide_keys.data_ptr()), None if self.guide_tier is None else C.c_void_p(self.guide_tier.data_ptr())))
+
+    def route(self, goal="stairs", fallback=None, secrets=False, known=False, cells=None):
+        """(keys, dist, tier) on the device (rg_route): path() with two switches and a fallback goal, without a field.  secrets=True plans THROUGH hidden and
+        locked cells and answers 's' when the next cell of the route is one.  known=True plans on the player's own map only (the cells that are drawn or
+        in view): nothing is privileged then.  goal / fallback: "stairs", "gold", "stairs+gold", or "frontier" with known=True (the known cells beside an
+        unknown one); goal None with `cells` = the caller's cells alone.  An env that `goal` does not reach is answered from `fallback`; tier uint8 [N]
+        says which answered: 0, 1, or 255 = neither (dist -1, key 's').  cells as path()'s; they join `goal`.  No host trip; the states, mirrors and
+        `obs` are left as they are."""
+        torch = self.torch
+        goals, fb, mode = inner._route_args(goal, fallback, secrets, known, cells is not None)
+        if cells is not None:
+            if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or cells.device != self.device or tuple(cells.shape) != (self.num_envs, 2):
+                raise ValueError("route: cells must be an int32 tensor [%d, 2] on %s" % (self.num_envs, self.device))
+            cells = cells.contiguous()
+        with torch.cuda.device(self.device):
+            keys = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
+            dist = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+            tier = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
+        self._h.check(self._h.L.rg_route(self._h.h, goals, fb, mode, None if cells is None else C.c_void_p(cells.data_ptr()), C.c_void_p(dist.data_ptr()),
+                                         C.c_void_p(keys.data_ptr()), C.c_void_p(tier.data_ptr())))
+        return keys, dist, tier
 
     def path(self, goal="stairs", cells=None, field=False):
         """(keys, dist, field) on the device (rg_path): keys uint8 [N], the teacher key of every env towards its nearest goal cell, for step_keys; dist int32 [N],

@@ -76,6 +76,11 @@ class ParallelRogueEnv:
         """(keys uint8 [N], dist int32 [N]): RogueEnv.path_key for the whole batch, as key bytes and distances with -1 for unreachable."""
         return self.game.path_keys(goal)
 
+    def route_keys(self, goal: str = "stairs", fallback=None, secrets: bool = False, known: bool = False):
+        """(keys uint8 [N], dist int32 [N], tier uint8 [N]): RogueEnv.route_key for the whole batch, as key bytes, distances with -1 for unreachable and
+        tiers with 255 for neither."""
+        return self.game.route_keys(goal, fallback, secrets, known)
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
         return batch

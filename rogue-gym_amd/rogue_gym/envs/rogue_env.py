@@ -213,6 +213,15 @@ class RogueEnv(Env):
         key, dist = self.game.path_key(goal)
         return key.decode("latin-1"), dist
 
+    def route_key(self, goal: str = "stairs", fallback: Optional[str] = None, secrets: bool = False, known: bool = False):
+        """(key, dist, tier): path_key with two switches and a fallback goal.  secrets=True plans THROUGH hidden and locked cells and answers 's' when the
+        next cell of the route is one (Search works on the eight cells around the player).  known=True plans on the player's own map only -- the cells
+        that are drawn or in view -- so nothing is privileged.  fallback ("stairs", "gold", "stairs+gold", or "frontier" with known=True: the known
+        cells beside an unknown one) answers when `goal` cannot be reached; tier says which answered (0, 1, None = neither; dist is None then).
+        route_key("stairs", "frontier", known=True) is a scripted explorer that sees what the player sees."""
+        key, dist, tier = self.game.route_key(goal, fallback, secrets, known)
+        return key.decode("latin-1"), dist, tier
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

@@ -48,7 +48,7 @@ _INT_FUNCS = (
     "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed", "rg_step_obs_typed",
     "rg_obs_crop_typed", "rg_step_obs_crop_typed",
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-    "rg_path", "rg_path_host",
+    "rg_path", "rg_path_host", "rg_route", "rg_route_host",
 )
 
 
@@ -115,12 +115,13 @@ def load_library():
         "rg_action_mask": [vp, vp, i32, vp, vp, C.c_uint64, C.c_uint64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
         "rg_sample_index": [C.c_uint64, u32, C.c_uint64, u32],
         "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
+        "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-                "rg_sample_index", "rg_path", "rg_path_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -285,6 +286,28 @@ def _path_goals(goal, with_cells=False):
     return PATH_GOALS[goal] | (4 if with_cells else 0)
 
 
+# rg_route: its goal names (RG_GOAL_*; "frontier" = RG_GOAL_FRONTIER, with known=True only), its mode bits, and the guide that is a route of its own
+ROUTE_GOALS = {"stairs": 1, "gold": 2, "stairs+gold": 3, "frontier": 8}
+ROUTE_SECRETS, ROUTE_KNOWN = 1, 2  # RG_ROUTE_*
+ROUTE_NO_TIER = 255
+# guide="explore": (goal, fallback, secrets, known).  known alone: with secrets it would read the LOCKED bit of a door that the player's map shows as a wall
+EXPLORE = ("stairs", "frontier", False, True)
+
+
+def _route_args(goal, fallback=None, secrets=False, known=False, with_cells=False):
+    """(goals, fallback_goals, mode) of rg_route.  goal: a name of ROUTE_GOALS, or None with cells (the caller's cells alone); with cells RG_GOAL_CELL joins
+    `goal`'s word, never the fallback's.  fallback: a name of ROUTE_GOALS or None."""
+    def word(name, what):
+        if not isinstance(name, str) or name not in ROUTE_GOALS:
+            raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(repr(g) for g in ROUTE_GOALS), name))
+        return ROUTE_GOALS[name]
+    goals = 4 if (goal is None and with_cells) else word(goal, "goal") | (4 if with_cells else 0)
+    fb = 0 if fallback is None else word(fallback, "fallback")
+    if ((goals | fb) & 8) and not known:
+        raise ValueError("the goal 'frontier' needs known=True: the frontier is of the player's own map")
+    return goals, fb, (ROUTE_SECRETS if secrets else 0) | (ROUTE_KNOWN if known else 0)
+
+
 class _Handle:
     """Owns one rg_t."""
 
@@ -413,6 +436,25 @@ class _Handle:
         out = np.empty(nbytes, np.uint8)
         self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
         return out[4 * self.n:].copy(), out[:4 * self.n].view(np.int32).copy()
+
+    def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
+        """(keys u8 [n], dist i32 [n], tier u8 [n]) of rg_route (_route_args names the arguments): into the device scratch buffer the handle keeps, one
+        rg_dev_read.  dist -1 = unreachable, tier 255 = neither tier reached the player."""
+        goals, fb, mode = _route_args(goal, fallback, secrets, known)
+        nbytes = self.n * 6
+        if self._mask_dev is None or self._mask_dev[1] < nbytes:
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._mask_dev = (p.value, nbytes)
+        base = self._mask_dev[0]  # dist i32 [n], then keys u8 [n], then tier u8 [n]
+        self.check(self.L.rg_route(self.h, goals, fb, mode, None, C.c_void_p(base), C.c_void_p(base + 4 * self.n), C.c_void_p(base + 5 * self.n)))
+        out = np.empty(nbytes, np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
+        return out[4 * self.n:5 * self.n].copy(), out[:4 * self.n].view(np.int32).copy(), out[5 * self.n:].copy()
 
     def history_keys(self, env, previous=False):
         n = C.c_uint32()
@@ -819,6 +861,13 @@ class GameState:
         keys, dist = self._h.path_keys(goal)
         return bytes(keys[:1]), (None if dist[0] < 0 else int(dist[0]))
 
+    def route_key(self, goal="stairs", fallback=None, secrets=False, known=False):
+        """(key byte as bytes of length 1, distance or None, tier or None): rg_route for this game (not part of the reference's API).  secrets: plan through
+        hidden / locked cells and search beside them; known: plan on the player's own map only (nothing privileged then); fallback: the goal that
+        answers when `goal` is not reached ("frontier" with known=True: the explorer)."""
+        keys, dist, tier = self._h.route_keys(goal, fallback, secrets, known)
+        return bytes(keys[:1]), (None if dist[0] < 0 else int(dist[0])), (None if tier[0] == ROUTE_NO_TIER else int(tier[0]))
+
     def save_state(self):
         """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
         after a load_state dumps the saved episode's keys."""
@@ -886,6 +935,10 @@ class ParallelGameState:
     def path_keys(self, goal="stairs"):
         """(keys numpy u8 [n], dist numpy i32 [n], -1 = unreachable) towards `goal` (not part of the reference's API; rg_path)."""
         return self._h.path_keys(goal)
+
+    def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
+        """(keys numpy u8 [n], dist numpy i32 [n], tier numpy u8 [n]) of rg_route (not part of the reference's API; GameState.route_key names the arguments)."""
+        return self._h.route_keys(goal, fallback, secrets, known)
 
     def dump_config(self, env=0):
         buf = C.create_string_buffer(1 << 16)
