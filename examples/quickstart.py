@@ -132,3 +132,12 @@ for kw in (dict(guide="stairs", guide_secrets=True), dict(guide="explore")):
     print("HipVecRogueEnv(%s): dungeon level %.2f per env after 200 steps, %.1f %% of the envs without a route now"
           % (", ".join("%s=%r" % kv for kv in kw.items()), venv.status[:, 0].float().mean().item(), 100 * (venv.guide_dist < 0).float().mean().item()))
     venv.close()
+
+# 3i. episode accounting and the scout reward on the device: what ended (died / time_limit), the finished episode's return and length, and one point per
+#     map cell seen for the first time on a level -- no host trip until pop_episodes() ---------------------------------------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], max_steps=100, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, scout=True, episode_log=8192, guide="explore")
+total = sum(venv.step_keys(venv.guide_keys)[1].sum() + venv.scout.sum() for t in range(200))  # gold + scout as one reward
+ep = venv.pop_episodes()
+print("HipVecRogueEnv(scout=True): reward + scout %.0f over 200 explorer steps; %d episodes finished (%d died, %d time limits), mean return %.1f, length %.1f, scout %.1f"
+      % (total.item(), len(ep["env"]), (ep["cause"] == 1).sum(), (ep["cause"] == 2).sum(), ep["ret"].mean(), ep["length"].mean(), ep["scout"].mean()))
+venv.close()

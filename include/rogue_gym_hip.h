@@ -317,6 +317,62 @@ int rg_route(rg_t *h, uint32_t goals, uint32_t fallback_goals, uint32_t mode, co
 int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, uint32_t fallback_goals,
                   uint32_t mode, int cell_y, int cell_x, uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out);
 
+/* EPISODE ACCOUNTING AND THE SCOUT REWARD: returns, lengths, depths and end causes of the episodes the stepper ends by itself, and one point per map cell
+ * seen for the first time on a level (NLE's "scout" task), kept on the device beside the stepper.  rg_step rebuilds a finished env in the launch that ends
+ * its episode; afterwards only reward and done = 1 are left of the old game.  This is a pass of its own behind the step (Gymnasium's
+ * RecordEpisodeStatistics, EnvPool's info["episode"]): a handle that does not enable it launches and allocates nothing more.
+ *   Per env: ret f32, len i32, depth i32 (the deepest level the running episode has reported), and -- with RG_EP_SCOUT -- `seen`, a bitmap of
+ *     SB = 16 * ceil(H*W / 128) bytes: bit b of byte j is cell 8 j + b in row-major order y * W + x; bits of cells outside rows 1 .. H-2 (the rows the
+ *     screen draws tiles on) and bits at or past H*W are always 0.  None of it is part of a state record (rg_state_save) or of the compact record.
+ *   A KNOWN cell is one in rows 1 .. H-2 whose word has C_VISIBLE or C_DRAWN: the player's own map, which the state keeps bit-exact with the reference.
+ *   rg_episode_update, once after a step, for the envs that step played (all, or the first n_keys of rg_step_prefix), on the mirrors and the cells as the
+ *     step left them:  ret = ret + reward[e] as one f32 add (the reward mirror: a stair bonus of rg_set_stair_reward is included), len += 1.
+ *     done[e] != 0 (the env has been rebuilt already): time_limit = len >= max_steps, died = !time_limit -- the engine has only these two terminal causes,
+ *       and A DEATH ON THE VERY LAST ALLOWED STEP IS REPORTED AS A TIME LIMIT (after the rebuild the mirrors cannot tell the two apart).  The finished
+ *       episode {ret, len, depth, cause, scout sum} goes to last_return / last_length / last_depth / last_cause and to the log; then ret = 0, len = 0,
+ *       depth = the status mirror's dungeon_level (the new game's), seen = the known cells of the new level, scout[e] = 0: the first view of a new game
+ *       is not something the old episode earned.
+ *     else: a dungeon_level other than the one `seen` belongs to empties `seen` and raises depth; then scout[e] = the number of known cells not in
+ *       `seen`, which join it.  Arriving on a new level pays for what is in view there; a cell that drops off the player's map (leaving a dark room)
+ *       stays in `seen` and is never paid twice.
+ *     It does not guard against being called twice for one step: a second call accounts the mirrors again.
+ *   rg_episode_cut, after the caller rebuilt or overwrote envs (rg_reset, rg_reset_envs, rg_reset_mask, rg_state_load), for those envs: with record != 0
+ *     and len > 0 the running episode is finished as above with cause RG_EP_CUT; in every case the lane is rebased as after a done, except that len is
+ *     taken from the env's step counter (0 after a reset, the saved game's count after a load).  env_ids / k / ids_on_device as rg_reset_envs (host ids
+ *     are range-checked and duplicates refused), or mask_dev as rg_reset_mask; both NULL = every env; both non-NULL is refused.
+ *   rg_episode_enable: what = RG_EP_STATS or RG_EP_STATS | RG_EP_SCOUT; log_cap records of 32 bytes (0 = no log).  Allocates, and rebases every lane
+ *     as a cut without record does.  Refused with a message: a handle created without auto-reset, a handle with config groups, a second enable, another
+ *     `what`, a negative log_cap.
+ *   rg_episode_arrays: device pointers valid until rg_destroy -- ret f32 [N], len / depth i32 [N], died / time_limit u8 [N] (rewritten by every update,
+ *     0 where done is 0), last_return f32 [N], last_length / last_depth i32 [N], last_cause u8 [N] (0 = no episode yet), scout f32 [N] and seen
+ *     u8 [N][SB] (both NULL without RG_EP_SCOUT), seen_bytes = SB.  Every array has 64 envs of slack behind env N-1 that no launch writes.
+ *   The log: a wave that holds finished episodes takes ONE returning atomic for its slots, so the records of one call are contiguous in the buffer, in
+ *     no particular order there; a record that finds the buffer full is dropped and counted.  rg_episode_log_read waits for the stream, copies the
+ *     records appended since the last read to out_host (cap >= log_cap entries, else it is refused and the log stays), sorted by (serial, env), stores
+ *     their number in *n and the number dropped since the last read in *dropped (nullable), and empties the log.  serial = the ordinal of the update
+ *     or cut call since the enable, from 1.
+ *   rg_scout_host (stateless, needs no device): the bitmap rule on ONE grid, `cells` = u16 [height][width] in rg_debug_fetch's layout, seen_inout =
+ *     u8 [SB]: *fresh_out (nullable) = the known cells not in seen_inout, which join it; pad bits are written 0.  Refused, the message read through
+ *     rg_last_error(NULL): cells or seen_inout NULL, sizes out of range.
+ * Update, cut and enable are asynchronous on the handle's stream; they read game state and mirrors only and flush nothing. */
+#define RG_EP_STATS 1u
+#define RG_EP_SCOUT 2u
+#define RG_EP_DIED       1u
+#define RG_EP_TIME_LIMIT 2u
+#define RG_EP_CUT        3u
+typedef struct rg_episode_rec { uint32_t serial; int32_t env; float ret; int32_t length; int32_t depth; uint32_t cause; int32_t scout; uint32_t zero; } rg_episode_rec;
+typedef struct rg_episode_arrays_t {
+    float *ret; int32_t *len; int32_t *depth; uint8_t *died; uint8_t *time_limit;
+    float *last_return; int32_t *last_length; int32_t *last_depth; uint8_t *last_cause;
+    float *scout; uint8_t *seen; int32_t seen_bytes;
+} rg_episode_arrays_t;
+int rg_episode_enable(rg_t *h, uint32_t what, int log_cap);
+int rg_episode_update(rg_t *h);
+int rg_episode_cut(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, const uint8_t *mask_dev, int record);
+int rg_episode_arrays(rg_t *h, rg_episode_arrays_t *out);
+int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint64_t *dropped);
+int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

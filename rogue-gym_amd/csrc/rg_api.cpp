@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include "rg_action_mask.h"
 #include "rg_path.h"
 #include "rg_route.h"
+#include "rg_episode.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -64,6 +66,8 @@ void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, i
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
 void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
                hipStream_t st);
+void rgk_episode(const RgState *S, const RgConfig *c, const RgEpisode *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, int record, uint32_t serial,
+                 hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -151,6 +155,11 @@ struct rg_handle {
     // partial reset (rg_reset_envs / rg_reset_mask): the envs to rebuild, device-resident
     int32_t *reset_list = nullptr;                     // [n]
     uint32_t *reset_cnt = nullptr;                     // [1] entries of reset_list
+    // episode accounting (rg_episode_*; rg_episode.h): off until rg_episode_enable, which allocates the arrays
+    bool ep_on = false;
+    RgEpisode ep = {};
+    uint32_t ep_serial = 0;                            // update / cut calls since the enable
+    int32_t *ep_ids = nullptr;                         // [n] a cut's host-side env ids, uploaded
 };
 
 #define RG_TIMING_MAX 4096
@@ -1211,6 +1220,115 @@ int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, 
     if (dist_out) *dist_out = rg_path_dist(dp);
     if (key_out) *key_out = rg_route_key(dead, dp, gw, (cells[pi] & C_SURF_MASK) == S_STAIR, (gw & RG_GOAL_FRONTIER) && frontier_at(pi), dirs);
     if (tier_out) *tier_out = (uint8_t)tier;
+    return 0;
+}
+// ---- episode accounting and the scout reward (rg_episode.h; k_episode in rg_episode.hip) ----
+int rg_episode_enable(rg_t *h, uint32_t what, int log_cap) {
+    if (!h->sub.empty()) { h->err = "rg_episode_enable: not for a handle with config groups (one handle per config)"; return 1; }
+    if (!h->cfg.auto_reset) { h->err = "rg_episode_enable: the handle was created without auto-reset: its episodes do not end inside rg_step"; return 1; }
+    if (h->ep_on) { h->err = "rg_episode_enable: episode accounting is enabled already"; return 1; }
+    if (what != RG_EP_STATS && what != RG_EP_WHAT_ALL) { h->err = "rg_episode_enable: what must be RG_EP_STATS (1) or RG_EP_STATS | RG_EP_SCOUT (3), got " + std::to_string(what); return 1; }
+    if (log_cap < 0) { h->err = "rg_episode_enable: negative log_cap"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t m = (size_t)h->S.n + RG_EP_SLACK;
+    RgEpisode A = {};
+    if (!dev_alloc(h, &A.ret, m) || !dev_alloc(h, &A.len, m) || !dev_alloc(h, &A.depth, m) || !dev_alloc(h, &A.level, m) || !dev_alloc(h, &A.scout_sum, m) || !dev_alloc(h, &A.died, m) ||
+        !dev_alloc(h, &A.time_limit, m) || !dev_alloc(h, &A.last_return, m) || !dev_alloc(h, &A.last_length, m) || !dev_alloc(h, &A.last_depth, m) || !dev_alloc(h, &A.last_cause, m) ||
+        !dev_alloc(h, &h->ep_ids, (size_t)h->S.n))
+        return 1;
+    A.seen_bytes = rg_ep_seen_bytes(h->S.hw);
+    if (what & RG_EP_SCOUT)
+        if (!dev_alloc(h, &A.scout, m) || !dev_alloc(h, &A.seen, m * (size_t)A.seen_bytes)) return 1;
+    A.log_cap = log_cap;
+    if (log_cap > 0)
+        if (!dev_alloc(h, &A.log, (size_t)log_cap) || !dev_alloc(h, &A.log_cnt, 4)) return 1;
+    h->ep = A;
+    h->ep_on = true;
+    h->ep_serial = 0;
+    // (the allocations were zeroed on the null stream, which the handle's stream may not wait for)
+    HIPCHK(h, hipDeviceSynchronize());
+    rgk_episode(&h->S, &h->cfg, &h->ep, h->S.n, nullptr, nullptr, 1, 0, 0u, h->stream);  // every lane: a cut without record
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+static int episode_on(rg_handle *h, const char *what) {
+    if (!h->ep_on) { h->err = std::string(what) + ": episode accounting is not enabled (rg_episode_enable)"; return 1; }
+    return 0;
+}
+int rg_episode_update(rg_t *h) {
+    if (episode_on(h, "rg_episode_update")) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    rgk_episode(&h->S, &h->cfg, &h->ep, h->S.n_keys, nullptr, nullptr, 0, 0, ++h->ep_serial, h->stream);  // the envs the last step played
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_episode_cut(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, const uint8_t *mask_dev, int record) {
+    if (episode_on(h, "rg_episode_cut")) return 1;
+    if (env_ids && mask_dev) { h->err = "rg_episode_cut: both env_ids and mask_dev are given: a list or a mask, not both"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t *ids = nullptr;
+    int slots = h->S.n;
+    if (env_ids) {
+        if (k < 0 || k > h->S.n) { h->err = "rg_episode_cut: k = " + std::to_string(k) + " env_ids for " + std::to_string(h->S.n) + " envs"; return 1; }
+        if (!ids_on_device) {  // checked before anything is launched (two groups on one lane would race)
+            std::vector<uint8_t> seen((size_t)h->S.n, 0);
+            for (int i = 0; i < k; i++) {
+                const int32_t e = env_ids[i];
+                if (e < 0 || e >= h->S.n) { h->err = "rg_episode_cut: env_ids[" + std::to_string(i) + "] = " + std::to_string(e) + " out of range [0, " + std::to_string(h->S.n) + ")"; return 1; }
+                if (seen[e]) { h->err = "rg_episode_cut: env_ids holds " + std::to_string(e) + " twice"; return 1; }
+                seen[e] = 1;
+            }
+            if (k) HIPCHK(h, hipMemcpyAsync(h->ep_ids, env_ids, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));  // (pageable source: staged before the call returns)
+            ids = h->ep_ids;
+        } else ids = env_ids;
+        slots = k;
+    }
+    rgk_episode(&h->S, &h->cfg, &h->ep, slots, ids, mask_dev, 1, record ? 1 : 0, ++h->ep_serial, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_episode_arrays(rg_t *h, rg_episode_arrays_t *out) {
+    if (episode_on(h, "rg_episode_arrays")) return 1;
+    if (!out) { h->err = "rg_episode_arrays: out is NULL"; return 1; }
+    const RgEpisode &A = h->ep;
+    *out = rg_episode_arrays_t{A.ret, A.len, A.depth, A.died, A.time_limit, A.last_return, A.last_length, A.last_depth, A.last_cause, A.scout, A.seen, A.seen_bytes};
+    return 0;
+}
+int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint64_t *dropped) {
+    if (episode_on(h, "rg_episode_log_read")) return 1;
+    if (!n) { h->err = "rg_episode_log_read: n is NULL"; return 1; }
+    *n = 0;
+    if (dropped) *dropped = 0;
+    if (!h->ep.log) return 0;  // no log: nothing to read
+    if (!out_host || cap < h->ep.log_cap) { h->err = "rg_episode_log_read: out_host must hold the log's capacity, " + std::to_string(h->ep.log_cap) + " records"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    uint32_t cnt = 0;
+    HIPCHK(h, hipMemcpyAsync(&cnt, h->ep.log_cnt, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const uint32_t got = cnt < (uint32_t)h->ep.log_cap ? cnt : (uint32_t)h->ep.log_cap;
+    if (got) HIPCHK(h, hipMemcpy(out_host, h->ep.log, (size_t)got * sizeof(rg_episode_rec), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemsetAsync(h->ep.log_cnt, 0, 4, h->stream));
+    std::sort(out_host, out_host + got, [](const rg_episode_rec &a, const rg_episode_rec &b) { return a.serial != b.serial ? a.serial < b.serial : a.env < b.env; });
+    *n = (int)got;
+    if (dropped) *dropped = cnt - got;
+    return 0;
+}
+int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out) {
+    if (!cells) { g_create_err = "rg_scout_host: cells must not be NULL"; return 1; }
+    if (!seen_inout) { g_create_err = "rg_scout_host: seen_inout must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        g_create_err = "rg_scout_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
+                       std::to_string(height) + ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    const int hw = height * width, sb = rg_ep_seen_bytes(hw);
+    int32_t fresh = 0;
+    for (int j = 0; j < sb; j++) {
+        uint32_t s = seen_inout[j];
+        fresh += __builtin_popcount(rg_ep_fresh(rg_ep_known_byte(cells, j, hw, width), s, false) & 0xffu);
+        seen_inout[j] = (uint8_t)(s & rg_ep_row_bits(j, hw, width));  // (bits that can never count are written 0, whatever the caller passed)
+    }
+    if (fresh_out) *fresh_out = fresh;
     return 0;
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }

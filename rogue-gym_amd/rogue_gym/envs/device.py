@@ -37,7 +37,8 @@ class HipVecRogueEnv:
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
-                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False):
+                 persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False,
+                 episodes: bool = False, scout: bool = False, episode_log: int = 0):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -73,7 +74,17 @@ class HipVecRogueEnv:
         guide="explore" is the explorer that is NOT privileged: it plans on the player's own map only (the cells that are drawn or in view), towards the
         stairs once they are on it, else towards the nearest known cell beside an unknown one, and searches when it stands on such a cell -- a hidden
         passage cell is what stays unknown beside it (rg_route: goals stairs, fallback frontier, mode known).  `self.guide_tier` is a uint8
-        tensor [N]: 0 = the stairs answered, 1 = the frontier, 255 = neither (the key is 's' then); None for every other guide."""
+        tensor [N]: 0 = the stairs answered, 1 = the frontier, 255 = neither (the key is 's' then); None for every other guide.
+
+        episodes (opt-in): episode accounting on the device (rg_episode_update, one small launch behind every step, no host trip).  The stepper rebuilds a
+        finished env inside the step, so `done` and `reward` are all that is left of the old game; with episodes=True these device tensors [N] say the rest:
+        `ep_return` f32, `ep_length` and `ep_depth` i32 of the running episode; `died` and `time_limit` bool, why an env whose `done` is set ended (a death
+        on the very last allowed step is reported as a time limit); `last_return`, `last_length`, `last_depth` and `last_cause` uint8 (1 died, 2 time limit,
+        3 cut by reset() / reset_envs()) of each env's last finished episode.  scout=True (implies episodes): `scout` f32 [N] is the number of map cells the
+        step made known for the first time on the env's level -- NLE's "scout" reward, 0 in the step that starts a new game -- and `seen_bits` uint8 [N, SB]
+        the bitmap behind it (bit b of byte j: cell 8 j + b).  episode_log (> 0, implies episodes): that many finished episodes are kept on the device
+        between two pop_episodes() calls.  Without any of the three every one of these attributes is None and nothing is added to any call.  Not for
+        batches with config groups."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -145,10 +156,72 @@ class HipVecRogueEnv:
         self.guide_tier = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device) if guide == "explore" else None
         self.guide_keys = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
         self.guide_dist = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+        self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         self._encode()
+
+    _EP_NAMES = ("ep_return", "ep_length", "ep_depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen_bits")
+
+    def _episode_setup(self, on, scout, log_cap):
+        torch = self.torch
+        self._episodes, self._ep_log_cap = on, log_cap
+        for k in self._EP_NAMES:
+            setattr(self, k, None)
+        if not on:
+            return
+        if log_cap < 0:
+            raise ValueError("episode_log must be >= 0, got %d" % log_cap)
+        L, h, n = self._h.L, self._h.h, self.num_envs
+        self._h.check(L.rg_episode_enable(h, inner.RG_EP_STATS | (inner.RG_EP_SCOUT if scout else 0), log_cap))
+        a = inner.RgEpisodeArrays()
+        self._h.check(L.rg_episode_arrays(h, C.byref(a)))
+        with torch.cuda.device(self.device):
+            def view(ptr, shape, typestr):
+                return None if not ptr else torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
+            self.ep_return, self.ep_length, self.ep_depth = view(a.ret, (n,), "<f4"), view(a.len, (n,), "<i4"), view(a.depth, (n,), "<i4")
+            self.died, self.time_limit = view(a.died, (n,), "|b1"), view(a.time_limit, (n,), "|b1")
+            self.last_return, self.last_length, self.last_depth = view(a.last_return, (n,), "<f4"), view(a.last_length, (n,), "<i4"), view(a.last_depth, (n,), "<i4")
+            self.last_cause = view(a.last_cause, (n,), "|u1")
+            self.scout, self.seen_bits = view(a.scout, (n,), "<f4"), view(a.seen, (n, a.seen_bytes), "|u1")
+
+    def cut_episodes(self, env_ids=None, mask=None, record=False):
+        """Tell the episode accounting that the caller overwrote envs (load_state / clone_state, which leave it alone): the lanes of env_ids (a list, a numpy
+        array or a device tensor, without duplicates), of mask (a bool / uint8 device tensor [num_envs]) or -- both None -- of every env start anew from the
+        game that stands in them now, `ep_length` from that game's own step counter.  record=True first finishes the running episode of each (if it has
+        played a step) with cause 3, as reset() and reset_envs() do.  Needs episodes=True."""
+        torch = self.torch
+        if not self._episodes:
+            raise ValueError("cut_episodes needs episodes=True")
+        if env_ids is not None and mask is not None:
+            raise ValueError("cut_episodes takes env_ids or mask, not both")
+        L, h = self._h.L, self._h.h
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,):
+                raise ValueError("cut_episodes: mask must be a bool / uint8 tensor [%d] on %s" % (self.num_envs, self.device))
+            mask = mask.contiguous()
+            self._h.check(L.rg_episode_cut(h, None, 0, 0, C.c_void_p(mask.data_ptr()), int(bool(record))))
+            return
+        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
+        if on_dev and torch.unique(_keep).numel() != k:
+            raise ValueError("cut_episodes: duplicate env_ids")
+        if env_ids is not None and k == 0:
+            return
+        self._h.check(L.rg_episode_cut(h, ptr, k, on_dev, None, int(bool(record))))
+
+    def pop_episodes(self):
+        """The episodes finished since the last call, as a dict of numpy arrays in (serial, env) order -- serial (the ordinal of the step, reset or cut since
+        the env was built, from 1), env, ret, length, depth, cause, scout (the episode's scout sum) -- plus `dropped`, the number that found the log full.
+        The only host trip of the accounting: it waits for the stream.  Needs episode_log > 0."""
+        if not self._episodes or self._ep_log_cap <= 0:
+            raise ValueError("pop_episodes needs episode_log > 0")
+        buf = np.zeros(self._ep_log_cap, dtype=np.dtype(inner.EPISODE_REC))
+        n, dropped = C.c_int(0), C.c_uint64(0)
+        self._h.check(self._h.L.rg_episode_log_read(self._h.h, buf.ctypes.data, self._ep_log_cap, C.byref(n), C.byref(dropped)))
+        out = {k: buf[k][:n.value].copy() for k in ("serial", "env", "ret", "length", "depth", "cause", "scout")}
+        out["dropped"] = int(dropped.value)
+        return out
 
     @staticmethod
     def _crop_radii(crop):
@@ -327,6 +400,8 @@ class HipVecRogueEnv:
 
     def reset(self):
         self._h.check(self._h.L.rg_reset(self._h.h))
+        if self._episodes:  # the running episodes end here, cause 3
+            self._h.check(self._h.L.rg_episode_cut(self._h.h, None, 0, 0, None, 1))
         return self._encode()
 
     def reset_envs(self, env_ids=None, mask=None, seeds=None):
@@ -346,6 +421,8 @@ class HipVecRogueEnv:
                     self.num_envs, self.device, "%s %s on %s" % (tuple(mask.shape), mask.dtype, mask.device) if isinstance(mask, torch.Tensor) else type(mask).__name__))
             mask = mask.contiguous()
             self._h.check(L.rg_reset_mask(h, C.c_void_p(mask.data_ptr())))  # (a bool tensor is one byte per element, 0 / 1)
+            if self._episodes:
+                self._h.check(L.rg_episode_cut(h, None, 0, 0, C.c_void_p(mask.data_ptr()), 1))
             return self._encode()
         ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
         if on_dev and torch.unique(_keep).numel() != k:
@@ -363,6 +440,8 @@ class HipVecRogueEnv:
             _keep = np.zeros(1, np.int32)
             ptr, on_dev = C.c_void_p(_keep.ctypes.data), 0
         self._h.check(L.rg_reset_envs(h, ptr, k, on_dev))
+        if self._episodes and k:
+            self._h.check(L.rg_episode_cut(h, ptr, k, on_dev, None, 1))
         return self._encode()
 
     def seed(self, seeds):
@@ -394,6 +473,8 @@ class HipVecRogueEnv:
             self._h.check(self._h.L.rg_step_obs_gray(self._h.h, C.c_void_p(keys.data_ptr()), 1, self.image_setting.status.value, int(self.image_setting.includes_hist),
                                                       C.c_void_p(self.obs.data_ptr())))
             obs = self.obs
+        if self._episodes:  # the accounting of this step, on the mirrors and cells as it left them
+            self._h.check(self._h.L.rg_episode_update(self._h.h))
         return obs, self.reward, self.done
 
     def step(self, actions):
@@ -581,7 +662,8 @@ class HipVecRogueEnv:
     def load_state(self, records, env_ids=None):
         """Restore envs env_ids (default: every env, in order) from state records u8 [k, R] (save_state of this or another batch of the same config,
         seed aside, or RogueEnv.save_state).  A restored env plays out the saved episode; when that ends it resets from its OWN seed.  A record that
-        does not fit leaves its env unchanged and makes check_errors() raise.  Returns the observation batch, re-encoded."""
+        does not fit leaves its env unchanged and makes check_errors() raise.  Returns the observation batch, re-encoded.  The episode accounting
+        (episodes=True) is left alone -- the lanes go on counting as if nothing had happened; cut_episodes() rebases them on the loaded games."""
         torch = self.torch
         if not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.dim() != 2 or records.device != self.device:
             raise ValueError("load_state needs a uint8 tensor [k, record bytes] on %s" % (self.device,))
@@ -595,7 +677,8 @@ class HipVecRogueEnv:
 
     def clone_state(self, src_ids, dst_ids):
         """Copy the states of src_ids into dst_ids (through a scratch record batch, so overlapping id sets are well defined): e.g. one
-        interesting env branched into many lanes, clone_state([17] * 4096, range(4096))."""
+        interesting env branched into many lanes, clone_state([17] * 4096, range(4096)).  As load_state, it leaves the episode accounting alone
+        (cut_episodes())."""
         return self.load_state(self.save_state(src_ids), dst_ids)
 
     def enable_history(self, cap_per_env: int):

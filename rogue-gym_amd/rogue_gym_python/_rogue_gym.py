@@ -38,6 +38,15 @@ class RgDebugState(C.Structure):
     ]
 
 
+class RgEpisodeArrays(C.Structure):
+    """rg_episode_arrays_t (include/rogue_gym_hip.h): device pointers."""
+    _fields_ = [(k, C.c_void_p) for k in ("ret", "len", "depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen")] + [("seen_bytes", C.c_int32)]
+
+
+RG_EP_STATS, RG_EP_SCOUT = 1, 2
+RG_EP_DIED, RG_EP_TIME_LIMIT, RG_EP_CUT = 1, 2, 3
+EPISODE_REC = [("serial", "<u4"), ("env", "<i4"), ("ret", "<f4"), ("length", "<i4"), ("depth", "<i4"), ("cause", "<u4"), ("scout", "<i4"), ("zero", "<u4")]  # rg_episode_rec
+
 _lib = None
 
 _INT_FUNCS = (
@@ -49,6 +58,7 @@ _INT_FUNCS = (
     "rg_obs_crop_typed", "rg_step_obs_crop_typed",
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
+    "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
 )
 
 
@@ -116,12 +126,15 @@ def load_library():
         "rg_sample_index": [C.c_uint64, u32, C.c_uint64, u32],
         "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
         "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
+        "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, C.POINTER(RgEpisodeArrays)],
+        "rg_episode_log_read": [vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)], "rg_scout_host": [vp, i32, i32, vp, C.POINTER(i32)],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-                "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
+                "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
