@@ -141,3 +141,16 @@ ep = venv.pop_episodes()
 print("HipVecRogueEnv(scout=True): reward + scout %.0f over 200 explorer steps; %d episodes finished (%d died, %d time limits), mean return %.1f, length %.1f, scout %.1f"
       % (total.item(), len(ep["env"]), (ep["cause"] == 1).sum(), (ep["cause"] == 2).sum(), ep["ret"].mean(), ep["length"].mean(), ep["scout"].mean()))
 venv.close()
+
+# 3j. the monsters as an entity table and four threat words, kept beside `obs`: what is next to me, where, which letter -- without parsing the image ----------
+ENEMIES = dict(MINI, enemies={"enemies": list(range(12))})
+venv = HipVecRogueEnv([dict(ENEMIES, seed=i) for i in range(4096)], max_steps=100, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0,
+                      monsters="shown", monster_cap=4, action_mask=True)
+for t in range(60):
+    venv.step_keys(venv.sample_keys(seed=1))
+e = int(venv.threat[:, 0].argmax())                      # an env with a monster next to the player
+attackable = venv.threat[:, 2] & (venv.action_mask[:, 1:9].int() << torch.arange(8, device=venv.device)).sum(1)   # the positional mask ANDed with the legal moves
+print("HipVecRogueEnv(monsters='shown'): %.1f %% of the envs have a monster next to the player, %.1f %% can attack one; env %d sees %s"
+      % (100 * (venv.threat[:, 0] > 0).float().mean().item(), 100 * (attackable != 0).float().mean().item(), e,
+         [dict(zip(venv.MONSTER_COLS[:5], (chr(r[0]),) + tuple(r[1:5]))) for r in venv.monsters[e].tolist() if r[0]]))
+venv.close()

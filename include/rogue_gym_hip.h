@@ -373,6 +373,45 @@ int rg_episode_arrays(rg_t *h, rg_episode_arrays_t *out);
 int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint64_t *dropped);
 int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out);
 
+/* MONSTER TABLES AND THREAT WORDS: the nearest monsters of every env as an entity list, and four words that say how close they are.  The monster tables are
+ * device-resident and bit-exact with the reference; this is one small pass behind the step that hands them out in a form a policy, a shaping term or a
+ * teacher can use, without parsing the image.  The rule is stated once in csrc/rg_monsters.h.
+ *   A monster of the env's current level is ALIVE when its slot holds one.  It is SHOWN when a Redraw at this moment would put its letter on the screen
+ *     (RunTime::draw_screen): its row is in 1 .. H-2, its cell is visible or drawn, it is not the player's cell, the cell holds no gold (gold is drawn
+ *     over a monster), and either dx*dx + dy*dy <= 2 or Floor::in_same_room holds (same assigned area and, unless the room is Empty, both cells inside
+ *     the room's rect or both outside it), with dx = x - px, dy = y - py.
+ *   RG_MON_SHOWN lists the shown monsters: what the screen can show.  RG_MON_ALL lists every alive monster of the level and is PRIVILEGED in the same sense
+ *     as rg_path: positions, hit points and wakefulness of monsters the player has not met.
+ *   Order: ascending by (cheb = max(|dx|, |dy|), dx*dx + dy*dy, x<<8|y).  The nearest `cap` (1 .. RG_MON_MAX_CAP) are written as rows of RG_MON_COLS int16,
+ *     16 bytes each: [0] the tile byte the screen shows for the monster's kind ('A'..'Z'; 0 marks an empty row), [1] dx, [2] dy, [3] cheb, [4] 1 if shown
+ *     (always 1 in SHOWN mode), and in ALL mode [5] 1 if the monster is active (awake), [6] min(hp, 32767), [7] the monster's table slot; [5..7] are 0 in
+ *     SHOWN mode.  Rows past the last listed monster are all zero, and every row of every env is written by every call.
+ *   threat i32 [4], always over the SHOWN monsters whatever the mode: [0] how many have cheb == 1; [1] the cheb of the nearest, -1 = none; [2] a positional
+ *     attack mask, bit i set when the cell the move key RG_ACTION_KEYS[1 + i] (h j k l n b u y) aims at holds a shown monster -- positional only, it says
+ *     nothing about the corner rule: AND it with rg_action_mask's answer for legality; [3] the number of monsters that qualify in the call's mode (it may
+ *     exceed cap).
+ *   An env in the Grave modal (RG_FLAG_DEAD) answers an all-zero table and threat {0, -1, 0, 0}.
+ *   The rule reads the GAME STATE, not the screen mirror: it equals the reference's own drawing whenever the reference draws, and between Redraws (a key
+ *     that produced none) it is more current than the image.
+ * rg_monsters: table_dev (nullable) = i16 [n_env][cap][RG_MON_COLS], threat_dev (nullable) = i32 [n_env][4], both 16-byte aligned.  Asynchronous on the
+ *   handle's stream; it reads game state only and flushes nothing.  Config groups and mixed sizes are served, every env's rows at the handle's env index.
+ *   Refused with a message, nothing launched or written: an unknown mode; cap outside 1 .. RG_MON_MAX_CAP while table_dev is given; both outputs NULL; an
+ *   output that is not 16-byte aligned.
+ * rg_monsters_host (stateless, needs no device): the same rule for ONE env on host arrays -- cells u16 [height][width], the player's cell, the dead bit, the
+ *   n_mon monsters and the room_num_x * room_num_y rooms in rg_debug_state's layout (mon_type = tile - 'A'; room_rect packed, room_meta bits 0-1 the kind),
+ *   so that an rg_debug_fetch result feeds it directly.  mon_alive (nullable) = i32 [n_mon], 0 = the entry is skipped; NULL = every entry is alive.  A row's
+ *   slot column is the monster's index in the arrays given.  table_out = i16 [cap][RG_MON_COLS], threat_out = i32 [4], either NULL but not both.  Refusals as
+ *   rg_monsters' (alignment aside), and NULL arrays, sizes, the player's cell or a monster's cell out of range; the message is read through
+ *   rg_last_error(NULL). */
+#define RG_MON_SHOWN   0u
+#define RG_MON_ALL     1u
+#define RG_MON_MAX_CAP 16
+#define RG_MON_COLS    8
+int rg_monsters(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev);
+int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int py, int dead, int n_mon, const int32_t *mon_x, const int32_t *mon_y,
+                     const int32_t *mon_type, const int32_t *mon_active, const int32_t *mon_hp, const int32_t *mon_alive, int room_num_x, int room_num_y,
+                     const uint32_t *room_rect, const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

@@ -20,6 +20,7 @@
 #include "rg_path.h"
 #include "rg_route.h"
 #include "rg_episode.h"
+#include "rg_monsters.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -68,6 +69,7 @@ void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fal
                hipStream_t st);
 void rgk_episode(const RgState *S, const RgConfig *c, const RgEpisode *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, int record, uint32_t serial,
                  hipStream_t st);
+void rgk_monsters(const RgState *S, const RgConfig *c, uint32_t mode, int cap, int16_t *table, int32_t *threat, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -1220,6 +1222,86 @@ int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, 
     if (dist_out) *dist_out = rg_path_dist(dp);
     if (key_out) *key_out = rg_route_key(dead, dp, gw, (cells[pi] & C_SURF_MASK) == S_STAIR, (gw & RG_GOAL_FRONTIER) && frontier_at(pi), dirs);
     if (tier_out) *tier_out = (uint8_t)tier;
+    return 0;
+}
+// ---- monster tables and threat words (rg_monsters.h; k_monsters in rg_monsters.hip) ----
+// mon_args_check: the words of a call, refused before anything is launched or written
+static int mon_args_check(std::string &err, const char *what, uint32_t mode, int cap, bool have_table, bool have_threat, const char *table_name, const char *threat_name) {
+    const std::string w = std::string(what) + ": ";
+    if (mode != RG_MON_SHOWN && mode != RG_MON_ALL) { err = w + "mode must be RG_MON_SHOWN (0) or RG_MON_ALL (1), got " + std::to_string(mode); return 1; }
+    if (!have_table && !have_threat) { err = w + table_name + " and " + threat_name + " are both NULL"; return 1; }
+    if (have_table && (cap < 1 || cap > RG_MON_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_MON_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
+    return 0;
+}
+static int monsters_checked(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {  // every group writes its envs' rows straight into the handle's tensors (RgState::ext), as rg_path does
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, monsters_checked(sh, mode, cap, table_dev, threat_dev));
+        return 0;
+    }
+    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
+    rgk_monsters(&h->S, &h->cfg, mode, cap, table_dev, threat_dev, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_monsters(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
+    if (mon_args_check(h->err, "rg_monsters", mode, cap, table_dev != nullptr, threat_dev != nullptr, "table_dev", "threat_dev")) return 1;
+    if (((uintptr_t)table_dev | (uintptr_t)threat_dev) & 15) { h->err = "rg_monsters: table_dev and threat_dev must be 16-byte aligned device pointers"; return 1; }
+    return monsters_checked(h, mode, cap, table_dev, threat_dev);
+}
+// Every qualifier gets its key, the keys are sorted, the first cap become rows: the plain form of what k_monsters keeps in registers.
+int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int py, int dead, int n_mon, const int32_t *mon_x, const int32_t *mon_y, const int32_t *mon_type,
+                     const int32_t *mon_active, const int32_t *mon_hp, const int32_t *mon_alive, int room_num_x, int room_num_y, const uint32_t *room_rect,
+                     const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out) {
+    std::string &err = g_create_err;
+    if (mon_args_check(err, "rg_monsters_host", mode, cap, table_out != nullptr, threat_out != nullptr, "table_out", "threat_out")) return 1;
+    if (!cells) { err = "rg_monsters_host: cells must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        err = "rg_monsters_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
+              std::to_string(height) + ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    if (px < 0 || py < 0 || px >= width || py >= height) {
+        err = "rg_monsters_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+              std::to_string(height) + " grid";
+        return 1;
+    }
+    if (n_mon < 0 || n_mon > RG_MAX_ROOMS) { err = "rg_monsters_host: n_mon must satisfy 0 <= n_mon <= " + std::to_string(RG_MAX_ROOMS) + ", got " + std::to_string(n_mon); return 1; }
+    if (n_mon > 0 && (!mon_x || !mon_y || !mon_type || !mon_active || !mon_hp)) { err = "rg_monsters_host: mon_x, mon_y, mon_type, mon_active and mon_hp must not be NULL"; return 1; }
+    if (room_num_x < 1 || room_num_y < 1 || room_num_x > width || room_num_y > height || room_num_x * room_num_y > RG_MAX_ROOMS) {
+        err = "rg_monsters_host: room_num_x, room_num_y = (" + std::to_string(room_num_x) + ", " + std::to_string(room_num_y) + ") do not fit the grid";
+        return 1;
+    }
+    if (!room_rect || !room_meta) { err = "rg_monsters_host: room_rect and room_meta must not be NULL"; return 1; }
+    for (int i = 0; i < n_mon; i++) {
+        if (mon_alive && !mon_alive[i]) continue;
+        if (mon_x[i] < 0 || mon_y[i] < 0 || mon_x[i] >= width || mon_y[i] >= height) {
+            err = "rg_monsters_host: monster " + std::to_string(i) + " at (" + std::to_string(mon_x[i]) + ", " + std::to_string(mon_y[i]) + ") is outside the grid";
+            return 1;
+        }
+        if (mon_type[i] < 0 || mon_type[i] > 25) { err = "rg_monsters_host: mon_type[" + std::to_string(i) + "] = " + std::to_string(mon_type[i]) + " is not a tile index 0 .. 25"; return 1; }
+    }
+    RgMonEnv E = {px, py, height, 0, 0, 0, 0, 0, 0, 0, 0, false, false};
+    const int id = rg_mon_area(E, px, py, width, height, room_num_x, room_num_y);
+    if (id >= 0) rg_mon_room(E, room_rect[id], (uint32_t)room_meta[id]);
+    RgMonThreat T;
+    rg_mon_threat_init(T);
+    std::vector<std::pair<uint64_t, uint32_t>> list;
+    for (int i = 0; i < n_mon && !dead; i++) {
+        if (mon_alive && !mon_alive[i]) continue;
+        const int x = mon_x[i], y = mon_y[i];
+        const bool shown = rg_mon_shown(E, cells[y * width + x], x, y), q = mode == RG_MON_ALL || shown;
+        rg_mon_threat_add(T, px, py, x, y, shown, q);
+        if (q) list.emplace_back(rg_mon_key(px, py, x, y, shown, i), rg_mon_pay((uint32_t)('A' + mon_type[i]), mon_active[i] != 0, mon_hp[i]));
+    }
+    std::sort(list.begin(), list.end());
+    if (table_out)
+        for (int r = 0; r < cap; r++) {
+            uint32_t row[4];
+            rg_mon_row(r < (int)list.size() ? list[r].first : RG_MON_EMPTY_KEY, r < (int)list.size() ? list[r].second : 0u, px, py, mode, row);
+            memcpy(table_out + (size_t)r * RG_MON_COLS, row, 16);
+        }
+    if (threat_out) { threat_out[0] = T.adjacent; threat_out[1] = T.nearest; threat_out[2] = T.attack; threat_out[3] = T.count; }
     return 0;
 }
 // ---- episode accounting and the scout reward (rg_episode.h; k_episode in rg_episode.hip) ----

@@ -16,6 +16,9 @@ from rogue_gym_python import _rogue_gym as inner
 from .rogue_env import DungeonType, ImageSetting, RogueEnv, StatusFlag
 
 
+MONSTER_COLS = inner.MONSTER_COLS  # the int16 columns of a row of HipVecRogueEnv.monsters
+
+
 class _DevArray:
     """Zero-copy view of a device buffer owned by the C library (via __cuda_array_interface__)."""
 
@@ -34,11 +37,12 @@ class CropView:
 
 class HipVecRogueEnv:
     ACTIONS = RogueEnv.ACTIONS
+    MONSTER_COLS = MONSTER_COLS
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
                  persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False,
-                 episodes: bool = False, scout: bool = False, episode_log: int = 0):
+                 episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -84,7 +88,16 @@ class HipVecRogueEnv:
         step made known for the first time on the env's level -- NLE's "scout" reward, 0 in the step that starts a new game -- and `seen_bits` uint8 [N, SB]
         the bitmap behind it (bit b of byte j: cell 8 j + b).  episode_log (> 0, implies episodes): that many finished episodes are kept on the device
         between two pop_episodes() calls.  Without any of the three every one of these attributes is None and nothing is added to any call.  Not for
-        batches with config groups."""
+        batches with config groups.
+
+        monsters (opt-in; "shown" or "all"): `self.monsters` is an int16 tensor [N, monster_cap, 8] on the device -- for each env the nearest monster_cap
+        (1 .. 16) monsters as rows of MONSTER_COLS (tile, dx, dy, cheb, shown, active, hp, slot; a row whose tile is 0 is empty), nearest first -- and
+        `self.threat` an int32 tensor [N, 4]: shown monsters next to the player, the distance of the nearest shown one (-1 = none), a bit per move key of
+        ACTIONS[1:9] whose target cell holds a shown monster (positional only: AND it with `action_mask` for legality), and the number of monsters that
+        qualify (rg_monsters).  Both are rewritten in place by everything that refreshes `obs`: one small launch more per step, no host trip.  "shown"
+        lists what a redraw of the screen would show now -- read off the game state, so between two redraws it is more current than the image.  "all"
+        lists every living monster of the level with its hit points and is PRIVILEGED, as the guide is.  It works on every env this class builds, config
+        groups and mixed sizes included.  None: both attributes are None and nothing is added to any call.  monster_table() works either way."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -156,6 +169,10 @@ class HipVecRogueEnv:
         self.guide_tier = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device) if guide == "explore" else None
         self.guide_keys = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
         self.guide_dist = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+        self._mon_args = None if monsters is None else inner._monster_args(monsters, monster_cap)  # (mode, cap) of rg_monsters, None = it is not called
+        with torch.cuda.device(self.device):
+            self.monsters = None if monsters is None else torch.zeros((self.num_envs, self._mon_args[1], len(self.MONSTER_COLS)), dtype=torch.int16, device=self.device)
+            self.threat = None if monsters is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
         self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
@@ -290,6 +307,22 @@ class HipVecRogueEnv:
         if self._guide_route is not None:
             self._h.check(self._h.L.rg_route(self._h.h, self._guide_route[0], self._guide_route[1], self._guide_route[2], None, C.c_void_p(self.guide_dist.data_ptr()),
                                              C.c_void_p(self.guide_keys.data_ptr()), None if self.guide_tier is None else C.c_void_p(self.guide_tier.data_ptr())))
+        if self._mon_args is not None:
+            self._h.check(self._h.L.rg_monsters(self._h.h, self._mon_args[0], self._mon_args[1], C.c_void_p(self.monsters.data_ptr()), C.c_void_p(self.threat.data_ptr())))
+
+    def monster_table(self, mode="shown", cap=4):
+        """(table, threat) on the device (rg_monsters): table int16 [N, cap, 8], the nearest `cap` (1 .. 16) monsters of every env as rows of MONSTER_COLS, nearest
+        first, empty rows zero; threat int32 [N, 4], always about the shown monsters: how many stand next to the player, the distance of the nearest (-1 =
+        none), the positional attack mask over ACTIONS[1:9], and the number of monsters that qualify in `mode`.  mode "shown": what a redraw would show now.
+        mode "all": every living monster of the level, with active, hp and slot filled in -- PRIVILEGED.  No host trip; the states, mirrors and `obs` are left
+        as they are."""
+        torch = self.torch
+        m, cap = inner._monster_args(mode, cap)
+        with torch.cuda.device(self.device):
+            table = torch.empty((self.num_envs, cap, len(self.MONSTER_COLS)), dtype=torch.int16, device=self.device)
+            threat = torch.empty((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        self._h.check(self._h.L.rg_monsters(self._h.h, m, cap, C.c_void_p(table.data_ptr()), C.c_void_p(threat.data_ptr())))
+        return table, threat
 
     def route(self, goal="stairs", fallback=None, secrets=False, known=False, cells=None):
         """(keys, dist, tier) on the device (rg_route): path() with two switches and a fallback goal, without a field.  secrets=True plans THROUGH hidden and

@@ -81,6 +81,10 @@ class ParallelRogueEnv:
         tiers with 255 for neither."""
         return self.game.route_keys(goal, fallback, secrets, known)
 
+    def monster_tables(self, mode: str = "shown", cap: int = 4):
+        """(table int16 [N, cap, 8], threat int32 [N, 4]): RogueEnv.monsters for the whole batch; mode "all" is privileged."""
+        return self.game.monster_tables(mode, cap)
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
         return batch

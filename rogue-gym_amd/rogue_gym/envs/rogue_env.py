@@ -222,6 +222,14 @@ class RogueEnv(Env):
         key, dist, tier = self.game.route_key(goal, fallback, secrets, known)
         return key.decode("latin-1"), dist, tier
 
+    def monsters(self, mode: str = "shown", cap: int = 4):
+        """(table, threat): the nearest `cap` (1 .. 16) monsters as an int16 array [cap, 8] -- columns tile, dx, dy, cheb, shown, active, hp, slot; a row
+        whose tile is 0 is empty -- ordered by distance from the player, and the int32 threat words [4]: shown monsters next to the player, the distance of
+        the nearest shown one (-1 = none), a bit per move key of ACTIONS[1:9] whose target cell holds a shown monster (AND it with action_mask() for
+        legality), and the number of monsters that qualify.  mode "shown" lists what a redraw of the screen would show now.  mode "all" lists every
+        living monster of the level with its hit points and is PRIVILEGED, as path_key is: a teacher or a shaping term, not an observation."""
+        return self.game.monsters(mode, cap)
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

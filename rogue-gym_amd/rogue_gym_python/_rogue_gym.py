@@ -7,6 +7,7 @@ MI355X; this file only marshals.  There is no CPU fallback: importing works anyw
 constructing a GameState without the built library or without a HIP device raises.
 """
 import ctypes as C
+import operator
 import weakref
 import json
 import os
@@ -45,6 +46,10 @@ class RgEpisodeArrays(C.Structure):
 
 RG_EP_STATS, RG_EP_SCOUT = 1, 2
 RG_EP_DIED, RG_EP_TIME_LIMIT, RG_EP_CUT = 1, 2, 3
+RG_MON_SHOWN, RG_MON_ALL, RG_MON_MAX_CAP, RG_MON_COLS = 0, 1, 16, 8
+MONSTER_MODES = {"shown": RG_MON_SHOWN, "all": RG_MON_ALL}
+MONSTER_COLS = ("tile", "dx", "dy", "cheb", "shown", "active", "hp", "slot")   # the int16 columns of a monster-table row (rg_monsters)
+THREAT_COLS = ("adjacent", "nearest", "attack_mask", "count")                  # the int32 threat words
 EPISODE_REC = [("serial", "<u4"), ("env", "<i4"), ("ret", "<f4"), ("length", "<i4"), ("depth", "<i4"), ("cause", "<u4"), ("scout", "<i4"), ("zero", "<u4")]  # rg_episode_rec
 
 _lib = None
@@ -59,6 +64,7 @@ _INT_FUNCS = (
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
     "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
+    "rg_monsters", "rg_monsters_host",
 )
 
 
@@ -128,13 +134,16 @@ def load_library():
         "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
         "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, C.POINTER(RgEpisodeArrays)],
         "rg_episode_log_read": [vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)], "rg_scout_host": [vp, i32, i32, vp, C.POINTER(i32)],
+        "rg_monsters": [vp, u32, i32, vp, vp],
+        "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
     optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
                 "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
-                "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
+                "rg_monsters", "rg_monsters_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -288,6 +297,19 @@ def _mask_keys(keys):
 
 
 PATH_GOALS = {"stairs": 1, "gold": 2, "stairs+gold": 3}  # RG_GOAL_STAIRS, RG_GOAL_GOLD; RG_GOAL_CELL (4) comes with a caller's cells
+
+
+def _monster_args(mode, cap):
+    """(RG_MON_* mode, cap) of rg_monsters for a mode name and a row count."""
+    if not isinstance(mode, str) or mode not in MONSTER_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(repr(m) for m in MONSTER_MODES), mode))
+    try:
+        cap = operator.index(cap)
+    except TypeError:
+        cap = -1
+    if not 1 <= cap <= RG_MON_MAX_CAP:
+        raise ValueError("cap must be an int in 1 .. %d, got %r" % (RG_MON_MAX_CAP, cap))
+    return MONSTER_MODES[mode], cap
 
 
 def _path_goals(goal, with_cells=False):
@@ -449,6 +471,26 @@ class _Handle:
         out = np.empty(nbytes, np.uint8)
         self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
         return out[4 * self.n:].copy(), out[:4 * self.n].view(np.int32).copy()
+
+    def monster_tables(self, mode="shown", cap=4):
+        """(table i16 [n, cap, 8], threat i32 [n, 4]) of rg_monsters (_monster_args names the arguments): into the device scratch buffer the handle keeps,
+        one rg_dev_read."""
+        m, cap = _monster_args(mode, cap)
+        tb = self.n * cap * 16
+        nbytes = tb + self.n * 16
+        if self._mask_dev is None or self._mask_dev[1] < nbytes:
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._mask_dev = (p.value, nbytes)
+        base = self._mask_dev[0]  # table i16 [n][cap][8], then threat i32 [n][4]: both on multiples of 16 bytes
+        self.check(self.L.rg_monsters(self.h, m, cap, C.c_void_p(base), C.c_void_p(base + tb)))
+        out = np.empty(nbytes, np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
+        return out[:tb].view(np.int16).reshape(self.n, cap, RG_MON_COLS).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
 
     def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
         """(keys u8 [n], dist i32 [n], tier u8 [n]) of rg_route (_route_args names the arguments): into the device scratch buffer the handle keeps, one
@@ -881,6 +923,12 @@ class GameState:
         keys, dist, tier = self._h.route_keys(goal, fallback, secrets, known)
         return bytes(keys[:1]), (None if dist[0] < 0 else int(dist[0])), (None if tier[0] == ROUTE_NO_TIER else int(tier[0]))
 
+    def monsters(self, mode="shown", cap=4):
+        """(table numpy i16 [cap, 8], threat numpy i32 [4]): the nearest monsters of this game as rows of MONSTER_COLS and the threat words (not part of the
+        reference's API; rg_monsters -- mode "all" is privileged: it lists monsters the screen does not show)."""
+        table, threat = self._h.monster_tables(mode, cap)
+        return table[0], threat[0]
+
     def save_state(self):
         """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
         after a load_state dumps the saved episode's keys."""
@@ -952,6 +1000,10 @@ class ParallelGameState:
     def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
         """(keys numpy u8 [n], dist numpy i32 [n], tier numpy u8 [n]) of rg_route (not part of the reference's API; GameState.route_key names the arguments)."""
         return self._h.route_keys(goal, fallback, secrets, known)
+
+    def monster_tables(self, mode="shown", cap=4):
+        """(table numpy i16 [n, cap, 8], threat numpy i32 [n, 4]) of rg_monsters (not part of the reference's API; GameState.monsters names the arguments)."""
+        return self._h.monster_tables(mode, cap)
 
     def dump_config(self, env=0):
         buf = C.create_string_buffer(1 << 16)
