@@ -992,6 +992,38 @@ int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int
 }
 // Legal-action masks (rg_action_mask.hip; the rule: rg_action_mask.h).  mask_keys_check: the key list of a call, every refusal before anything is launched;
 // on success `list` holds the n_keys keys the call judges.
+// The readers of game state (rg_action_mask, rg_path, rg_route, rg_monsters): launch(leaf) enqueues one kernel on a handle without groups; on a handle
+// with config groups every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do.
+// Game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are.
+extern "C++" template <class Launch> static int reader_launch(rg_t *h, Launch launch) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, reader_launch(sh, launch));
+        return 0;
+    }
+    launch(h);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+// The grid and the player's cell of a *_host entry: the refusals they share, `what` being the entry's name
+static int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
+    const std::string w = std::string(what) + ": ";
+    if (!cells) { err = w + "cells must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        err = w + "height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" + std::to_string(height) +
+              ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    return 0;
+}
+static int player_check(std::string &err, const char *what, int px, int py, int height, int width) {
+    if (px < 0 || py < 0 || px >= width || py >= height) {
+        err = std::string(what) + ": the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+              std::to_string(height) + " grid";
+        return 1;
+    }
+    return 0;
+}
 static int mask_keys_check(std::string &err, const char *what, const uint8_t *keys, int &n_keys, uint8_t list[RG_MASK_MAX_KEYS]) {
     const std::string w = std::string(what) + ": ";
     if (!keys) { keys = reinterpret_cast<const uint8_t *>(RG_ACTION_KEYS); n_keys = (int)(sizeof(RG_ACTION_KEYS) - 1); }
@@ -1009,15 +1041,7 @@ static int mask_keys_check(std::string &err, const char *what, const uint8_t *ke
     return 0;
 }
 static int action_mask_checked(rg_t *h, const uint8_t *list, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, action_mask_checked(sh, list, n_keys, mask_dev, sample_dev, seed, draw));
-        return 0;
-    }
-    // game state only: the pending render is not flushed, mirrors, flag words and a bound observation tensor stay as they are
-    rgk_action_mask(&h->S, &h->cfg, list, n_keys, mask_dev, sample_dev, seed, draw, h->stream, nullptr, nullptr);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return reader_launch(h, [=](rg_t *l) { rgk_action_mask(&l->S, &l->cfg, list, n_keys, mask_dev, sample_dev, seed, draw, l->stream, nullptr, nullptr); });
 }
 int rg_action_mask(rg_t *h, const uint8_t *keys, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
     uint8_t list[RG_MASK_MAX_KEYS];
@@ -1030,11 +1054,7 @@ int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, in
     uint8_t list[RG_MASK_MAX_KEYS];
     if (mask_keys_check(g_create_err, "rg_action_mask_host", keys, n_keys, list)) return 1;
     if (!cells || !out) { g_create_err = "rg_action_mask_host: cells and out must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || px < 0 || py < 0 || px >= width || py >= height) {
-        g_create_err = "rg_action_mask_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
-                       std::to_string(height) + " grid";
-        return 1;
-    }
+    if (player_check(g_create_err, "rg_action_mask_host", px, py, height, width)) return 1;  // (an empty grid has no cell inside it: the same refusal)
     for (int k = 0; k < n_keys; k++) out[k] = (uint8_t)rg_key_legal(cells, height, width, px, py, dead, list[k]);
     return 0;
 }
@@ -1048,15 +1068,7 @@ static int path_goals_check(std::string &err, const char *what, uint32_t goals) 
     return 0;
 }
 static int path_checked(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group writes its envs' entries straight into the handle's tensors (RgState::ext), as the masks do
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, path_checked(sh, goals, cells_dev, field_dev, dist_dev, key_dev));
-        return 0;
-    }
-    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
-    rgk_path(&h->S, &h->cfg, goals, cells_dev, field_dev, dist_dev, key_dev, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return reader_launch(h, [=](rg_t *l) { rgk_path(&l->S, &l->cfg, goals, cells_dev, field_dev, dist_dev, key_dev, l->stream); });
 }
 int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
     if (path_goals_check(h->err, "rg_path", goals)) return 1;
@@ -1072,17 +1084,7 @@ int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, i
                  uint8_t *key_out) {
     if (path_goals_check(g_create_err, "rg_path_host", goals)) return 1;
     if (!field_out && !dist_out && !key_out) { g_create_err = "rg_path_host: field_out, dist_out and key_out are all NULL"; return 1; }
-    if (!cells) { g_create_err = "rg_path_host: cells must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
-        g_create_err = "rg_path_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
-                       std::to_string(height) + ", " + std::to_string(width) + ")";
-        return 1;
-    }
-    if (px < 0 || py < 0 || px >= width || py >= height) {
-        g_create_err = "rg_path_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
-                       std::to_string(height) + " grid";
-        return 1;
-    }
+    if (grid_check(g_create_err, "rg_path_host", cells, height, width) || player_check(g_create_err, "rg_path_host", px, py, height, width)) return 1;
     const int hw = height * width;
     std::vector<uint16_t> D((size_t)hw, (uint16_t)RG_PATH_INF);
     std::vector<int> fifo;
@@ -1139,15 +1141,7 @@ static int route_args_check(std::string &err, const char *what, uint32_t goals, 
     return 0;
 }
 static int route_checked(rg_t *h, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group writes its envs' entries straight into the handle's tensors (RgState::ext), as rg_path does
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, route_checked(sh, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev));
-        return 0;
-    }
-    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
-    rgk_route(&h->S, &h->cfg, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return reader_launch(h, [=](rg_t *l) { rgk_route(&l->S, &l->cfg, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev, l->stream); });
 }
 int rg_route(rg_t *h, uint32_t goals, uint32_t fallback_goals, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
     if (route_args_check(h->err, "rg_route", goals, fallback_goals, mode, cells_dev != nullptr, "cells_dev")) return 1;
@@ -1160,17 +1154,7 @@ int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, 
                   uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out) {
     if (route_args_check(g_create_err, "rg_route_host", goals, fallback_goals, mode, true, "cells")) return 1;
     if (!field_out && !dist_out && !key_out && !tier_out) { g_create_err = "rg_route_host: field_out, dist_out, key_out and tier_out are all NULL"; return 1; }
-    if (!cells) { g_create_err = "rg_route_host: cells must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
-        g_create_err = "rg_route_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
-                       std::to_string(height) + ", " + std::to_string(width) + ")";
-        return 1;
-    }
-    if (px < 0 || py < 0 || px >= width || py >= height) {
-        g_create_err = "rg_route_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
-                       std::to_string(height) + " grid";
-        return 1;
-    }
+    if (grid_check(g_create_err, "rg_route_host", cells, height, width) || player_check(g_create_err, "rg_route_host", px, py, height, width)) return 1;
     const int hw = height * width, pi = py * width + px;
     auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < width && y < height && !rg_route_known(cells[y * width + x], y * width + x == pi); };
     auto frontier_at = [&](int i) {
@@ -1234,15 +1218,7 @@ static int mon_args_check(std::string &err, const char *what, uint32_t mode, int
     return 0;
 }
 static int monsters_checked(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group writes its envs' rows straight into the handle's tensors (RgState::ext), as rg_path does
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, monsters_checked(sh, mode, cap, table_dev, threat_dev));
-        return 0;
-    }
-    // game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are
-    rgk_monsters(&h->S, &h->cfg, mode, cap, table_dev, threat_dev, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return reader_launch(h, [=](rg_t *l) { rgk_monsters(&l->S, &l->cfg, mode, cap, table_dev, threat_dev, l->stream); });
 }
 int rg_monsters(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
     if (mon_args_check(h->err, "rg_monsters", mode, cap, table_dev != nullptr, threat_dev != nullptr, "table_dev", "threat_dev")) return 1;
@@ -1255,17 +1231,7 @@ int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int p
                      const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out) {
     std::string &err = g_create_err;
     if (mon_args_check(err, "rg_monsters_host", mode, cap, table_out != nullptr, threat_out != nullptr, "table_out", "threat_out")) return 1;
-    if (!cells) { err = "rg_monsters_host: cells must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
-        err = "rg_monsters_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
-              std::to_string(height) + ", " + std::to_string(width) + ")";
-        return 1;
-    }
-    if (px < 0 || py < 0 || px >= width || py >= height) {
-        err = "rg_monsters_host: the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
-              std::to_string(height) + " grid";
-        return 1;
-    }
+    if (grid_check(err, "rg_monsters_host", cells, height, width) || player_check(err, "rg_monsters_host", px, py, height, width)) return 1;
     if (n_mon < 0 || n_mon > RG_MAX_ROOMS) { err = "rg_monsters_host: n_mon must satisfy 0 <= n_mon <= " + std::to_string(RG_MAX_ROOMS) + ", got " + std::to_string(n_mon); return 1; }
     if (n_mon > 0 && (!mon_x || !mon_y || !mon_type || !mon_active || !mon_hp)) { err = "rg_monsters_host: mon_x, mon_y, mon_type, mon_active and mon_hp must not be NULL"; return 1; }
     if (room_num_x < 1 || room_num_y < 1 || room_num_x > width || room_num_y > height || room_num_x * room_num_y > RG_MAX_ROOMS) {
@@ -1398,11 +1364,7 @@ int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint
 int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out) {
     if (!cells) { g_create_err = "rg_scout_host: cells must not be NULL"; return 1; }
     if (!seen_inout) { g_create_err = "rg_scout_host: seen_inout must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
-        g_create_err = "rg_scout_host: height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" +
-                       std::to_string(height) + ", " + std::to_string(width) + ")";
-        return 1;
-    }
+    if (grid_check(g_create_err, "rg_scout_host", cells, height, width)) return 1;
     const int hw = height * width, sb = rg_ep_seen_bytes(hw);
     int32_t fresh = 0;
     for (int j = 0; j < sb; j++) {

@@ -3,67 +3,13 @@
 //   k_path<WN, GS, FIELD> : one wave per 64 / GS consecutive envs; lane y of a group of GS lanes owns grid row y of the group's env as bit masks
 //
 // A translation unit of its own, as rg_action_mask.hip is, so that the code generation of the step and observation kernels -- their register counts are
-// pinned by the resource tests -- is not touched by anything here.  The rule itself is rg_path.h's, shared with the host entry point.
+// pinned by the resource tests -- is not touched by anything here.  The rule itself is rg_path.h's, shared with the host entry point; the bit rows
+// and the choice of instance are rg_rows.h's, shared with rg_route.hip.
 // The field is PRIVILEGED (rg_path.h): it sees stairs, gold and passages the player has not discovered.
 #include "rg_device.h"
 #include "rg_path.h"
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-// one-lane DPP shifts (rg_kernels.hip's, copied: that file is not edited from here).  Whole wave: lane i <- lane i -+ 1 ...
-static __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }  // lane i <- lane i-1
-static __device__ __forceinline__ uint32_t wave_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false); }  // lane i <- lane i+1
-// ... and inside a DPP row of 16 lanes, zeros shifted in at the row's ends (bound_ctrl): with H <= 16 a group IS a DPP row, and "no neighbour" is free
-static __device__ __forceinline__ uint32_t row_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); }
-static __device__ __forceinline__ uint32_t row_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true); }
-
-// a grid row as WN 32-bit words, cell x = bit x & 31 of word x >> 5
-template <int WN> struct Row { uint32_t w[WN]; };
-template <int WN> static __device__ __forceinline__ Row<WN> r_zero() {
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = 0u;
-    return r;
-}
-template <int WN> static __device__ __forceinline__ Row<WN> r_shl1(const Row<WN> &a) {  // cell x-1 -> x
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = (a.w[k] << 1) | (k > 0 ? a.w[k > 0 ? k - 1 : 0] >> 31 : 0u);
-    return r;
-}
-template <int WN> static __device__ __forceinline__ Row<WN> r_shr1(const Row<WN> &a) {  // cell x+1 -> x
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = (a.w[k] >> 1) | (k + 1 < WN ? a.w[k + 1 < WN ? k + 1 : k] << 31 : 0u);
-    return r;
-}
-// the same masks of the row above (UP: lane - 1) or below; ROW16: a group is a DPP row, else a select keeps the groups (and the wave's ends) apart
-template <int WN, bool ROW16, bool UP> static __device__ __forceinline__ Row<WN> r_neighbour(const Row<WN> &a, bool there) {
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) {
-        if (ROW16) r.w[k] = UP ? row_shr1(a.w[k]) : row_shl1(a.w[k]);
-        else { const uint32_t v = UP ? wave_shr1(a.w[k]) : wave_shl1(a.w[k]); r.w[k] = there ? v : 0u; }
-    }
-    return r;
-}
-// the player's cell as (word, bit of that word); pw = -1: not in my row
-struct Spot { int pw; uint32_t pb; };
-template <int WN> static __device__ __forceinline__ bool r_at(const Row<WN> &a, const Spot &p) {  // is the spot's bit set in a?  (a select per word)
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < WN; k++) v |= p.pw == k ? a.w[k] : 0u;
-    return (v & p.pb) != 0;
-}
-template <int WN> static __device__ __forceinline__ void r_set(Row<WN> &a, int x, uint32_t bit) {  // a |= bit << x: a select per word, never an indexed word
-#pragma unroll
-    for (int k = 0; k < WN; k++) a.w[k] |= ((x >> 5) == k ? bit : 0u) << (x & 31);
-}
-
-template <int WN> static __device__ __forceinline__ void r_put(Row<WN> &a, int x, bool v) {  // bit x of a = v
-#pragma unroll
-    for (int k = 0; k < WN; k++) a.w[k] = (a.w[k] & ~(((x >> 5) == k ? 1u : 0u) << (x & 31))) | (((x >> 5) == k && v ? 1u : 0u) << (x & 31));
-}
+#include "rg_rows.h"
 
 // one cell word -> its bits of the three row masks (rg_path.h: the rule), as a cell that is neither the player's nor the caller's: those two are
 // judged again, on their own, once the row is in
@@ -326,20 +272,10 @@ static void launch_path(const RgState *S, const RgConfig *c, uint32_t goals, con
         hipLaunchKernelGGL((k_path<WN, GS, false>), dim3(blocks), dim3(WAVE), 0, st, S->p_pos, S->flags, S->cell, S->ext, S->n, W, H, goals, gcell, field, dist, key);
     }
 }
-template <int WN>
-static void launch_path_h(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st) {
-    if (c->height <= 16) launch_path<WN, 16>(S, c, goals, gcell, field, dist, key, st);
-    else if (c->height <= 32) launch_path<WN, 32>(S, c, goals, gcell, field, dist, key, st);
-    else launch_path<WN, 64>(S, c, goals, gcell, field, dist, key, st);
-}
 extern "C" {
 // goals: a non-empty subset of RG_GOAL_*; gcell: needed iff RG_GOAL_CELL; field / dist / key: any may be NULL (checked by the caller)
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st) {
     if (S->n <= 0) return;
-    const int W = (int)c->width;  // <= RG_MAX_W = 160 = 5 words
-    if (W <= 32) launch_path_h<1>(S, c, goals, gcell, field, dist, key, st);
-    else if (W <= 64) launch_path_h<2>(S, c, goals, gcell, field, dist, key, st);
-    else if (W <= 96) launch_path_h<3>(S, c, goals, gcell, field, dist, key, st);
-    else launch_path_h<5>(S, c, goals, gcell, field, dist, key, st);
+    rows_dispatch((int)c->width, (int)c->height, [&](auto wn, auto gs) { launch_path<decltype(wn)::value, decltype(gs)::value>(S, c, goals, gcell, field, dist, key, st); });
 }
 }

@@ -3,58 +3,12 @@
 //   k_route<WN, GS> : one wave per 64 / GS consecutive envs; lane y of a group of GS lanes owns grid row y of the group's env as bit masks
 //
 // Shaped like rg_path.hip's keys-only pass, as a translation unit of its own so that nothing here touches the code generation of the kernels whose
-// register counts the resource tests pin.  The rule itself is rg_route.h's, shared with the host entry point.
+// register counts the resource tests pin.  The rule itself is rg_route.h's, shared with the host entry point; the bit rows and the choice of instance
+// are rg_rows.h's, shared with rg_path.hip.
 #include "rg_device.h"
 #include "rg_route.h"
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-// one-lane DPP shifts and the row helpers (rg_path.hip's, repeated: that file is not edited from here)
-static __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }  // lane i <- lane i-1
-static __device__ __forceinline__ uint32_t wave_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false); }  // lane i <- lane i+1
-static __device__ __forceinline__ uint32_t row_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); }
-static __device__ __forceinline__ uint32_t row_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true); }
-
-template <int WN> struct Row { uint32_t w[WN]; };
-template <int WN> static __device__ __forceinline__ Row<WN> r_zero() {
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = 0u;
-    return r;
-}
-template <int WN> static __device__ __forceinline__ Row<WN> r_shl1(const Row<WN> &a) {  // cell x-1 -> x
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = (a.w[k] << 1) | (k > 0 ? a.w[k > 0 ? k - 1 : 0] >> 31 : 0u);
-    return r;
-}
-template <int WN> static __device__ __forceinline__ Row<WN> r_shr1(const Row<WN> &a) {  // cell x+1 -> x
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) r.w[k] = (a.w[k] >> 1) | (k + 1 < WN ? a.w[k + 1 < WN ? k + 1 : k] << 31 : 0u);
-    return r;
-}
-// the same masks of the row above (UP: lane - 1) or below; ROW16: a group is a DPP row, else a select keeps the groups (and the wave's ends) apart
-template <int WN, bool ROW16, bool UP> static __device__ __forceinline__ Row<WN> r_neighbour(const Row<WN> &a, bool there) {
-    Row<WN> r;
-#pragma unroll
-    for (int k = 0; k < WN; k++) {
-        if (ROW16) r.w[k] = UP ? row_shr1(a.w[k]) : row_shl1(a.w[k]);
-        else { const uint32_t v = UP ? wave_shr1(a.w[k]) : wave_shl1(a.w[k]); r.w[k] = there ? v : 0u; }
-    }
-    return r;
-}
-struct Spot { int pw; uint32_t pb; };  // the player's cell as (word, bit of that word); pw = -1: not in my row
-template <int WN> static __device__ __forceinline__ bool r_at(const Row<WN> &a, const Spot &p) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < WN; k++) v |= p.pw == k ? a.w[k] : 0u;
-    return (v & p.pb) != 0;
-}
-template <int WN> static __device__ __forceinline__ void r_put(Row<WN> &a, int x, bool v) {  // bit x of a = v
-#pragma unroll
-    for (int k = 0; k < WN; k++) a.w[k] = (a.w[k] & ~(((x >> 5) == k ? 1u : 0u) << (x & 31))) | (((x >> 5) == k && v ? 1u : 0u) << (x & 31));
-}
+#include "rg_rows.h"
 
 // the five row masks of the rule (rg_route.h): ps = pass, ck = corner, kn = known, g0 / g1 = the goals of the two tiers that a cell word decides
 // alone (the frontier joins them once every row is in)
@@ -259,22 +213,13 @@ static void launch_route(const RgState *S, const RgConfig *c, uint32_t goals, ui
     hipLaunchKernelGGL((k_route<WN, GS>), dim3(blocks), dim3(WAVE), 0, st, S->p_pos, S->flags, S->cell, S->ext, S->n, (int)c->width, (int)c->height, goals, fallback, mode, gcell,
                        dist, key, tier);
 }
-template <int WN>
-static void launch_route_h(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
-                           hipStream_t st) {
-    if (c->height <= 16) launch_route<WN, 16>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-    else if (c->height <= 32) launch_route<WN, 32>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-    else launch_route<WN, 64>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-}
 extern "C" {
 // goals / fallback / mode: checked by the caller (rg_route); gcell: needed iff either goal word has RG_GOAL_CELL; dist / key / tier: any may be NULL
 void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
                hipStream_t st) {
     if (S->n <= 0) return;
-    const int W = (int)c->width;  // <= RG_MAX_W = 160 = 5 words
-    if (W <= 32) launch_route_h<1>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-    else if (W <= 64) launch_route_h<2>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-    else if (W <= 96) launch_route_h<3>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
-    else launch_route_h<5>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
+    rows_dispatch((int)c->width, (int)c->height, [&](auto wn, auto gs) {
+        launch_route<decltype(wn)::value, decltype(gs)::value>(S, c, goals, fallback, mode, gcell, dist, key, tier, st);
+    });
 }
 }
