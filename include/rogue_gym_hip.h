@@ -141,8 +141,9 @@ int rg_done(rg_t *h, uint8_t **dev);
 int rg_set_stair_reward(rg_t *h, float bonus);
 
 /* rg_step_obs_gray on the plain f32 gray image of a 512-cell grid stepped by the capped W <= 32 kernel (no status planes, no history plane, no config
- * groups, no bound tensor) lets the step waves that finish early write their envs' images themselves and a residual pass the rest (DESIGN.md section 4:
- * the tail encode).  on = 0: the step kernel and the full observation pass one after the other, as on every other handle -- the same bits either way (A/B
+ * groups, no bound tensor) streams every env's image from the screen mirror in helper blocks of the step launch, beside the turns, and a fix-up pass
+ * behind it re-encodes the image lines the turns touched and draws the Redraw envs (the pre-streamed encode).  on = 0: the step
+ * kernel and the full observation pass one after the other, as on every other handle -- the same bits either way (A/B
  * runs, twin-handle tests).  Default: on.  The Python binding calls it with 0 for a handle created while ROGUE_GYM_HIP_NO_TAIL_ENCODE=1 is set. */
 int rg_tail_encode(rg_t *h, int on);
 

@@ -55,6 +55,7 @@ int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, 
 int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st);
 int rgk_obs_tail_capable(const RgState *S, const RgConfig *c);
 int rgk_step_tail_capable(const RgConfig *c);
+int rgk_step_enc_helpers(int n, int want);
 void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any, hipStream_t st, hipEvent_t ev0,
                   hipEvent_t ev1);
@@ -78,10 +79,9 @@ void rgk_reset_compact(const uint8_t *mask, int n, int32_t *list, uint32_t *cnt,
 void rgk_build_list(const RgState *S, const RgConfig *c, const int32_t *list, const uint32_t *cnt, uint8_t *mark, hipStream_t st);
 }
 
-// RgState::enc_cut: step waves that reach their tail within 40 us of their start encode their envs' images there, later ones leave them to k_obs_resid.
-// On the headline batch the first waves end at ~33 us, half of them by ~41 us and the last at ~55 us; the stream of the early ones runs beside the turns of
-// the late ones, the rest of it beside the residual pass's Redraw chains.  Swept on one box, 27 .. 52 us and none: profiles/r09_experiments.txt.
-#define RG_ENC_CUT_TICKS 4000u
+// RgState::enc_delay: the helper blocks of rg_step_obs_gray's step launch start streaming 25 us into the launch, when the turns' first load rounds are over
+// (rg_kernels.hip enc_helper).  Swept 0 .. 40 us with 128 .. 768 helpers on one box: profiles/r10_experiments.txt.
+#define RG_ENC_DELAY_TICKS 2500u
 #define RG_TIMED_KERNELS 5   // k_step, k_render, k_obs (or the unfused encode), k_build, k_regen
 struct rg_handle {
     RgParsed parsed;             // config of env 0 (all envs agree except for the seed)
@@ -110,9 +110,11 @@ struct rg_handle {
     // rg_obs_bind: the caller's standing observation tensor and whether its contents are the current screens of every env up to the SCR_CHANGED / REDRAW flags
     float *bound_out = nullptr; int bound_kind = 0; bool bound_valid = false;
     int32_t *obs_list_mem = nullptr; uint32_t *obs_cnt_mem = nullptr; float *gray_lut_mem = nullptr;
-    // the tail encode (rg_state.h enc_out): rg_step_obs_gray's step launch writes the images of the envs it leaves without a Redraw itself, the pass behind it the rest.
-    // Whether it applies is decided when the handle is created (the grid and step-kernel class); rg_tail_encode(h, 0) keeps the two full passes; armed per call.
+    // the pre-streamed encode (rg_state.h enc_out): helper blocks of rg_step_obs_gray's step launch stream every env's image beside the turns, the pass behind it
+    // fixes up the lines the turns touched and draws the Redraws.  Whether it applies is decided when the handle is created (the grid and step-kernel class);
+    // rg_tail_encode(h, 0) keeps the two full passes; armed per call.
     bool tail_enc = false, tail_enc_off = false;
+    int enc_helpers = 0;   // helper blocks per launch (rgk_step_enc_helpers); 0: none, the pass encodes every env
     int bound_steps = 0;   // k_step launches since the bound tensor was last written: its in-place pass works from the list of exactly ONE
     int stair_gen = 0;           // producers of the stair set launched so far (k_build, k_step, the debug descent; rg_state.h)
     float *obs_scratch = nullptr;  // rg_obs_host: device-side observation buffer, kept between calls
@@ -324,12 +326,16 @@ static int create_homog(const RgParsed &parsed, const EnvSeed *seeds, int n_env,
     if (ok && nr <= RG_OBS_MAX_ROOMS) ok = dev_alloc(h, &S.obs_rec, n * (size_t)RG_OBS_REC_WORDS(nr));
     if (ok && nr <= RG_OVL_MAX && getenv("ROGUE_GYM_HIP_NO_MIRROR_UPDATE") == nullptr)  // (the A side: every Redraw drawn from the tiles by the observation pass)
         ok = dev_alloc(h, &S.ovl, (nr + 1) * n) && hipMemset(S.ovl, 0xff, (nr + 1) * n * 2) == hipSuccess;
-    {   // the tail encode: the capped W <= 32 step kernel on a grid of exactly 512 cells (rg_kernels.hip rgk_step_tail_capable) whose Redraws the turn and the stream pass handle
+    {   // the pre-streamed encode: the capped W <= 32 step kernel on a grid of exactly 512 cells (rg_kernels.hip rgk_step_tail_capable) whose Redraws the turn and the stream pass handle
         if (ok && rgk_step_tail_capable(&h->cfg) && S.ovl && S.obs_rec) {
-            ok = dev_alloc(h, &S.enc_stamp, n) && ensure_gray_lut(h) == 0;
+            ok = dev_alloc(h, &S.enc_rows, n) && ensure_gray_lut(h) == 0;
             h->tail_enc = ok;
-            S.enc_cut = RG_ENC_CUT_TICKS;
-            if (const char *ev = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_CUT")) S.enc_cut = (uint32_t)atoi(ev);  // (development: the sweep; 0 = every wave leaves its envs to the pass)
+            // (development: ROGUE_GYM_HIP_ENC_HELPERS = that many helper blocks, ROGUE_GYM_HIP_ENC_DELAY = their start delay in 100 MHz ticks -- the sweeps;
+            // ROGUE_GYM_HIP_ENC_CUT = 0: no helper blocks, every env's line mask is all ones and the pass re-encodes everything; any other value: as without it)
+            const char *hv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_HELPERS"), *dv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_DELAY"), *cv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_CUT");
+            h->enc_helpers = rgk_step_enc_helpers((int)n, hv ? atoi(hv) : 0);
+            if (cv && atoi(cv) == 0) h->enc_helpers = 0;
+            S.enc_delay = dv ? (uint32_t)atoi(dv) : RG_ENC_DELAY_TICKS;
         }
     }
     h->spares = auto_reset != 0 && getenv("ROGUE_GYM_HIP_NO_SPARES") == nullptr;
@@ -633,18 +639,17 @@ int rg_reset(rg_t *h) {
 static int obs_common(rg_t *h, uint32_t status_flag, int with_hist, int kind, float *out_dev);
 int rg_step(rg_t *h, const uint8_t *keys, int keys_on_device) { return rg_step_prefix(h, keys, h->S.n, keys_on_device); }
 int rg_step_obs_gray(rg_t *h, const uint8_t *keys, int keys_on_device, uint32_t status_flag, int with_hist, float *out_dev) {
-    // The tail encode: the plain f32 gray image of an ordinary handle without a bound tensor, where rgk_obs would stream it (k_obs_stream) and the step is the
-    // capped W <= 32 kernel's -- this launch's waves write the images of the envs they leave without a Redraw, k_obs_resid the others.  Armed for this launch
-    // only: rg_step alone, and every observation call on its own, are what they were.
+    // The pre-streamed encode: the plain f32 gray image of an ordinary handle without a bound tensor, where rgk_obs would stream it (k_obs_stream) and the step is
+    // the capped W <= 32 kernel's -- this launch's helper blocks stream every env's image beside the turns, k_obs_resid fixes up the lines the turns touched and
+    // draws the Redraws.  Armed for this launch only: rg_step alone, and every observation call on its own, are what they were.
     const bool enc = h->tail_enc && !h->tail_enc_off && h->sub.empty() && (status_flag & 0x1ffu) == 0 && !with_hist && !h->bound_out && out_dev && rgk_obs_tail_capable(&h->S, &h->cfg);
     if (enc) {
         h->S.enc_out = out_dev;
-        h->S.enc_step = (uint32_t)(h->step_count % 0xffffffffull) + 1u;  // (never 0.  step_count only grows -- rg_reset and rg_state_load leave it -- so an env's older stamps are older
-                                                                          // launches' and differ from this one; the value comes round again after 2^32 - 1 launches, by when the env would
-                                                                          // have to have gone unstamped for every one of them)
+        h->S.enc_helpers = h->enc_helpers;
     }
     const int rc = rg_step_prefix(h, keys, h->S.n, keys_on_device);
     h->S.enc_out = nullptr;
+    h->S.enc_helpers = 0;
     if (rc) return 1;
     if (!enc) return obs_common(h, status_flag, with_hist, 0, out_dev);
     {
@@ -780,7 +785,7 @@ int rg_set_stair_reward(rg_t *h, float bonus) {
 }
 
 int rg_tail_encode(rg_t *h, int on) {
-    h->tail_enc_off = on == 0;  // (a handle the tail encode does not apply to takes the two passes either way)
+    h->tail_enc_off = on == 0;  // (a handle the pre-streamed encode does not apply to takes the two passes either way)
     for (rg_handle *sh : h->sub) sh->tail_enc_off = on == 0;
     return 0;
 }
@@ -836,7 +841,7 @@ static uint32_t host_tile_to_sym(uint32_t t) {
     }
 }
 // RgState::gray_lut: the value the observation pass encodes a glyph to (rg_obs.hip `lutf`: the same single IEEE division), for the step kernels that write
-// gray pixels themselves (a bound gray tensor's mirror update, the tail encode)
+// gray pixels themselves (a bound gray tensor's mirror update, the pre-streamed encode)
 static int ensure_gray_lut(rg_handle *h) {
     if (!h->gray_lut_mem) {
         float lut[128];

@@ -2393,8 +2393,9 @@ __device__ __forceinline__ uint32_t base_glyph(const RgConfig &c, uint32_t v, in
 #define OVL_NONE 0xffffu
 // Returns false -- nothing written -- when a cell it would have to write lies outside the window: its tile is not at hand, and a load here would wait for every
 // store of the turn; the Redraw then goes to the observation pass as before.
-template <bool BND>  // BND: the handle has a bound observation tensor (rg_obs_bind) -- a step-kernel instance of its own, so that the ordinary one carries none of it
-__device__ __forceinline__ bool mirror_update(const RgState &S, const RgConfig &c, const Env &E, const Win &w, uint32_t react, int rid0) {
+// ENC: the launch pre-streams the gray images (enc_helper) -- every put() adds the image line of its cell, idx >> 5 (32 cells = one 128-byte line), to `rows`
+template <bool BND, bool ENC = false>  // BND: the handle has a bound observation tensor (rg_obs_bind) -- a step-kernel instance of its own, so that the ordinary one carries none of it
+__device__ __forceinline__ bool mirror_update(const RgState &S, const RgConfig &c, const Env &E, const Win &w, uint32_t react, int rid0, uint32_t &rows) {
     const int W = c.width, nrooms = c.room_num_x * c.room_num_y, n = E.n;
     // (the env index through an opaque move: the addresses below are then computed HERE -- left alone, the compiler computes `S.ovl + ... + e`, `S.hist + e * hw`
     // at the top of the kernel, spills them, and reloads them here one by one, each reload waiting for every store the turn has issued: 5 us per wave)
@@ -2407,6 +2408,7 @@ __device__ __forceinline__ bool mirror_update(const RgState &S, const RgConfig &
     const __attribute__((address_space(3))) float *lutg = (const __attribute__((address_space(3))) float *)(g_smem + STEP_LDS_LUT);
     auto put = [&](int idx, uint32_t g) {
         scr[idx] = (uint8_t)g;
+        if constexpr (ENC) rows |= 1u << (idx >> 5);
         if constexpr (BND) { if (og) og[idx] = lutg[g & 0x7fu]; }
     };
     // (the lane's LDS columns from the lane id, here: a pointer carried from the top of the wave is one more spilled register to reload)
@@ -2604,46 +2606,50 @@ __device__ __forceinline__ void take_spares(const RgState &S, const RgState *__r
     if (taken && !(S.keep_spares && S.reseed[e] == 0)) __hip_atomic_store(&S.sp_ready[es], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The tail encode (k_step_w32<false, true>; rg_state.h enc_out): the wave writes the f32 gray images of its own envs at the very end of its turn, while
-// slower waves are still playing -- the observation pass's 134 MB stream starts when the first waves end instead of when the last one does.  Lane `encl`:
-// the env played this key and its final flag word has no pending Redraw, so its screen mirror is current (mirror_update); everything else is left to
-// the pass behind the launch (rg_obs.hip k_obs_resid), which goes by the stamp alone.  Per env exactly k_obs_stream's work: mirror words `lane` and
-// `lane + 64`, glyph -> gray value through the wave's LDS table, two whole-line non-temporal float4 stores -- the same bits.
-// The wave is alone on its SIMD by now, so nothing but its own queue hides latency: envs go in batches of ENC_BATCH (all loads of a batch, then all its
-// stores), the loads of batch b + 1 issued BEFORE the stores of batch b.  vmcnt retires in order, so the wait for batch b + 1's words leaves batch b's stores in
-// flight.  The first batch is peeled: with the loop entered straight from the loads the compiler's wait insertion merges "loads only" with the back edge's
-// "loads, then stores" and falls back to vmcnt(0) once per iteration (profiles/r09_experiments.txt).  The env of a slot is a scalar (the set bits of the
-// ballot in turn); the slots past the last env repeat it -- the same bytes to the same address -- so there is no branch inside a batch.
-#ifndef ENC_BATCH
-#define ENC_BATCH 8
+// The pre-streamed encode (k_step_w32<false, true>; rg_state.h enc_out): the body of a HELPER block, one of S.enc_helpers one-wave blocks behind the stair
+// and index-order blocks of the launch.  It plays no turn.  At the lowest wave priority it streams the f32 gray image of every env of the batch from the
+// screen mirror AS IT FINDS IT -- k_obs_stream's streaming half: runs of ENC_RUN consecutive envs, persistent and one run ahead, mirror words `lane` and
+// `lane + 64` of each env, glyph -> gray value through the wave's LDS table (S.gray_lut), two whole-line non-temporal float4 stores -- so the observation's
+// 166 MB move while the turns wait on their own latency chains instead of behind the last of them.  No flag is read, no Redraw drawn, nothing published.
+// Why the images are exact whatever a helper saw: it shares the launch with the turns, so all its stores are complete before the pass behind the launch
+// (rg_obs.hip k_obs_resid) starts.  A mirror byte the helper read is the one the previous step left, the final one, or an intermediate put() of the turn
+// (byte stores do not tear).  A byte the turn wrote lies in a line of the env's enc_rows mask (mirror_update) or in an env that keeps its Redraw flag; the
+// pass rewrites both from the final mirror.  Every other byte was not written, so what the helper read was final.  No cross-wave flag, fence or spin.
+#ifndef ENC_RUN
+#define ENC_RUN 4
 #endif
-// A wave that reaches its tail later than S.enc_cut after its own start encodes nothing and stamps nothing: its envs are streamed by the pass behind the
-// launch.  The launch is as long as its last wave, and an encode costs a wave 10-20 us while the memory system is busy with everybody else's: the waves
-// whose turn ends late would end the launch that much later, while the pass behind it has its Redraw chains to wait for anyway and streams beside them
-// (rg_api.cpp RG_ENC_CUT_TICKS; profiles/r09_experiments.txt: the sweep).  Which waves are late changes from run to run; the images do not.
-__device__ __forceinline__ void tail_encode(const RgState &S, const int lane, const int e, const bool encl) {
+#define ENC_DELAY_MAX 20000u  // (the longest start delay the kernel honours, 200 us)
+__device__ __forceinline__ void enc_helper(const RgState &S, const int hb, const int nh) {
     typedef float f4v __attribute__((ext_vector_type(4)));
-    const uint64_t em = __ballot(encl);
-    if (encl) S.enc_stamp[e] = S.enc_step;
-    if (!em) return;
-    const int ebase = __builtin_amdgcn_readfirstlane(e - lane);  // (an index-order wave: lane i holds env ebase + i; a stair wave: lane 0 alone)
-    // the mirror bytes this wave's lanes wrote in mirror_update are read by OTHER lanes below: drained first, and read with loads no stale L1 line can serve
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_setprio(0);
+    const int lane = threadIdx.x;
+    const int n = S.n, nruns = (n + ENC_RUN - 1) / ENC_RUN;
+    if (hb >= nruns) return;
+    lds_u32 *lutw = (lds_u32 *)(g_smem + STEP_LDS_LUT);
+    lutw[lane] = __float_as_uint(S.gray_lut[lane]);
+    lutw[lane + WAVE] = __float_as_uint(S.gray_lut[lane + WAVE]);
+    __syncthreads();
+    // The start delay (RgState::enc_delay; rg_api.cpp RG_ENC_DELAY_TICKS): the first load rounds of a turn -- the env's scalars, the 5x5 window -- are its most
+    // latency-bound part, and against a saturated HBM they took 5.9 + 11.5 us instead of 3.5 + 6.2 (profiles/r10_experiments.txt); the stream starts once they
+    // are over.  A bounded wait on the chip-wide 100 MHz clock, asleep in between: no other wave is waited for.
+    if (S.enc_delay) {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), lim = S.enc_delay < ENC_DELAY_MAX ? S.enc_delay : ENC_DELAY_MAX;
+        while (__builtin_amdgcn_s_memrealtime() - t0 < lim) __builtin_amdgcn_s_sleep(16);
+    }
     const __attribute__((address_space(3))) float *lut = (const __attribute__((address_space(3))) float *)(g_smem + STEP_LDS_LUT);
     const uint32_t *mir = reinterpret_cast<const uint32_t *>(S.screen) + lane;
     f4v *img = reinterpret_cast<f4v *>(S.enc_out) + lane;
-    uint64_t rem = em;
-    int last = 0;
-    struct Batch { int env[ENC_BATCH]; uint32_t w0[ENC_BATCH], w1[ENC_BATCH]; };
-    auto load = [&](Batch &b) {
+    struct Run { uint32_t w0[ENC_RUN], w1[ENC_RUN]; };
+    // (a run past the batch, and the envs past the batch of the last run: env n - 1's words again.  Loads no L1 line can serve: other waves of this launch
+    // are writing these bytes)
+    auto load = [&](int r, Run &R) {
 #pragma unroll
-        for (int k = 0; k < ENC_BATCH; k++) {
-            last = rem ? __builtin_ctzll(rem) : last;
-            rem &= rem - (rem ? 1ull : 0ull);
-            b.env[k] = ebase + last;
-            const uint32_t *m = mir + (size_t)b.env[k] * 128;
-            b.w0[k] = __hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            b.w1[k] = __hip_atomic_load(m + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int k = 0; k < ENC_RUN; k++) {
+            int e = r * ENC_RUN + k;
+            e = e < n ? e : n - 1;
+            const uint32_t *m = mir + (size_t)e * 128;
+            R.w0[k] = __hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            R.w1[k] = __hip_atomic_load(m + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
     auto gray4 = [&](uint32_t w) {
@@ -2651,30 +2657,39 @@ __device__ __forceinline__ void tail_encode(const RgState &S, const int lane, co
         f4v v = {lut[w & 0xff], lut[(w >> 8) & 0xff], lut[(w >> 16) & 0xff], lut[w >> 24]};
         return v;
     };
-    auto store = [&](const Batch &b) {
+    // (no branch on the end of the batch inside a run: with one, the wait insertion no longer knows how many stores are in flight behind the next run's loads
+    // and drains them all.  The slots past the last env repeat it -- to the same address, and whatever differs between two reads of its mirror lies in a
+    // line the pass rewrites)
+    auto store = [&](int r, const Run &R) {
 #pragma unroll
-        for (int k = 0; k < ENC_BATCH; k++) {
-            f4v *o = img + (size_t)b.env[k] * 128;
-            __builtin_nontemporal_store(gray4(b.w0[k]), o);
-            __builtin_nontemporal_store(gray4(b.w1[k]), o + WAVE);
+        for (int k = 0; k < ENC_RUN; k++) {
+            int e = r * ENC_RUN + k;
+            e = e < n ? e : n - 1;
+            f4v *o = img + (size_t)e * 128;
+            __builtin_nontemporal_store(gray4(R.w0[k]), o);
+            __builtin_nontemporal_store(gray4(R.w1[k]), o + WAVE);
         }
     };
-    const int nb = (__popcll(em) + ENC_BATCH - 1) / ENC_BATCH;
-    Batch cur, nxt;
-    load(cur);
-    load(nxt);  // (past the last env: its words again, loads only)
-    store(cur);
+    // one run ahead: run r + nh's words are requested before run r's stores issue, and vmcnt retires in order, so the wait for them leaves the stores in
+    // flight.  The first run is peeled: entered straight from the loads, the compiler's wait insertion merges "loads only" with the back edge's "loads, then
+    // stores" and falls back to vmcnt(0) once per iteration (profiles/r09_experiments.txt).
+    Run cur, nxt;
+    int r = hb;
+    load(r, cur);
+    load(r + nh, nxt);
+    store(r, cur);
 #pragma nounroll
-    for (int b = 1; b < nb; b++) {
+    for (r += nh; r < nruns; r += nh) {
         cur = nxt;
-        load(nxt);
-        store(cur);
+        load(r + nh, nxt);
+        store(r, cur);
     }
 }
 
 // One wave's share of a step: lane i plays the key of env `e` (any env index -- the lanes of a wave need not hold consecutive envs), `valid`
 // lanes only; the other lanes still take part in the wave-cooperative services.
-// ENC: the instance that ends in the tail encode (k_step_w32 only: the handle armed it for this launch, rgk_step) -- the others carry none of it.
+// ENC: the instance whose launch pre-streams the gray images (k_step_w32 only: the handle armed it for this launch, rgk_step; enc_helper): its turns publish the
+// image lines they touched (S.enc_rows) -- the others carry none of it.
 template <int BW, int GM, bool BND = false, bool ENC = false>
 __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__restrict__ SPd, const RgConfig &c, const uint8_t *__restrict__ keys, int use_spares, int stage_off,
                                           const int e, const bool valid_in, const int stair_role) {
@@ -2682,7 +2697,6 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     uint16_t *lds_grid = reinterpret_cast<uint16_t *>(g_smem + stage_off);  // (behind the per-lane columns: STEP_LDS_*)
     const int lane = threadIdx.x;
     Prof pf; pf.start(S.prof);
-    const unsigned long long enc_t0 = ENC ? __builtin_amdgcn_s_memrealtime() : 0ull;  // (tail_encode: S.enc_cut)
     Env E;
     E.err = 0; E.on_stairs = 0;
     uint32_t react = 0, err = 0, old_flags = 0, steps = 0, flags = 0;
@@ -2691,6 +2705,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     bool live = false;   // this lane processes a key this call
     bool ui_dead = false, terminal = false;
     bool inc_done = false;  // the turn applied its Redraw to the screen mirror itself (mirror_update)
+    uint32_t enc_rows = 0;  // ENC: the image lines whose mirror bytes mirror_update wrote (live from there to the tail's store)
     bool taken = false;  // terminal + auto-reset + spare ready: the spare becomes the live state at the end of the wave (take_spares)
     uint32_t n_bfs = 0, n_inline = 0, n_taken = 0, n_cont = 0;  // workload counters (S.stats)
     uint32_t key = 0, nxs = RG_NX_NONE;
@@ -2757,7 +2772,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     // Redraw (S.ovl) -- parked here from the first load round to the incremental mirror update at the end of the turn
     lds_u32 *ovl_l = (lds_u32 *)(g_smem + STEP_LDS_OVL) + lane;
     ovl_l[0] = 0;
-    if ((BND && S.bound_gray) || ENC) {  // (ENC: the table of the tail encode, the same one)
+    if (BND && S.bound_gray) {
         // glyph -> gray value as the observation pass encodes it (rg_obs.hip k_obs `lutf`, python/src/lib.rs:84), for the pixels mirror_update writes into the bound
         // tensor: the host's table straight into LDS (computed per wave -- two tile_to_sym + two IEEE divisions per lane -- it cost every wave 1.1 us)
         typedef const __attribute__((address_space(1))) void *gptr;
@@ -2959,7 +2974,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
                 !(old_flags & (RG_FLAG_REDRAW | RG_FLAG_HIST_STALE | RG_FLAG_HIST_LAG | RG_FLAG_HIST_DIRTY)) && !(ovl_l[0] >> 31)) {
                 // (SCR_CHANGED: bytes of the mirror changed without a Redraw flag -- what a bound observation tensor, rg_obs_bind, re-encodes this env for)
                 // (... unless the update wrote the image's pixels too: a bound gray tensor)
-                if (mirror_update<BND>(S, c, E, w, react, room_id_of(c, w.ox, w.oy))) flags = (flags & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_DIRTY)) | ((!BND || S.bound_gray) ? 0u : RG_FLAG_SCR_CHANGED);
+                if (mirror_update<BND, ENC>(S, c, E, w, react, room_id_of(c, w.ox, w.oy), enc_rows)) flags = (flags & ~(RG_FLAG_REDRAW | RG_FLAG_HIST_DIRTY)) | ((!BND || S.bound_gray) ? 0u : RG_FLAG_SCR_CHANGED);
                 inc_done = true;  // (the overlays' positions and how they show are recorded either way)
             }
         }
@@ -2975,7 +2990,6 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     // end: its return value is first needed behind all the stores of the tail, and vmcnt being in order it is there by then (asked for at the end, the wave
     // waited 2.6 us for it: it returns behind every store issued before it).
     bool pend = false; uint64_t pm = 0; uint32_t lbase = 0;
-    bool encl = false;  // ENC: this lane's env gets its image from the tail encode
     if (BND && S.obs_list) {
         const uint32_t fw = (live ? ((terminal && c.auto_reset) ? RG_FLAG_REDRAW : flags) : old_flags);
         pend = valid && (fw & (RG_FLAG_REDRAW | RG_FLAG_SCR_CHANGED));
@@ -3022,7 +3036,6 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
         if (!taken) store_env(S, E);  // (a taken env's live scalars are the spare's: copied below)
         S.steps[et] = steps;
         S.flags[et] = flags;
-        if (ENC) encl = !(flags & RG_FLAG_REDRAW);  // (this branch: the env played its key)
         S.done[et] = terminal ? 1 : 0;
         // The env's observation record (rg_state.h obs_rec; rg_obs.hip ObsTabs): the fused observation pass overlays a Redraw from these words -- one line
         // per env instead of the env's column of the [slot][env] tables.  Here: the monsters as they stand after their turn (the wave's LDS table) and the
@@ -3094,11 +3107,9 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
     take_spares(S, SPd, c, lane, et, taken, on_next);
     stair_publish(S, lane, et, valid, on_next);
     pf.mark(7);
-    if constexpr (ENC) {
-        const bool late = __builtin_amdgcn_s_memrealtime() - enc_t0 > (unsigned long long)S.enc_cut;  // (wave-uniform)
-        tail_encode(S, lane, et, encl && !late);
-        pf.mark(31);
-    }
+    // (ENC: every env has exactly one valid lane in the launch, so the pass behind it finds this launch's mask for every env.  Without helper blocks nothing
+    // has been streamed: all lines)
+    if constexpr (ENC) { if (valid) S.enc_rows[et] = (uint16_t)(S.enc_helpers ? enc_rows : 0xffffu); }
     pf.finish();
 }
 
@@ -3157,10 +3168,15 @@ __global__ void __launch_bounds__(WAVE) k_step(RgState S, const RgState *__restr
 // for the whole launch, as many index-order blocks started only when the first waves ended (33-38 us) and finished last (84 us against 57-67 us
 // for every other wave).  The wider instances spill under the cap (15-136 VGPRs: a measured loss) and keep their natural allocation.
 // (BND: the instance for handles with a bound observation tensor, rg_obs_bind -- the list of redrawn envs, the gray pixels of the incremental mirror update)
-// (ENC: the instance that ends every wave in the tail encode of its envs' gray images -- tail_encode; armed per launch by rg_step_obs_gray)
+// (ENC: the instance whose last S.enc_helpers blocks stream the gray images beside the turns -- enc_helper; armed per launch by rg_step_obs_gray.  They come
+// behind the stair and index-order blocks, so the step waves are placed first and the helpers take the wave slots the cap leaves free: up to 768 at 65 536 envs)
 template <bool BND, bool ENC = false>
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_step_w32(RgState S, const RgState *__restrict__ SPd, RgConfig c, const uint8_t *__restrict__ keys, int use_spares, int stage_off, int epw, int parity) {
+    if constexpr (ENC) {
+        const int first_helper = (int)gridDim.x - S.enc_helpers;
+        if ((int)blockIdx.x >= first_helper) { enc_helper(S, (int)blockIdx.x - first_helper, S.enc_helpers); return; }
+    }
     RG_STEP_BLOCK_BODY(0, 0, BND, ENC)
 }
 // More than 64 rooms (only possible on wide grids: 65 rooms need W >= 65): the generic row-width class with the 384-room generator.  Its LDS
@@ -3239,10 +3255,23 @@ int rgk_step_bound_capable(const RgConfig *c) {
     if (c->width <= 32 && gen_mode_of(c) == 0) return 1;
     return (c->width <= 96 && hw <= 4096 && c->width > 64) ? 1 : 0;
 }
-// whether rgk_step launches the instance that ends its waves in the tail encode when S->enc_out is set: the capped W <= 32 class -- the very test of the
-// dispatch below -- on a grid of exactly 512 cells (tail_encode: two mirror words per lane).  rg_api.cpp arms the encode only where this holds, so a
-// launch with enc_out set never takes another class's kernel and leaves every env to the residual pass.
+// whether rgk_step launches the instance that pre-streams the gray images when S->enc_out is set: the capped W <= 32 class -- the very test of the
+// dispatch below -- on a grid of exactly 512 cells (enc_helper: two mirror words per lane, 16 image lines per env).  rg_api.cpp arms the encode only where
+// this holds, so a launch with enc_out set never takes another class's kernel and leaves every env to the pass behind it.
 int rgk_step_tail_capable(const RgConfig *c) { return (c->width <= 32 && gen_mode_of(c) == 0 && c->width * c->height == 512) ? 1 : 0; }
+// helper blocks of such a launch (RgState::enc_helpers).  The capped kernel's two waves per SIMD leave 2048 - 256 - 1024 = 768 slots free beside the stair and
+// index-order blocks of 65 536 envs, but the count is set by the memory system, not by the slots: a helper streams a run in ~0.55 us, so H helpers move the
+// batch's 166 MB in 16 384 / H x 0.55 us, and the faster they go the more the turns' own loads wait behind them.  384 helpers, started 25 us into the launch
+// (rg_api.cpp RG_ENC_DELAY_TICKS), are done ~48 us in -- before the slowest turns -- and cost the turns least (swept 128 .. 768 helpers x 0 .. 40 us,
+// profiles/r10_experiments.txt; 128 and 192 helpers end after the turns and lengthen the launch).  Never more than there are runs.
+// want > 0: that many (development builds: the sweep, and the test that lets one helper stream every run).
+#define ENC_HELPERS 384
+int rgk_step_enc_helpers(int n, int want) {
+    const int nruns = (n + ENC_RUN - 1) / ENC_RUN;
+    int h = ENC_HELPERS;
+    if (want > 0) h = want > 2048 ? 2048 : want;
+    return h < nruns ? h : nruns;
+}
 int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const bool bnd = S->obs_list != nullptr && rgk_step_bound_capable(c);
     int hw = c->width * c->height;
@@ -3252,7 +3281,8 @@ int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const u
     const int epw = rgk_step_epw(S->n, (c->width <= 32 && gen_mode_of(c) == 0) ? 2 : 1);
     // parity >= 0: stair isolation with the list the last render / observation pass wrote into set `parity`
     const int nb = (S->n + epw - 1) / epw;
-    const dim3 grid(parity >= 0 ? STAIR_BLOCKS + nb : nb), block(WAVE);
+    const bool enc = !bnd && S->enc_out && c->width <= 32 && gen_mode_of(c) == 0;  // (the ENC instance below: its helper blocks come last)
+    const dim3 grid((parity >= 0 ? STAIR_BLOCKS + nb : nb) + (enc ? S->enc_helpers : 0)), block(WAVE);
     // (ev0 / ev1: optional events stamped with this dispatch's own begin and end -- rg_timing; ev1 alone: the completion event k_regen's stream waits for)
 #define RG_LAUNCH_STEP(K) do { if (ev0 || ev1) hipExtLaunchKernelGGL(K, grid, block, (uint32_t)smem, st, ev0, ev1, 0, *S, SP_dev, *c, keys, use_spares, stage_off, epw, parity); \
                                else hipLaunchKernelGGL(K, grid, block, smem, st, *S, SP_dev, *c, keys, use_spares, stage_off, epw, parity); } while (0)

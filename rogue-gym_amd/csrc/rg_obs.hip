@@ -588,14 +588,14 @@ __global__ void __launch_bounds__(WAVE) k_obs_stream(RgState S, RgConfig c, floa
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_obs_resid: the observation pass behind a step launch that encoded in its waves' tails (rg_kernels.hip tail_encode; RgState::enc_stamp).  It serves the
-// envs the tails left -- stamp != this launch's enc_step -- and nothing else: a stamped env costs its share of one coalesced load of flag words and stamps.
-// The stamp alone says "already encoded": an unstamped env with a pending Redraw is drawn from the tiles exactly as k_obs_stream draws it (mirror
-// write-back, history plane, flag word); an unstamped env without one (its wave ended late and left the stream to this pass, no key, an error) is streamed
-// from its mirror as k_obs_stream streams it.  Same bits as k_obs_stream.
+// k_obs_resid: the fix-up pass behind a step launch whose helper blocks pre-streamed every env's gray image from the screen mirror as they found it
+// (rg_kernels.hip enc_helper; RgState::enc_rows).  An env with a pending Redraw is drawn from the tiles exactly as k_obs_stream draws it (mirror write-back,
+// history plane, flag word).  Any other env whose turn wrote mirror bytes has the image lines of its mask -- bit b: cells 32 b .. 32 b + 31, one 128-byte line
+// -- re-encoded from the final mirror: whole lines, the lanes of the other lines idle.  An env with mask 0 costs its share of one coalesced load of flag
+// words and masks.  Same bits as k_obs_stream.
 // ---------------------------------------------------------------------------------------------
-// One wave owns a run of OBS_RESID_RUN consecutive envs, persistent and one run ahead with the flag words and stamps (lane i: env i of the run).  The mirror
-// words of the run's unstamped envs are requested together once those are known, then stored; then the run's Redraw envs, one at a time.
+// One wave owns a run of OBS_RESID_RUN consecutive envs, persistent and one run ahead with the flag words and masks (lane i: env i of the run).  The mirror
+// words of the run's masked lines are requested together once those are known, then stored; then the run's Redraw envs, one at a time.
 #ifndef OBS_RESID_RUN
 #define OBS_RESID_RUN 4
 #endif
@@ -610,16 +610,16 @@ __global__ void __launch_bounds__(WAVE) k_obs_resid(RgState S, RgConfig c, float
     const int lane = threadIdx.x, W = c.width, HW = W * c.height, Q4 = HW >> 2, Q8 = HW >> 3, n = S.n;
     const int nrooms = c.room_num_x * c.room_num_y, rec_words = RG_OBS_REC_WORDS(nrooms);
     const int nruns = (n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
-    // a run's flag words and stamps; a lane past the run or the batch holds this launch's stamp: nothing to serve
-    auto load_run = [&](int r, uint32_t &fl, uint32_t &stamp) {
+    // a run's flag words and line masks; a lane past the run or the batch holds zeros: nothing to serve
+    auto load_run = [&](int r, uint32_t &fl, uint32_t &rows) {
         const int base = r * OBS_RESID_RUN;
         const bool in = r < nruns && lane < OBS_RESID_RUN && base + lane < n;
         fl = in ? S.flags[base + lane] : 0u;
-        stamp = in ? S.enc_stamp[base + lane] : S.enc_step;
+        rows = in ? (uint32_t)S.enc_rows[base + lane] : 0u;
     };
-    uint32_t fl_cur, st_cur;
-    load_run(blockIdx.x, fl_cur, st_cur);
-    // the table the step kernel's tails encoded with (RgState::gray_lut: the host's, the same single division as k_obs_stream's)
+    uint32_t fl_cur, rw_cur;
+    load_run(blockIdx.x, fl_cur, rw_cur);
+    // the table the step launch's helpers encoded with (RgState::gray_lut: the host's, the same single division as k_obs_stream's)
     lutf[lane] = S.gray_lut[lane];
     lutf[lane + WAVE] = S.gray_lut[lane + WAVE];
     for (int g = lane; g < RG_MAX_ENEMY_KINDS + 6; g += WAVE) mtile[g] = c.mon[g].tile;
@@ -633,30 +633,35 @@ __global__ void __launch_bounds__(WAVE) k_obs_resid(RgState S, RgConfig c, float
         v = lane < Q8 ? reinterpret_cast<const uint4 *>(S.cell + (size_t)e * HW)[lane] : make_uint4(0, 0, 0, 0);
         rec = lane < rec_words ? S.obs_rec[(size_t)e * rec_words + lane] : 0u;
     };
+    const int band = lane >> 3;  // mirror word `lane` lies in image line lane >> 3, word lane + 64 in line 8 + (lane >> 3)
     for (int r = blockIdx.x; r < nruns; r += gridDim.x) {
         const int base = r * OBS_RESID_RUN;
-        const uint32_t fl = fl_cur;
-        const bool need = st_cur != S.enc_step;
-        load_run(r + gridDim.x, fl_cur, st_cur);
-        uint64_t rmask = __ballot(need && (fl & RG_FLAG_REDRAW));
-        const uint64_t smask = __ballot(need && !(fl & RG_FLAG_REDRAW));
+        const uint32_t fl = fl_cur, rows = rw_cur;
+        load_run(r + gridDim.x, fl_cur, rw_cur);
+        uint64_t rmask = __ballot(fl & RG_FLAG_REDRAW);
+        const uint64_t smask = __ballot(!(fl & RG_FLAG_REDRAW) && rows != 0u);
         if (!(rmask | smask)) continue;
         uint4 tv = make_uint4(0, 0, 0, 0);
         uint32_t trec = 0;
-        if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);  // in flight while the mirror-streamed envs are served
+        if (rmask) load_tiles(base + __builtin_ctzll(rmask), tv, trec);  // in flight while the masked lines are served
         const uint32_t *m = reinterpret_cast<const uint32_t *>(S.screen) + (size_t)base * Q4;
         float4 *o = reinterpret_cast<float4 *>(out) + (size_t)base * Q4;
         uint32_t w0[OBS_RESID_RUN], w1[OBS_RESID_RUN];
 #pragma unroll
-        for (int i = 0; i < OBS_RESID_RUN; i++) {  // (run-uniform branches)
+        for (int i = 0; i < OBS_RESID_RUN; i++) {  // (run-uniform branches; the line's eight lanes inside)
             w0[i] = w1[i] = 0u;
-            if ((smask >> i) & 1) { w0[i] = m[i * Q4 + lane]; w1[i] = m[i * Q4 + lane + WAVE]; }
+            if ((smask >> i) & 1) {
+                const uint32_t ri = __builtin_amdgcn_readlane(rows, i);
+                if ((ri >> band) & 1u) w0[i] = m[i * Q4 + lane];
+                if ((ri >> (8 + band)) & 1u) w1[i] = m[i * Q4 + lane + WAVE];
+            }
         }
 #pragma unroll
         for (int i = 0; i < OBS_RESID_RUN; i++) {
             if (!((smask >> i) & 1)) continue;
-            store_obs(&o[i * Q4 + lane], gray4(w0[i]));
-            store_obs(&o[i * Q4 + lane + WAVE], gray4(w1[i]));
+            const uint32_t ri = __builtin_amdgcn_readlane(rows, i);
+            if ((ri >> band) & 1u) store_obs(&o[i * Q4 + lane], gray4(w0[i]));
+            if ((ri >> (8 + band)) & 1u) store_obs(&o[i * Q4 + lane + WAVE], gray4(w1[i]));
         }
         while (rmask) {  // (k_obs_stream's Redraw service)
             const int i = __builtin_ctzll(rmask);
@@ -1193,7 +1198,7 @@ int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, 
     return 1;
 }
 // whether rgk_obs serves this handle's plain gray image (no status planes, no history plane, not bound) with k_obs_stream -- of the conditions under which
-// rg_step_obs_gray arms the tail encode, the ones that are this file's -- on a grid of exactly 512 cells (two mirror words per lane)
+// rg_step_obs_gray arms the pre-streamed encode, the ones that are this file's -- on a grid of exactly 512 cells (two mirror words per lane)
 int rgk_obs_tail_capable(const RgState *S, const RgConfig *c) {
     const int hw = c->width * c->height, nr = c->room_num_x * c->room_num_y;
     if (hw != 512 || nr > RG_OBS_MAX_ROOMS || !S->obs_rec || !S->ovl || S->ext) return 0;
@@ -1203,7 +1208,7 @@ int rgk_obs_tail_capable(const RgState *S, const RgConfig *c) {
 #endif
     return 1;
 }
-// the observation pass behind a step launch that encoded in its tails (S->enc_stamp / enc_step are that launch's): the envs it left
+// the fix-up pass behind a step launch that pre-streamed the images (S->enc_rows is that launch's): its Redraw envs and the image lines its turns touched
 void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     int blocks = (S->n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
     if (blocks > OBS_RESID_WAVES) blocks = OBS_RESID_WAVES;

@@ -137,13 +137,14 @@ struct RgState {
     float *bound_gray;   // the bound tensor itself when it is a GRAY image [n][1][H][W]: the turn's incremental mirror update writes the pixels it changes straight
                          // into it (k_step mirror_update), so such an env needs no observation pass at all; NULL otherwise
     const float *gray_lut;  // [128] glyph -> gray value as the observation pass encodes it (rg_obs_bind fills it on the host: symbol id / symbols, one IEEE division)
-    // The tail encode (rg_step_obs_gray on an eligible handle; rg_kernels.hip tail_encode): a step wave that has finished its turn writes the f32 gray image of
-    // each of its envs that played and is left without a pending Redraw into enc_out, from the screen mirror, and stamps the env with enc_step; the
-    // observation pass behind it (rg_obs.hip k_obs_resid) serves exactly the envs whose stamp is not this launch's.  enc_out == NULL: the launch encodes nothing.
+    // The pre-streamed encode (rg_step_obs_gray on an eligible handle; rg_kernels.hip enc_helper): enc_helpers one-wave blocks at the back of the step launch
+    // stream the f32 gray image of EVERY env into enc_out from the screen mirror as they find it, beside the turns; a turn that writes mirror bytes itself
+    // (mirror_update) leaves the set of image lines it touched in enc_rows, and the pass behind the launch (rg_obs.hip k_obs_resid) re-encodes exactly those
+    // lines from the final mirror and draws the envs that keep a Redraw flag.  enc_out == NULL: the launch encodes nothing.
     float *enc_out;      // this step's observation tensor [n][1][H][W], H * W = 512
-    uint32_t *enc_stamp; // [n] the enc_step of the last launch whose tail wrote the env's image
-    uint32_t enc_step;   // this launch's stamp, never 0 (the stamps start at 0)
-    uint32_t enc_cut;    // a wave that reaches its tail later than this after its own start (ticks of the chip-wide 100 MHz clock) encodes and stamps nothing
+    uint16_t *enc_rows;  // [n] bit b: this launch's turn wrote a mirror byte of cells 32 b .. 32 b + 31 (one 128-byte line of the image); written by every valid lane
+    int32_t enc_helpers; // helper blocks of this launch (the last blocks of the grid); 0: none, and every env's enc_rows is all ones -- the pass encodes everything
+    uint32_t enc_delay;  // a helper waits this long (ticks of the chip-wide 100 MHz clock, capped in the kernel) before its first load
     int32_t *obs_list;   // [2][n]
     uint32_t *obs_cnt;   // [2]
     int32_t obs_par;     // which half this launch writes (set by the host before every k_step)
