@@ -154,3 +154,25 @@ print("HipVecRogueEnv(monsters='shown'): %.1f %% of the envs have a monster next
       % (100 * (venv.threat[:, 0] > 0).float().mean().item(), 100 * (attackable != 0).float().mean().item(), e,
          [dict(zip(venv.MONSTER_COLS[:5], (chr(r[0]),) + tuple(r[1:5]))) for r in venv.monsters[e].tolist() if r[0]]))
 venv.close()
+
+# 3k. the rest of the level as an object table ordered by WALKING distance, and an option rollout on it: every env picks a target -- its first gold row, else
+#     its first stairs row, else its first row (the nearest frontier cell) -- hands the row's (y, x) to route() and plays the key.  objects="known" reads the
+#     player's own map: nothing privileged ---------------------------------------------------------------------------------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], max_steps=1000, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0,
+                      objects="known", object_kinds="stairs+gold+frontier", object_cap=8)
+gold = torch.zeros(4096, device=venv.device)
+lanes = torch.arange(4096, device=venv.device)
+for t in range(200):
+    kind = venv.objects[:, :, 0]
+    is_gold, is_stairs = (kind & 2) != 0, (kind & 1) != 0
+    pick = torch.where(is_gold.any(1), is_gold.int().argmax(1), torch.where(is_stairs.any(1), is_stairs.int().argmax(1), 0))
+    row = venv.objects[lanes, pick].to(torch.int32)
+    keys, dist, _ = venv.route(goal=None, known=True, cells=row[:, [5, 4]].contiguous())                            # columns 5, 4: (y, x); dist == row[:, 3]
+    keys = torch.where(row[:, 3] == 0, torch.where((row[:, 0] & 1) != 0, ord(">"), ord("s")), keys.int()).to(torch.uint8)   # standing on it: descend, or search
+    obs, reward, done = venv.step_keys(keys)
+    gold += reward
+e = int((venv.objects[:, :, 0] != 0).sum(1).argmax())
+print("HipVecRogueEnv(objects='known'): %.0f gold per env in 200 option steps, dungeon level %.2f; counts (stairs, gold, door, frontier) of env %d: %s, its table %s"
+      % (gold.mean().item(), venv.status[:, 0].float().mean().item(), e, venv.object_count[e].tolist(),
+         [dict(zip(venv.OBJECT_COLS[:6], r[:6])) for r in venv.objects[e].tolist() if r[0]]))
+venv.close()

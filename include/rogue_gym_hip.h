@@ -413,6 +413,44 @@ int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int p
                      const int32_t *mon_type, const int32_t *mon_active, const int32_t *mon_hp, const int32_t *mon_alive, int room_num_x, int room_num_y,
                      const uint32_t *room_rect, const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out);
 
+/* OBJECT TABLES BY WALKING DISTANCE: the stairs, gold, doors and frontier cells of every env's level as an entity list, nearest first by the number of moves
+ * it takes to reach them -- what an object-centric policy, a feature-vector policy or an option policy that picks a target for rg_route needs beside
+ * rg_monsters.  One search from the player's cell over rg_route's graph visits the objects in that order.  The rule is stated once in csrc/rg_objects.h.
+ *   mode, the OR of RG_ROUTE_SECRETS and RG_ROUTE_KNOWN with rg_route's meaning; K, pass, corner and known are rg_route's predicates, the player's own cell
+ *     judged as its own.  With RG_ROUTE_KNOWN nothing in the answer is privileged: it is the player's own map (DRAWN / VISIBLE).  Without it the table is
+ *     PRIVILEGED in the sense of rg_path.
+ *   kinds, the OR of: RG_OBJ_STAIRS a cell that is K and whose surface is the stairs; RG_OBJ_GOLD a cell that is K and holds gold, EXCEPT the player's own
+ *     cell (gold is taken by moving onto it); RG_OBJ_DOOR a cell that is K and whose surface is a door, the '+' of the screen -- a hidden door keeps its wall
+ *     surface and is none; RG_OBJ_FRONTIER (legal only together with RG_ROUTE_KNOWN) rg_route's frontier cells.  A cell is ONE object; its kind column is
+ *     the OR of the asked kinds it satisfies (a door that is a frontier cell reads 12).
+ *   walk of a cell = the number of moves from the player's cell to it in rg_route's search graph under mode (a move's target is pass, a diagonal's two
+ *     orthogonal neighbours are corner, the own cell starts the search whatever its word, monsters are ignored): the distance rg_route answers when the cell
+ *     is given as RG_GOAL_CELL under the same mode.  A qualifying cell the search does not reach is not listed; the own cell is listed with walk 0 when it
+ *     qualifies.
+ *   The table: the listed objects in ascending order of (walk, y, x), the first `cap` (1 .. RG_OBJ_MAX_CAP) of them, as rows of RG_OBJ_COLS int16, 16 bytes
+ *     each: [0] the kind bits (0 marks an empty row), [1] dx = x - px, [2] dy = y - py, [3] walk (at most H*W <= 7 680), [4] x, [5] y, [6] max(|dx|, |dy|),
+ *     [7] 0.  Rows past the last listed object are all zero, and every row of every env is written by every call.
+ *   count i32 [4]: per kind bit the number of qualifying cells, reached or not; 0 for a kind that was not asked for.  It tells that more exists than the
+ *     table holds or the search reached.
+ *   An env in the Grave modal (RG_FLAG_DEAD) answers an all-zero table and zero counts.  Gold amounts and a first-move key per object are not part of it:
+ *     the key to a chosen object is rg_route with that cell.
+ * rg_objects: table_dev (nullable) = i16 [n_env][cap][RG_OBJ_COLS], count_dev (nullable) = i32 [n_env][4], both 16-byte aligned.  Asynchronous on the
+ *   handle's stream; it reads game state only and flushes nothing.  Config groups and mixed sizes are served, every env's rows at the handle's env index.
+ *   Refused with a message naming the argument, nothing launched or written: kinds zero or with unknown bits; unknown bits in mode; RG_OBJ_FRONTIER without
+ *   RG_ROUTE_KNOWN; cap outside 1 .. RG_OBJ_MAX_CAP while table_dev is given; both outputs NULL; an output that is not 16-byte aligned.
+ * rg_objects_host (stateless, needs no device): the same rule for ONE env by a plain queue search -- cells u16 [height][width] in rg_debug_fetch's layout,
+ *   the player's cell and the dead bit; table_out = i16 [cap][RG_OBJ_COLS], count_out = i32 [4], either NULL but not both.  Refusals as rg_objects'
+ *   (alignment aside), and cells NULL, the sizes or (px, py) out of range; the message is read through rg_last_error(NULL). */
+#define RG_OBJ_STAIRS   1u
+#define RG_OBJ_GOLD     2u
+#define RG_OBJ_DOOR     4u
+#define RG_OBJ_FRONTIER 8u
+#define RG_OBJ_MAX_CAP  32
+#define RG_OBJ_COLS     8
+int rg_objects(rg_t *h, uint32_t kinds, uint32_t mode, int cap, int16_t *table_dev, int32_t *count_dev);
+int rg_objects_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t kinds, uint32_t mode, int cap,
+                    int16_t *table_out, int32_t *count_out);
+
 /* PlayerState::status_vec (python/src/lib.rs:158-161, flags.rs:67-87) for the whole batch: out_host = i32 [n_env][popcount(flag)].  Synchronous. */
 int rg_status_vec(rg_t *h, uint32_t status_flag, int32_t *out_host);
 

@@ -21,6 +21,7 @@
 #include "rg_route.h"
 #include "rg_episode.h"
 #include "rg_monsters.h"
+#include "rg_objects.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -71,6 +72,7 @@ void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fal
 void rgk_episode(const RgState *S, const RgConfig *c, const RgEpisode *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, int record, uint32_t serial,
                  hipStream_t st);
 void rgk_monsters(const RgState *S, const RgConfig *c, uint32_t mode, int cap, int16_t *table, int32_t *threat, hipStream_t st);
+void rgk_objects(const RgState *S, const RgConfig *c, uint32_t kinds, uint32_t mode, int cap, int16_t *table, int32_t *count, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
@@ -997,7 +999,7 @@ int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int
 }
 // Legal-action masks (rg_action_mask.hip; the rule: rg_action_mask.h).  mask_keys_check: the key list of a call, every refusal before anything is launched;
 // on success `list` holds the n_keys keys the call judges.
-// The readers of game state (rg_action_mask, rg_path, rg_route, rg_monsters): launch(leaf) enqueues one kernel on a handle without groups; on a handle
+// The readers of game state (rg_action_mask, rg_path, rg_route, rg_monsters, rg_objects): launch(leaf) enqueues one kernel on a handle without groups; on a handle
 // with config groups every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do.
 // Game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are.
 extern "C++" template <class Launch> static int reader_launch(rg_t *h, Launch launch) {
@@ -1273,6 +1275,80 @@ int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int p
             memcpy(table_out + (size_t)r * RG_MON_COLS, row, 16);
         }
     if (threat_out) { threat_out[0] = T.adjacent; threat_out[1] = T.nearest; threat_out[2] = T.attack; threat_out[3] = T.count; }
+    return 0;
+}
+// ---- object tables by walking distance (rg_objects.h; k_objects in rg_objects.hip) ----
+// obj_args_check: the words of a call, refused before anything is launched or written
+static int obj_args_check(std::string &err, const char *what, uint32_t kinds, uint32_t mode, int cap, bool have_table, bool have_count, const char *table_name, const char *count_name) {
+    const std::string w = std::string(what) + ": ";
+    if (kinds == 0 || (kinds & ~RG_OBJ_KINDS_ALL)) {
+        err = w + "kinds must be a non-empty OR of RG_OBJ_STAIRS (1), RG_OBJ_GOLD (2), RG_OBJ_DOOR (4) and RG_OBJ_FRONTIER (8), got " + std::to_string(kinds);
+        return 1;
+    }
+    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
+    if ((kinds & RG_OBJ_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
+        err = w + "RG_OBJ_FRONTIER in kinds needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " + std::to_string(mode);
+        return 1;
+    }
+    if (!have_table && !have_count) { err = w + table_name + " and " + count_name + " are both NULL"; return 1; }
+    if (have_table && (cap < 1 || cap > RG_OBJ_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_OBJ_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
+    return 0;
+}
+int rg_objects(rg_t *h, uint32_t kinds, uint32_t mode, int cap, int16_t *table_dev, int32_t *count_dev) {
+    if (obj_args_check(h->err, "rg_objects", kinds, mode, cap, table_dev != nullptr, count_dev != nullptr, "table_dev", "count_dev")) return 1;
+    if (((uintptr_t)table_dev | (uintptr_t)count_dev) & 15) { h->err = "rg_objects: table_dev and count_dev must be 16-byte aligned device pointers"; return 1; }
+    return reader_launch(h, [=](rg_t *l) { rgk_objects(&l->S, &l->cfg, kinds, mode, cap, table_dev, count_dev, l->stream); });
+}
+// One FIFO search from the player's cell over rg_route.h's moves: the queue's order is ascending walk, so the objects it meets are sorted by
+// (walk, y, x) within each walk and the first cap of them are the table.
+int rg_objects_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t kinds, uint32_t mode, int cap, int16_t *table_out, int32_t *count_out) {
+    std::string &err = g_create_err;
+    if (obj_args_check(err, "rg_objects_host", kinds, mode, cap, table_out != nullptr, count_out != nullptr, "table_out", "count_out")) return 1;
+    if (grid_check(err, "rg_objects_host", cells, height, width) || player_check(err, "rg_objects_host", px, py, height, width)) return 1;
+    const int hw = height * width, pi = py * width + px;
+    auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < width && y < height && !rg_route_known(cells[y * width + x], y * width + x == pi); };
+    auto kind_at = [&](int i) {
+        const int x = i % width, y = i / width;
+        return rg_obj_kind(cells[i], kinds, mode, i == pi, unknown_at(x - 1, y) || unknown_at(x + 1, y) || unknown_at(x, y - 1) || unknown_at(x, y + 1));
+    };
+    int32_t count[4] = {0, 0, 0, 0};
+    std::vector<std::pair<uint32_t, uint32_t>> list;  // (walk << 16 | y << 8 | x, kind): the order of the table
+    if (!dead) {
+        std::vector<uint8_t> kind((size_t)hw);
+        for (int i = 0; i < hw; i++) {
+            kind[i] = (uint8_t)kind_at(i);
+            for (int k = 0; k < 4; k++) count[k] += (kind[i] >> k) & 1;
+        }
+        if (table_out) {
+            std::vector<uint16_t> D((size_t)hw, (uint16_t)RG_PATH_INF);
+            std::vector<int> fifo;
+            fifo.reserve((size_t)hw);
+            D[pi] = 0;
+            fifo.push_back(pi);
+            for (size_t head = 0; head < fifo.size(); head++) {
+                const int a = fifo[head], ax = a % width, ay = a / width;
+                if (kind[a]) list.emplace_back((uint32_t)D[a] << 16 | (uint32_t)ay << 8 | (uint32_t)ax, kind[a]);
+                for (int d = 0; d < 8; d++) {
+                    const int dx = rg_path_dx(d), dy = rg_path_dy(d), bx = ax + dx, by = ay + dy;
+                    if (bx < 0 || by < 0 || bx >= width || by >= height) continue;
+                    const int b = by * width + bx;
+                    if (D[b] != RG_PATH_INF || !rg_route_pass(cells[b], mode, b == pi)) continue;
+                    if (dx != 0 && dy != 0 && !(rg_route_corner(cells[ay * width + bx], mode, ay * width + bx == pi) && rg_route_corner(cells[by * width + ax], mode, by * width + ax == pi)))
+                        continue;
+                    D[b] = (uint16_t)(D[a] + 1);
+                    fifo.push_back(b);
+                }
+            }
+            std::sort(list.begin(), list.end());
+        }
+    }
+    if (table_out)
+        for (int r = 0; r < cap; r++) {
+            uint32_t row[4] = {0u, 0u, 0u, 0u};
+            if (r < (int)list.size()) rg_obj_row(list[r].second, px, py, (int)(list[r].first & 0xffu), (int)((list[r].first >> 8) & 0xffu), list[r].first >> 16, row);
+            memcpy(table_out + (size_t)r * RG_OBJ_COLS, row, 16);
+        }
+    if (count_out) memcpy(count_out, count, sizeof count);
     return 0;
 }
 // ---- episode accounting and the scout reward (rg_episode.h; k_episode in rg_episode.hip) ----

@@ -17,6 +17,7 @@ from .rogue_env import DungeonType, ImageSetting, RogueEnv, StatusFlag
 
 
 MONSTER_COLS = inner.MONSTER_COLS  # the int16 columns of a row of HipVecRogueEnv.monsters
+OBJECT_COLS = inner.OBJECT_COLS    # the int16 columns of a row of HipVecRogueEnv.objects
 
 
 class _DevArray:
@@ -38,11 +39,13 @@ class CropView:
 class HipVecRogueEnv:
     ACTIONS = RogueEnv.ACTIONS
     MONSTER_COLS = MONSTER_COLS
+    OBJECT_COLS = OBJECT_COLS
 
     def __init__(self, config_dicts: Iterable[dict], max_steps: int = 1000,
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
                  persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False,
-                 episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4):
+                 episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4,
+                 objects=None, object_kinds: str = "stairs+gold+door", object_cap: int = 8, object_secrets: bool = False):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -97,7 +100,18 @@ class HipVecRogueEnv:
         qualify (rg_monsters).  Both are rewritten in place by everything that refreshes `obs`: one small launch more per step, no host trip.  "shown"
         lists what a redraw of the screen would show now -- read off the game state, so between two redraws it is more current than the image.  "all"
         lists every living monster of the level with its hit points and is PRIVILEGED, as the guide is.  It works on every env this class builds, config
-        groups and mixed sizes included.  None: both attributes are None and nothing is added to any call.  monster_table() works either way."""
+        groups and mixed sizes included.  None: both attributes are None and nothing is added to any call.  monster_table() works either way.
+
+        objects (opt-in; "known" or "all"): `self.objects` is an int16 tensor [N, object_cap, 8] on the device -- for each env the stairs, gold and doors of
+        its level (object_kinds: names joined with '+'; "frontier", the known cells beside an unknown one, with "known" only) as rows of OBJECT_COLS (kind
+        bits 1 stairs | 2 gold | 4 door | 8 frontier, dx, dy, walk, x, y, cheb, 0; a row whose kind is 0 is empty), ordered by `walk`, the number of moves
+        it takes to walk there (then y, x), the first object_cap (1 .. 32) of them -- and `self.object_count` an int32 tensor [N, 4], the cells of each
+        kind on the level, listed or not (rg_objects: one search from the player over rg_route's graph; an object that cannot be reached is counted and
+        not listed).  Both are rewritten in place by everything that refreshes `obs`: one launch more per step, no host trip.  "known" reads the player's
+        own map only (the cells that are drawn or in view): nothing is privileged.  "all" reads the level itself and is PRIVILEGED, as the guide is.
+        object_secrets: the walk goes THROUGH hidden and locked cells, as guide_secrets' routes do.  A row's (y, x) is what route(goal=None, cells=...)
+        takes.  It works on every env this class builds, config groups and mixed sizes included.  None: both attributes are None and nothing is added to
+        any call.  object_table() works either way."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -173,6 +187,13 @@ class HipVecRogueEnv:
         with torch.cuda.device(self.device):
             self.monsters = None if monsters is None else torch.zeros((self.num_envs, self._mon_args[1], len(self.MONSTER_COLS)), dtype=torch.int16, device=self.device)
             self.threat = None if monsters is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        if objects is not None and (not isinstance(objects, str) or objects not in ("known", "all")):
+            raise ValueError("objects must be None, 'known' or 'all', got %r" % (objects,))
+        # (kinds, mode, cap) of rg_objects, None = it is not called
+        self._obj_args = None if objects is None else inner._object_args(object_kinds, objects == "known", bool(object_secrets), object_cap)
+        with torch.cuda.device(self.device):
+            self.objects = None if objects is None else torch.zeros((self.num_envs, self._obj_args[2], len(self.OBJECT_COLS)), dtype=torch.int16, device=self.device)
+            self.object_count = None if objects is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
         self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
@@ -309,6 +330,22 @@ class HipVecRogueEnv:
                                              C.c_void_p(self.guide_keys.data_ptr()), None if self.guide_tier is None else C.c_void_p(self.guide_tier.data_ptr())))
         if self._mon_args is not None:
             self._h.check(self._h.L.rg_monsters(self._h.h, self._mon_args[0], self._mon_args[1], C.c_void_p(self.monsters.data_ptr()), C.c_void_p(self.threat.data_ptr())))
+        if self._obj_args is not None:
+            self._h.check(self._h.L.rg_objects(self._h.h, self._obj_args[0], self._obj_args[1], self._obj_args[2], C.c_void_p(self.objects.data_ptr()),
+                                               C.c_void_p(self.object_count.data_ptr())))
+
+    def object_table(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
+        """(table, count) on the device (rg_objects): table int16 [N, cap, 8], the first `cap` (1 .. 32) objects of every env as rows of OBJECT_COLS in
+        ascending order of (walk, y, x), empty rows zero; count int32 [N, 4], the cells of each kind (stairs, gold, door, frontier), listed or not.  kinds:
+        "stairs", "gold", "door" and -- with known=True only -- "frontier", joined with '+'.  known=True reads the player's own map only; without it the
+        answer is PRIVILEGED.  secrets=True walks through hidden and locked cells.  No host trip; the states, mirrors and `obs` are left as they are."""
+        torch = self.torch
+        kw, mode, cap = inner._object_args(kinds, known, secrets, cap)
+        with torch.cuda.device(self.device):
+            table = torch.empty((self.num_envs, cap, len(self.OBJECT_COLS)), dtype=torch.int16, device=self.device)
+            count = torch.empty((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        self._h.check(self._h.L.rg_objects(self._h.h, kw, mode, cap, C.c_void_p(table.data_ptr()), C.c_void_p(count.data_ptr())))
+        return table, count
 
     def monster_table(self, mode="shown", cap=4):
         """(table, threat) on the device (rg_monsters): table int16 [N, cap, 8], the nearest `cap` (1 .. 16) monsters of every env as rows of MONSTER_COLS, nearest

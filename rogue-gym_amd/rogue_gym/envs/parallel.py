@@ -85,6 +85,10 @@ class ParallelRogueEnv:
         """(table int16 [N, cap, 8], threat int32 [N, 4]): RogueEnv.monsters for the whole batch; mode "all" is privileged."""
         return self.game.monster_tables(mode, cap)
 
+    def object_tables(self, kinds: str = "stairs+gold+door", known: bool = False, secrets: bool = False, cap: int = 8):
+        """(table int16 [N, cap, 8], count int32 [N, 4]): RogueEnv.objects for the whole batch; without known=True it is privileged."""
+        return self.game.object_tables(kinds, known, secrets, cap)
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
         return batch

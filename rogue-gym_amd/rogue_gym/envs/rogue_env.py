@@ -230,6 +230,13 @@ class RogueEnv(Env):
         living monster of the level with its hit points and is PRIVILEGED, as path_key is: a teacher or a shaping term, not an observation."""
         return self.game.monsters(mode, cap)
 
+    def objects(self, kinds: str = "stairs+gold+door", known: bool = False, secrets: bool = False, cap: int = 8):
+        """(table, count): the stairs, gold and doors of the level (kinds: names joined with '+'; "frontier" with known=True only) as an int16 array
+        [cap, 8] -- columns kind (1 stairs | 2 gold | 4 door | 8 frontier), dx, dy, walk, x, y, cheb, 0; a row whose kind is 0 is empty -- ordered by
+        walk, the number of moves it takes to reach the cell, and the int32 counts [4] of the cells of each kind, listed or not.  known=True reads the
+        player's own map only; without it the answer is PRIVILEGED, as path_key is.  secrets=True walks through hidden and locked cells."""
+        return self.game.objects(kinds, known, secrets, cap)
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)

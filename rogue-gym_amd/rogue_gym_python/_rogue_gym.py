@@ -50,6 +50,10 @@ RG_MON_SHOWN, RG_MON_ALL, RG_MON_MAX_CAP, RG_MON_COLS = 0, 1, 16, 8
 MONSTER_MODES = {"shown": RG_MON_SHOWN, "all": RG_MON_ALL}
 MONSTER_COLS = ("tile", "dx", "dy", "cheb", "shown", "active", "hp", "slot")   # the int16 columns of a monster-table row (rg_monsters)
 THREAT_COLS = ("adjacent", "nearest", "attack_mask", "count")                  # the int32 threat words
+RG_OBJ_STAIRS, RG_OBJ_GOLD, RG_OBJ_DOOR, RG_OBJ_FRONTIER, RG_OBJ_MAX_CAP, RG_OBJ_COLS = 1, 2, 4, 8, 32, 8
+OBJECT_KINDS = {"stairs": RG_OBJ_STAIRS, "gold": RG_OBJ_GOLD, "door": RG_OBJ_DOOR, "frontier": RG_OBJ_FRONTIER}   # joined with '+' in a kinds string
+OBJECT_COLS = ("kind", "dx", "dy", "walk", "x", "y", "cheb", "zero")           # the int16 columns of an object-table row (rg_objects)
+OBJECT_COUNT_COLS = ("stairs", "gold", "door", "frontier")                     # the int32 count words, one per kind bit
 EPISODE_REC = [("serial", "<u4"), ("env", "<i4"), ("ret", "<f4"), ("length", "<i4"), ("depth", "<i4"), ("cause", "<u4"), ("scout", "<i4"), ("zero", "<u4")]  # rg_episode_rec
 
 _lib = None
@@ -64,7 +68,7 @@ _INT_FUNCS = (
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
     "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
-    "rg_monsters", "rg_monsters_host",
+    "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
 )
 
 
@@ -136,6 +140,7 @@ def load_library():
         "rg_episode_log_read": [vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)], "rg_scout_host": [vp, i32, i32, vp, C.POINTER(i32)],
         "rg_monsters": [vp, u32, i32, vp, vp],
         "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
+        "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
@@ -143,7 +148,7 @@ def load_library():
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
                 "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
                 "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
-                "rg_monsters", "rg_monsters_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -310,6 +315,26 @@ def _monster_args(mode, cap):
     if not 1 <= cap <= RG_MON_MAX_CAP:
         raise ValueError("cap must be an int in 1 .. %d, got %r" % (RG_MON_MAX_CAP, cap))
     return MONSTER_MODES[mode], cap
+
+
+def _object_args(kinds="stairs+gold+door", known=False, secrets=False, cap=8):
+    """(kinds, mode, cap) of rg_objects.  kinds: names of OBJECT_KINDS joined with '+' ("frontier" with known=True only); known / secrets: rg_route's mode
+    bits; cap: the rows of the table, 1 .. RG_OBJ_MAX_CAP."""
+    names = kinds.split("+") if isinstance(kinds, str) else [None]
+    if any(k not in OBJECT_KINDS for k in names):
+        raise ValueError("kinds must be names of %s joined with '+', got %r" % (", ".join(repr(k) for k in OBJECT_KINDS), kinds))
+    word = 0
+    for k in names:
+        word |= OBJECT_KINDS[k]
+    if (word & RG_OBJ_FRONTIER) and not known:
+        raise ValueError("the kind 'frontier' needs known=True: the frontier is of the player's own map")
+    try:
+        cap = operator.index(cap)
+    except TypeError:
+        cap = -1
+    if not 1 <= cap <= RG_OBJ_MAX_CAP:
+        raise ValueError("cap must be an int in 1 .. %d, got %r" % (RG_OBJ_MAX_CAP, cap))
+    return word, (ROUTE_SECRETS if secrets else 0) | (ROUTE_KNOWN if known else 0), cap
 
 
 def _path_goals(goal, with_cells=False):
@@ -491,6 +516,26 @@ class _Handle:
         out = np.empty(nbytes, np.uint8)
         self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
         return out[:tb].view(np.int16).reshape(self.n, cap, RG_MON_COLS).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
+
+    def object_tables(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
+        """(table i16 [n, cap, 8], count i32 [n, 4]) of rg_objects (_object_args names the arguments): into the device scratch buffer the handle keeps,
+        one rg_dev_read."""
+        kw, mode, cap = _object_args(kinds, known, secrets, cap)
+        tb = self.n * cap * 16
+        nbytes = tb + self.n * 16
+        if self._mask_dev is None or self._mask_dev[1] < nbytes:
+            if self._mask_dev is not None:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
+                self._mask_dev = None
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._mask_dev = (p.value, nbytes)
+        base = self._mask_dev[0]  # table i16 [n][cap][8], then count i32 [n][4]: both on multiples of 16 bytes
+        self.check(self.L.rg_objects(self.h, kw, mode, cap, C.c_void_p(base), C.c_void_p(base + tb)))
+        out = np.empty(nbytes, np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
+        return out[:tb].view(np.int16).reshape(self.n, cap, RG_OBJ_COLS).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
 
     def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
         """(keys u8 [n], dist i32 [n], tier u8 [n]) of rg_route (_route_args names the arguments): into the device scratch buffer the handle keeps, one
@@ -929,6 +974,13 @@ class GameState:
         table, threat = self._h.monster_tables(mode, cap)
         return table[0], threat[0]
 
+    def objects(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
+        """(table numpy i16 [cap, 8], count numpy i32 [4]): the stairs, gold, doors and (known=True) frontier cells of this game's level as rows of
+        OBJECT_COLS, ordered by the number of moves it takes to walk there, and the number of cells of each kind (not part of the reference's API;
+        rg_objects -- without known=True it is privileged: it lists what the player has not discovered)."""
+        table, count = self._h.object_tables(kinds, known, secrets, cap)
+        return table[0], count[0]
+
     def save_state(self):
         """The running game as a state record (bytes; layout: include/rogue_gym_hip.h rg_state_save).  The key log goes with it, so dump_history
         after a load_state dumps the saved episode's keys."""
@@ -1004,6 +1056,10 @@ class ParallelGameState:
     def monster_tables(self, mode="shown", cap=4):
         """(table numpy i16 [n, cap, 8], threat numpy i32 [n, 4]) of rg_monsters (not part of the reference's API; GameState.monsters names the arguments)."""
         return self._h.monster_tables(mode, cap)
+
+    def object_tables(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
+        """(table numpy i16 [n, cap, 8], count numpy i32 [n, 4]) of rg_objects (not part of the reference's API; GameState.objects names the arguments)."""
+        return self._h.object_tables(kinds, known, secrets, cap)
 
     def dump_config(self, env=0):
         buf = C.create_string_buffer(1 << 16)
