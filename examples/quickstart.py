@@ -176,3 +176,17 @@ print("HipVecRogueEnv(objects='known'): %.0f gold per env in 200 option steps, d
       % (gold.mean().item(), venv.status[:, 0].float().mean().item(), e, venv.object_count[e].tolist(),
          [dict(zip(venv.OBJECT_COLS[:6], r[:6])) for r in venv.objects[e].tolist() if r[0]]))
 venv.close()
+
+# 3l. pixels: the player-centred 11 x 11 window drawn through the built-in 8 x 8 tileset, 88 x 88 gray, kept current beside `obs` (what a CNN agent reads after
+#     `.float() / 255`), and a few rgb_array frames -- a mosaic of six envs per frame -- written as .npy for a video writer ---------------------------------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(256)], max_steps=1000, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0,
+                      pixels="gray", pixel_crop=5)
+frames = []
+for t in range(40):
+    venv.step_keys(venv.sample_keys(seed=2))
+    if t % 10 == 9:
+        frames.append(venv.frame(range(6), cols=3).cpu().numpy())        # uint8 [2 * 128, 3 * 256, 3]
+np.save("rogue_frames.npy", np.stack(frames))
+print("HipVecRogueEnv(pixels='gray', pixel_crop=5): pixels %s %s, %.1f %% of the pixels are ink (the paper's luminance is 17); wrote %d frames %s to rogue_frames.npy"
+      % (tuple(venv.pixels.shape), venv.pixels.dtype, 100 * (venv.pixels > 17).float().mean().item(), len(frames), frames[0].shape))
+venv.close()

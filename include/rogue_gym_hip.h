@@ -214,6 +214,46 @@ int rg_obs_crop_typed(rg_t *h, int kind, int dtype, int radius_y, int radius_x, 
 int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist,
                            void *out_dev, int32_t *centers_dev);
 
+/* PIXELS: the screen, or the player-centred window, rendered through a tileset -- NLE's `pixel`, MiniHack's `pixel_crop`, Gym's rgb_array frame.
+ * A tileset is two tables: a monochrome bitmap font u8 [256][th] (glyphs 8 pixels wide and th rows high, RG_TILE_MIN_H <= th <= RG_TILE_MAX_H; bit 7 of
+ * a row byte is the leftmost pixel) and a palette u8 [257][3], the RGB ink of glyph byte g, entry 256 the paper.  With g the glyph of cell (y, x) and
+ * ink = (font[g][py] >> (7 - px)) & 1:
+ *   channels 3 (RGB):  out[e][c][y*th + py][x*8 + px] = ink ? palette[g][c] : palette[256][c]
+ *   channels 1 (gray): the same with lum(r, g, b) = (77 r + 150 g + 29 b + 128) >> 8 in place of the three values (integer: host and device agree to the bit).
+ * The glyph is the screen mirror byte of the cell after pending Redraws are drawn -- the byte rg_obs_typed kind 2 maps to a symbol id.  The output is u8,
+ * planar.  There is no float form (a learner does .float() / 255 in its first layer), no tile wider than 8 pixels and no full-colour tile image: a
+ * caller who wants another look passes another font and palette.
+ *   rg_tileset_default (stateless, needs no device): the built-in tileset -- th = 8, an 8 x 8 font for 0x21 .. 0x7E with every other byte blank (font is
+ *     filled as [256][8] and zero up to 256 * 16 bytes), and a palette that tells walls, doors, passages, floor, gold, stairs, the player and monsters apart
+ *     on a dark paper.  Any of the three pointers may be NULL.
+ *   rg_tileset_set: uploads a tileset to handle-owned device memory (allocated at the first call; the call waits for the handle's stream).  NULL font_host /
+ *     palette_host mean the built-in's (th is then taken from the built-in font).  th outside 8 .. 16 is refused.  A handle with config groups shares one
+ *     tileset.  Without a call, the first pixel call sets the built-in.
+ *   rg_obs_pixels: out_dev = u8 [n_env][channels][H*th][W*8], the whole screen.  Refuses handles with config groups or mixed sizes, as rg_obs_typed does.
+ *   rg_obs_pixels_crop: out_dev = u8 [n_env][channels][(2*radius_y+1)*th][(2*radius_x+1)*8], rg_obs_crop's window (the same radius range, the same
+ *     centers_dev).  A window cell outside the screen is the glyph ' ' THROUGH the tileset (a font that gives ' ' ink shows it in the padding): the crop is
+ *     bit-identical to slicing the full pixel image padded with ' ' cells.  Serves config groups and mixed sizes, as rg_obs_crop_typed does.  An 11 x 11
+ *     window of 8 x 8 tiles is 88 x 88 pixels, 7 744 bytes per env in gray.
+ * Side effects are those of rg_obs_crop_typed: pending Redraws are drawn first, history stale / lag rules unchanged, a bound tensor (rg_obs_bind) is left as
+ * it is and encoded in full by its next call -- a handle that makes only pixel calls has the same mirrors and flag words, step for step, as one that
+ * makes only rg_obs_crop calls.  The pass is timing kernel 2 (rg_timing_*), like the other observation passes.
+ * Refused, non-zero with a message naming the entry point and the argument, before anything is launched or stepped: channels not 1 or 3; radii outside
+ * rg_obs_crop's range; out_dev null or not 16-byte aligned.
+ * rg_step_obs_pixels / rg_step_obs_pixels_crop = rg_step + the pass in one trip through the binding; a refused call does not step.
+ * rg_pixels_host (stateless, needs no device): the rule on the CPU for ONE screen u8 [H][W] of arbitrary bytes, 1 <= H <= 48, 1 <= W <= 160; out as above
+ *   with n_env = 1.  radius_y < 0: the whole screen (cy, cx, radius_x unused); else the window around (cy, cx), which must be a cell of the screen.  NULL
+ *   font / palette: the built-in's.  A refused call writes nothing. */
+#define RG_TILE_MIN_H 8
+#define RG_TILE_MAX_H 16
+int rg_tileset_default(int *th, uint8_t *font /*[256][16]*/, uint8_t *palette /*[257][3]*/);
+int rg_tileset_set(rg_t *h, int th, const uint8_t *font_host, const uint8_t *palette_host);
+int rg_obs_pixels(rg_t *h, int channels, uint8_t *out_dev);
+int rg_obs_pixels_crop(rg_t *h, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev);
+int rg_step_obs_pixels(rg_t *h, const uint8_t *keys, int keys_on_device, int channels, uint8_t *out_dev);
+int rg_step_obs_pixels_crop(rg_t *h, const uint8_t *keys, int keys_on_device, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev);
+int rg_pixels_host(int th, const uint8_t *font, const uint8_t *palette, int channels, int H, int W, const uint8_t *screen, int cy, int cx, int radius_y, int radius_x,
+                   uint8_t *out);
+
 /* LEGAL-ACTION MASKS: which keys would do anything for each env right now, and one key per env drawn uniformly among those, on the device.
  * The rule is the reference's own test, which neither its Python surface nor the screen mirror gives away: Dungeon::can_move_player
  * (core/src/dungeon/mod.rs:79) -> Floor::can_move_impl as the player (floor.rs:169-182), which move_player asks before anything else (actions.rs:168-231).

@@ -22,6 +22,7 @@
 #include "rg_episode.h"
 #include "rg_monsters.h"
 #include "rg_objects.h"
+#include "rg_pixels.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
 // need the RCCL development headers either.  (ABI of nccl.h / rccl.h 2.x: ncclUniqueId = 128 opaque bytes passed by value, ncclComm_t an opaque
@@ -64,6 +65,8 @@ int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, 
                  uint32_t *err_any, hipStream_t st);
 int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, void *out, int32_t *centers,
                    uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_pixels(const RgState *S, const RgConfig *c, const uint8_t *tiles, int th, int channels, int ry, int rx, uint8_t *out, int32_t *centers, hipStream_t st, hipEvent_t ev0,
+               hipEvent_t ev1);
 void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
                      hipEvent_t ev0, hipEvent_t ev1);
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
@@ -166,6 +169,8 @@ struct rg_handle {
     RgEpisode ep = {};
     uint32_t ep_serial = 0;                            // update / cut calls since the enable
     int32_t *ep_ids = nullptr;                         // [n] a cut's host-side env ids, uploaded
+    // the tileset of the pixel passes (rg_tileset_set; rg_pixels.h): the font, then the ink table; allocated at the first call.  Config groups read the parent's
+    uint8_t *tiles = nullptr; int tile_th = 0;
 };
 
 #define RG_TIMING_MAX 4096
@@ -996,6 +1001,81 @@ int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int
                            void *out_dev, int32_t *centers_dev) {
     if (crop_typed_check(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
     return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
+}
+// Pixels (rg_pixels.hip; the rule: rg_pixels.h).  pixels_check: every refusal, before anything is launched (or stepped); radius_y < 0 = the whole screen.
+int rg_tileset_default(int *th, uint8_t *font, uint8_t *palette) { rg_px_default(th, font, palette); return 0; }
+int rg_tileset_set(rg_t *h, int th, const uint8_t *font_host, const uint8_t *palette_host) {
+    std::vector<uint8_t> blob(RG_PX_FONT_BYTES + RG_PX_TAB_BYTES, 0), dfont(RG_PX_FONT_BYTES), dpal(257 * 3);
+    int dth;
+    rg_px_default(&dth, dfont.data(), dpal.data());
+    if (!font_host) { font_host = dfont.data(); th = dth; }
+    if (!palette_host) palette_host = dpal.data();
+    if (th < RG_TILE_MIN_H || th > RG_TILE_MAX_H) {
+        h->err = "rg_tileset_set: th must satisfy " + std::to_string(RG_TILE_MIN_H) + " <= th <= " + std::to_string(RG_TILE_MAX_H) + ", got " + std::to_string(th);
+        return 1;
+    }
+    memcpy(blob.data(), font_host, 256 * (size_t)th);
+    rg_px_tables(palette_host, blob.data() + RG_PX_FONT_BYTES);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->tiles && !dev_alloc(h, &h->tiles, blob.size())) return 1;
+    // a pass in flight may still read the old tables (the groups' passes on their own streams too): wait, then copy before returning
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (rg_handle *sh : h->sub) HIPCHK(h, hipStreamSynchronize(sh->stream));
+    HIPCHK(h, hipMemcpy(h->tiles, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    h->tile_th = th;
+    return 0;
+}
+static int pixels_check(rg_t *h, const char *what, bool crop, int channels, int radius_y, int radius_x, const void *out_dev) {
+    const std::string w = std::string(what) + ": ";
+    if (channels != 1 && channels != 3) { h->err = w + "channels must be 1 (gray) or 3 (RGB), got " + std::to_string(channels); return 1; }
+    if (crop && (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1)) {
+        h->err = w + "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) + ", got (" +
+                 std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
+        return 1;
+    }
+    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    if (!crop && (!h->sub.empty() || h->mixed)) { h->err = w + "not for a handle with config groups or mixed sizes (rg_obs_pixels_crop serves them)"; return 1; }
+    return 0;
+}
+static int pixels_launch(rg_t *h, const uint8_t *tiles, int th, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
+    if (!h->sub.empty()) {  // every group renders its envs straight into the handle's tensor (RgState::ext), as rg_obs_crop_typed
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, pixels_launch(sh, tiles, th, channels, radius_y, radius_x, out_dev, centers_dev));
+        return 0;
+    }
+    if (flush_render(h)) return 1;  // (rg_obs_crop's rule: pending Redraws drawn by k_render, a bound observation tensor re-encoded in full by its next call)
+    {
+        TimedLaunch t(h, 2, true);
+        if (!rgk_pixels(&h->S, &h->cfg, tiles, th, channels, radius_y, radius_x, out_dev, centers_dev, h->stream, t.start_ev(), t.stop_ev())) {
+            t.cancel();
+            h->err = "rg_obs_pixels: image too large";
+            return 1;
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+static int pixels_checked(rg_t *h, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->tiles && rg_tileset_set(h, 0, nullptr, nullptr)) return 1;  // (no rg_tileset_set so far: the built-in)
+    return pixels_launch(h, h->tiles, h->tile_th, channels, radius_y, radius_x, out_dev, centers_dev);
+}
+int rg_obs_pixels(rg_t *h, int channels, uint8_t *out_dev) {
+    return pixels_check(h, "rg_obs_pixels", false, channels, -1, 0, out_dev) ? 1 : pixels_checked(h, channels, -1, 0, out_dev, nullptr);
+}
+int rg_obs_pixels_crop(rg_t *h, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
+    return pixels_check(h, "rg_obs_pixels_crop", true, channels, radius_y, radius_x, out_dev) ? 1 : pixels_checked(h, channels, radius_y, radius_x, out_dev, centers_dev);
+}
+int rg_step_obs_pixels(rg_t *h, const uint8_t *keys, int keys_on_device, int channels, uint8_t *out_dev) {
+    if (pixels_check(h, "rg_step_obs_pixels", false, channels, -1, 0, out_dev)) return 1;
+    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : pixels_checked(h, channels, -1, 0, out_dev, nullptr);
+}
+int rg_step_obs_pixels_crop(rg_t *h, const uint8_t *keys, int keys_on_device, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
+    if (pixels_check(h, "rg_step_obs_pixels_crop", true, channels, radius_y, radius_x, out_dev)) return 1;
+    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : pixels_checked(h, channels, radius_y, radius_x, out_dev, centers_dev);
+}
+int rg_pixels_host(int th, const uint8_t *font, const uint8_t *palette, int channels, int H, int W, const uint8_t *screen, int cy, int cx, int radius_y, int radius_x,
+                   uint8_t *out) {
+    return rg_px_host(g_create_err, th, font, palette, channels, H, W, screen, cy, cx, radius_y, radius_x, out);
 }
 // Legal-action masks (rg_action_mask.hip; the rule: rg_action_mask.h).  mask_keys_check: the key list of a call, every refusal before anything is launched;
 // on success `list` holds the n_keys keys the call judges.

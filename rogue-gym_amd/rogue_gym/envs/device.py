@@ -18,6 +18,7 @@ from .rogue_env import DungeonType, ImageSetting, RogueEnv, StatusFlag
 
 MONSTER_COLS = inner.MONSTER_COLS  # the int16 columns of a row of HipVecRogueEnv.monsters
 OBJECT_COLS = inner.OBJECT_COLS    # the int16 columns of a row of HipVecRogueEnv.objects
+Tileset = inner.Tileset
 
 
 class _DevArray:
@@ -45,7 +46,8 @@ class HipVecRogueEnv:
                  image_setting: ImageSetting = ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device: Optional[int] = None,
                  persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False,
                  episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4,
-                 objects=None, object_kinds: str = "stairs+gold+door", object_cap: int = 8, object_secrets: bool = False):
+                 objects=None, object_kinds: str = "stairs+gold+door", object_cap: int = 8, object_secrets: bool = False,
+                 pixels=None, pixel_crop=None, tileset=None):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -111,7 +113,16 @@ class HipVecRogueEnv:
         own map only (the cells that are drawn or in view): nothing is privileged.  "all" reads the level itself and is PRIVILEGED, as the guide is.
         object_secrets: the walk goes THROUGH hidden and locked cells, as guide_secrets' routes do.  A row's (y, x) is what route(goal=None, cells=...)
         takes.  It works on every env this class builds, config groups and mixed sizes included.  None: both attributes are None and nothing is added to
-        any call.  object_table() works either way."""
+        any call.  object_table() works either way.
+
+        pixels (opt-in; "gray" or "rgb"): `self.pixels` is a uint8 tensor [N, C, hp, wp] on the device, C = 1 or 3 -- every env's screen drawn through
+        `tileset` (a Tileset: a bitmap font of 8-pixel-wide glyphs and a palette; None = the built-in 8 x 8 one), planar, hp = H * th and wp = W * 8
+        (rg_obs_pixels).  pixel_crop (None, r or (ry, rx)): the player-centred window instead, hp = (2ry+1) * th and wp = (2rx+1) * 8, cells past the
+        screen edge drawn as ' ' through the tileset, and `self.pixel_center` i32 [N, 2] holds each window's centre (rg_obs_pixels_crop) -- an 11 x 11
+        window of 8 x 8 tiles is 88 x 88 pixels, 7.7 KB per env in gray, the form to train on; the whole-screen RGB image of an 80 x 24 env is 368 KB.
+        With a crop it works on every env this class builds; the whole screen not on batches with config groups or mixed sizes.  Rewritten in place by
+        everything that refreshes `obs`: one launch more per step, no host trip.  A learner does `.float() / 255` itself.  None: both attributes are None
+        and nothing is added to any call.  render_pixels() and frame() work either way."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -194,6 +205,21 @@ class HipVecRogueEnv:
         with torch.cuda.device(self.device):
             self.objects = None if objects is None else torch.zeros((self.num_envs, self._obj_args[2], len(self.OBJECT_COLS)), dtype=torch.int16, device=self.device)
             self.object_count = None if objects is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        if pixels not in (None, "gray", "rgb"):
+            raise ValueError("pixels must be None, 'gray' or 'rgb', got %r" % (pixels,))
+        if pixels is None and pixel_crop is not None:
+            raise ValueError("pixel_crop needs pixels='gray' or 'rgb'")
+        self._px_crop = None if pixel_crop is None else self._crop_radii(pixel_crop)
+        self._px_channels = 0 if pixels is None else 3 if pixels == "rgb" else 1
+        self.tileset = None
+        self.pixels = self.pixel_center = None
+        if tileset is not None or pixels is not None:
+            self.set_tileset(tileset)
+        if pixels is not None:
+            self.pixels = self._pixel_tensor(self.num_envs, self._px_channels, self._px_crop)
+            if self._px_crop is not None:
+                with torch.cuda.device(self.device):
+                    self.pixel_center = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
         self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
@@ -261,6 +287,67 @@ class HipVecRogueEnv:
         out["dropped"] = int(dropped.value)
         return out
 
+    def set_tileset(self, tileset=None):
+        """Give the handle another tileset (rg_tileset_set; None = the built-in): the next pixel pass draws with it.  Waits for the stream.  The tile height
+        decides the shape of `self.pixels`, so an env built with pixels= takes a tileset of the same height only."""
+        ts = Tileset.default() if tileset is None else tileset
+        if not isinstance(ts, Tileset):
+            raise ValueError("tileset must be a Tileset or None, got %r" % (tileset,))
+        if getattr(self, "pixels", None) is not None and ts.th != self.tileset.th:
+            raise ValueError("set_tileset: `pixels` was built for tiles %d rows high, got %d" % (self.tileset.th, ts.th))
+        self._h.check(self._h.L.rg_tileset_set(self._h.h, ts.th, ts.font.ctypes.data, ts.palette.ctypes.data))
+        self.tileset = ts
+
+    def _pixel_tensor(self, n, channels, crop):
+        th = self.tileset.th
+        hc, wc = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
+        with self.torch.cuda.device(self.device):
+            return self.torch.empty((n, channels, hc * th, wc * 8), dtype=self.torch.uint8, device=self.device)
+
+    def _pixel_call(self, channels, crop, out, center):
+        L, h = self._h.L, self._h.h
+        if crop is None:
+            self._h.check(L.rg_obs_pixels(h, channels, C.c_void_p(out.data_ptr())))
+        else:
+            self._h.check(L.rg_obs_pixels_crop(h, channels, crop[0], crop[1], C.c_void_p(out.data_ptr()), None if center is None else C.c_void_p(center.data_ptr())))
+
+    def render_pixels(self, rgb=True, crop=None, tileset=None, out=None):
+        """uint8 [N, C, hp, wp] on the device, C = 3 (rgb) or 1 (gray): every env's screen -- or with crop (r or (ry, rx)) its player-centred window -- drawn
+        through the env's tileset (rg_obs_pixels / rg_obs_pixels_crop).  tileset (optional): a Tileset that replaces the env's from this call on
+        (set_tileset).  out (optional): a contiguous uint8 tensor of that shape on this env's device to write into.  No host trip."""
+        torch = self.torch
+        if tileset is not None or self.tileset is None:
+            self.set_tileset(tileset)
+        crop = None if crop is None else self._crop_radii(crop)
+        channels = 3 if rgb else 1
+        if out is None:
+            out = self._pixel_tensor(self.num_envs, channels, crop)
+        else:
+            hc, wc = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
+            shape = (self.num_envs, channels, hc * self.tileset.th, wc * 8)
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != shape or not out.is_contiguous():
+                raise ValueError("render_pixels: out must be a contiguous uint8 tensor %s on %s" % (list(shape), self.device))
+        self._pixel_call(channels, crop, out, None)
+        return out
+
+    def frame(self, env_ids, cols=None):
+        """One HWC uint8 mosaic [rows * H*th, cols * W*8, 3] on the device of the chosen envs' screens, row-major in the order given, for a video writer
+        (`frame(...).cpu().numpy()`).  cols defaults to ceil(sqrt(k)); cells past the last env are black.  Built in torch from render_pixels."""
+        torch = self.torch
+        ids = torch.as_tensor(np.asarray(env_ids, dtype=np.int64).reshape(-1), device=self.device) if not isinstance(env_ids, torch.Tensor) else env_ids.reshape(-1).to(self.device, torch.int64)
+        k = int(ids.numel())
+        if k == 0:
+            raise ValueError("frame: no envs")
+        cols = int(np.ceil(np.sqrt(k))) if cols is None else operator.index(cols)
+        if cols < 1:
+            raise ValueError("frame: cols must be >= 1, got %r" % (cols,))
+        rows = (k + cols - 1) // cols
+        img = self.render_pixels(rgb=True)[ids]                      # [k, 3, hp, wp]
+        hp, wp = int(img.shape[2]), int(img.shape[3])
+        grid = torch.zeros((rows * cols, 3, hp, wp), dtype=torch.uint8, device=self.device)
+        grid[:k] = img
+        return grid.view(rows, cols, 3, hp, wp).permute(0, 3, 1, 4, 2).reshape(rows * hp, cols * wp, 3).contiguous()
+
     @staticmethod
     def _crop_radii(crop):
         try:
@@ -321,6 +408,8 @@ class HipVecRogueEnv:
         """After `obs` was refreshed: nothing is pending then, so the crop passes only read the mirrors (and a bound `obs` stays valid)."""
         for v in self._views:
             self._encode_view(v)
+        if self.pixels is not None:
+            self._pixel_call(self._px_channels, self._px_crop, self.pixels, self.pixel_center)
         if self._mask_u8 is not None:
             self._h.check(self._h.L.rg_action_mask(self._h.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0))
         if self._guide_goals:

@@ -12,7 +12,7 @@ from typing import Dict, Iterable, List, Tuple, Union
 
 import numpy as np
 
-from rogue_gym_python._rogue_gym import ParallelGameState, StateBatch
+from rogue_gym_python._rogue_gym import ParallelGameState, StateBatch, Tileset
 
 from ._gym_compat import Discrete
 from .rogue_env import ImageSetting, RogueEnv
@@ -67,6 +67,13 @@ class ParallelRogueEnv:
     def images(self, states: StateBatch = None) -> np.ndarray:
         """[N, C, H, W] float32 image of every env under `image_setting` (default: the states of the last step)."""
         return self.image_setting.expand_batch(self.states if states is None else states)
+
+    def render_frames(self, states: StateBatch = None, tileset=None):
+        """RogueEnv.render("rgb_array") for the whole batch: uint8 [N, H*th, W*8, 3] (a list of per-env frames when the batch mixes screen sizes)."""
+        ts = Tileset.default() if tileset is None else tileset
+        screens = (self.states if states is None else states).screen
+        frames = [np.ascontiguousarray(ts.render(scr, rgb=True).transpose(1, 2, 0)) for scr in screens]
+        return frames if isinstance(screens, list) else np.stack(frames)
 
     def action_masks(self) -> np.ndarray:
         """bool [N, ACTION_LEN]: entry [i, a] says whether ACTIONS[a] would do anything for env i now (RogueEnv.action_mask for the whole batch)."""

@@ -125,7 +125,7 @@ _ACTION_TABLE = (
 class RogueEnv(Env):
     """One Rogue game (GameState: no auto-reset; after death every further action key raises)."""
 
-    metadata = {"render.modes": ["human", "ascii"]}
+    metadata = {"render.modes": ["human", "ascii", "rgb_array"]}
     SYMBOLS = list(_FIXED_SYMBOLS) + [chr(ord("A") + i) for i in range(26)]
     ACTION_MEANINGS = dict(_ACTION_TABLE)
     ACTIONS = [key for key, _ in _ACTION_TABLE]
@@ -246,8 +246,12 @@ class RogueEnv(Env):
         state = self.result = self.game.prev()
         return state
 
-    def render(self, mode: str = "human", close: bool = False) -> None:
-        """Prints the screen and the status line (both modes)."""
+    def render(self, mode: str = "human", close: bool = False, tileset=None):
+        """"human" / "ascii": prints the screen and the status line.  "rgb_array": returns the screen as a uint8 frame [H*th, W*8, 3] drawn through `tileset`
+        (a Tileset; None = the built-in 8 x 8 one) -- the rule of rg_obs_pixels, on the CPU; the status line is not part of the frame."""
+        if mode == "rgb_array":
+            ts = rogue_gym_inner.Tileset.default() if tileset is None else tileset
+            return np.ascontiguousarray(ts.render(self.result._map, rgb=True).transpose(1, 2, 0))
         print(repr(self.result))
 
     def replay(self, interval_ms: int = 100) -> None:

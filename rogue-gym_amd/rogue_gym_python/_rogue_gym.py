@@ -69,6 +69,7 @@ _INT_FUNCS = (
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
     "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
     "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
+    "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host",
 )
 
 
@@ -141,6 +142,10 @@ def load_library():
         "rg_monsters": [vp, u32, i32, vp, vp],
         "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
         "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
+        "rg_tileset_default": [C.POINTER(i32), vp, vp], "rg_tileset_set": [vp, i32, vp, vp],
+        "rg_obs_pixels": [vp, i32, vp], "rg_obs_pixels_crop": [vp, i32, i32, i32, vp, vp],
+        "rg_step_obs_pixels": [vp, vp, i32, i32, vp], "rg_step_obs_pixels_crop": [vp, vp, i32, i32, i32, i32, vp, vp],
+        "rg_pixels_host": [i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp],
     }
     # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
     # exports every symbol of the header, tests/test_cabi_load.py)
@@ -148,7 +153,8 @@ def load_library():
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
                 "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
                 "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
-                "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
+                "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
+                "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -167,6 +173,47 @@ def load_library():
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+class Tileset:
+    """A tileset of the pixel passes (rg_obs_pixels): `font` uint8 [256, th], a monochrome bitmap font of glyphs 8 pixels wide and th rows high (8 <= th <= 16;
+    bit 7 of a row byte is the leftmost pixel), and `palette` uint8 [257, 3], the RGB ink of glyph byte g, entry 256 the paper.  Both may be given as numpy
+    arrays or torch tensors and are kept as contiguous numpy arrays."""
+
+    def __init__(self, font, palette):
+        font, palette = (np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)) for t in (font, palette))
+        if font.dtype != np.uint8 or font.ndim != 2 or font.shape[0] != 256 or not 8 <= font.shape[1] <= 16:
+            raise ValueError("Tileset: font must be uint8 [256, th] with 8 <= th <= 16, got %s %s" % (font.dtype, font.shape))
+        if palette.dtype != np.uint8 or palette.shape != (257, 3):
+            raise ValueError("Tileset: palette must be uint8 [257, 3], got %s %s" % (palette.dtype, palette.shape))
+        self.font, self.palette = font, palette
+
+    @property
+    def th(self):
+        return int(self.font.shape[1])
+
+    @classmethod
+    def default(cls):
+        """The built-in tileset (rg_tileset_default): an 8 x 8 font for 0x21 .. 0x7E and a palette on a dark paper."""
+        L = load_library()
+        th, font, pal = C.c_int(0), np.zeros(256 * 16, np.uint8), np.zeros((257, 3), np.uint8)
+        if L.rg_tileset_default(C.byref(th), font.ctypes.data, pal.ctypes.data):
+            raise RuntimeError("Error in rogue-gym: " + L.rg_last_error(None).decode())
+        return cls(font[:256 * th.value].reshape(256, th.value).copy(), pal)
+
+    def render(self, screen, rgb=True, center=None, crop=None):
+        """The rule on the CPU (rg_pixels_host) for one screen uint8 [H, W]: uint8 [C, H*th, W*8], or with crop = (ry, rx) and center = (cy, cx) the window
+        [C, (2ry+1)*th, (2rx+1)*8]."""
+        L = load_library()
+        screen = np.ascontiguousarray(screen, dtype=np.uint8)
+        H, W = screen.shape
+        ch = 3 if rgb else 1
+        ry, rx = (-1, 0) if crop is None else crop
+        cy, cx = (0, 0) if center is None else center
+        out = np.zeros((ch, (H if crop is None else 2 * ry + 1) * self.th, (W if crop is None else 2 * rx + 1) * 8), np.uint8)
+        if L.rg_pixels_host(self.th, self.font.ctypes.data, self.palette.ctypes.data, ch, H, W, screen.ctypes.data, int(cy), int(cx), int(ry), int(rx), out.ctypes.data):
+            raise RuntimeError("Error in rogue-gym: " + L.rg_last_error(None).decode())
+        return out
 
 
 def _default_device():
