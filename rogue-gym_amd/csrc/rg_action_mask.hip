@@ -7,11 +7,6 @@
 #include "rg_device.h"
 #include "rg_action_mask.h"
 
-// LDS-only workgroup barrier (rg_obs.hip): the blocks here are one wave
-static __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 // The key list as kernel arguments: the key bytes, eight per word, and each key's bit of rg_legal_bits, sixteen per word.  Read by shifts, not by
 // indexing, so the list stays in scalar registers whatever its length.
 struct MaskKeys {
@@ -97,11 +92,7 @@ void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, i
     }
     const MaskKeys K = {kw[0], kw[1], kw[2], kw[3], bw[0], bw[1]};
     const int blocks = (S->n + WAVE - 1) / WAVE;
-    if (ev0 || ev1)
-        hipExtLaunchKernelGGL(k_action_mask, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, 0, S->p_pos, S->flags, S->cell, S->ext, S->n, (int)c->width, (int)c->height, n_keys, K,
-                              mask, sample, seed, draw);
-    else
-        hipLaunchKernelGGL(k_action_mask, dim3(blocks), dim3(WAVE), 0, st, S->p_pos, S->flags, S->cell, S->ext, S->n, (int)c->width, (int)c->height, n_keys, K, mask, sample,
-                           seed, draw);
+    rg_launch(k_action_mask, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, S->p_pos, S->flags, S->cell, S->ext, S->n, (int)c->width, (int)c->height, n_keys, K, mask, sample, seed,
+              draw);
 }
 }

@@ -61,8 +61,6 @@ int rgk_step_enc_helpers(int n, int want);
 void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any, hipStream_t st, hipEvent_t ev0,
                   hipEvent_t ev1);
-int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
-                 uint32_t *err_any, hipStream_t st);
 int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, void *out, int32_t *centers,
                    uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 int rgk_pixels(const RgState *S, const RgConfig *c, const uint8_t *tiles, int th, int channels, int ry, int rx, uint8_t *out, int32_t *centers, hipStream_t st, hipEvent_t ev0,
@@ -176,7 +174,7 @@ struct rg_handle {
 #define RG_TIMING_MAX 4096
 struct TimedLaunch {  // times one kernel launch with an event pair when timing is on
     // Two forms.  bracket(): hipEventRecord before and after the launch -- the pair then also contains the marker packets' own processing and the
-    // gap to the neighbouring kernels (~5-10 us around an 80 us kernel).  ext(): the pair is handed to hipExtLaunchKernelGGL, which stamps it with the
+    // gap to the neighbouring kernels (~5-10 us around an 80 us kernel).  ext(): the pair is handed to the launch itself (rg_device.h rg_launch), which stamps it with the
     // dispatch's own begin / end -- the same clock rocprofv3 --kernel-trace reports; used for the two kernels of the step.
     rg_handle *h; int k; bool on, ext_;
     TimedLaunch(rg_handle *h_, int k_, bool ext = false) : h(h_), k(k_), on(false), ext_(ext) {
@@ -875,34 +873,6 @@ int rg_obs_bind(rg_t *h, int kind, uint32_t status_flag, int with_hist, float *o
     h->bound_out = out_dev; h->bound_kind = kind; h->bound_valid = false; h->bound_steps = 0;
     return 0;
 }
-int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_flag, int with_hist, float *out_dev, int32_t *centers_dev) {
-    if (kind != 0 && kind != 1) { h->err = "rg_obs_crop: kind must be 0 (gray) or 1 (symbol), got " + std::to_string(kind); return 1; }
-    if (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1) {
-        h->err = "rg_obs_crop: radii must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) +
-                 ", got (" + std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
-        return 1;
-    }
-    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = "rg_obs_crop: out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group crops its envs straight into the handle's tensor (RgState::ext): the window has one size for every env,
-                            // so a mixed-size batch is served too
-        for (rg_handle *sh : h->sub)
-            if (kind && sh->cfg.symbols > h->planes_sym) {
-                h->err = "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
-                         "), which sets the channel count (python/src/lib.rs:281-285)";
-                return 1;
-            }
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, rg_obs_crop(sh, kind, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev));
-        return 0;
-    }
-    if (flush_render(h)) return 1;  // (pending Redraws drawn by k_render: a bound observation tensor is then re-encoded in full by its next call)
-    if (!rgk_obs_crop(&h->S, &h->cfg, kind, radius_y, radius_x, status_flag & 0x1ffu, with_hist ? 1 : 0, h->planes_sym, out_dev, centers_dev, h->d_err, h->stream)) {
-        h->err = "rg_obs_crop: window too large";
-        return 1;
-    }
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
 // Typed observations (f16 / bf16 images, u8 symbol ids).  typed_check: every refusal, before anything is launched (or stepped).
 int rg_obs_dtype_bytes(int dtype) { return dtype == RG_OBS_F32 ? 4 : (dtype == RG_OBS_F16 || dtype == RG_OBS_BF16) ? 2 : dtype == RG_OBS_U8 ? 1 : -1; }
 static int typed_check(rg_t *h, const char *what, int kind, int dtype, uint32_t status_flag, const void *out_dev) {
@@ -954,20 +924,39 @@ int rg_step_obs_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind
     if (typed_check(h, "rg_step_obs_typed", kind, dtype, status_flag, out_dev)) return 1;
     return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : obs_typed_checked(h, kind, dtype, status_flag, with_hist, out_dev);
 }
-// The typed crop (rg_crop_typed.hip).  crop_typed_check: every refusal, before anything is launched (or stepped).
-static int crop_typed_check(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, const void *out_dev) {
+// The window passes: player-centred crops (rg_crop_typed.hip) and pixels (rg_pixels.hip).  window_check: the refusals they share, `w` being the entry
+// point's name and a colon; crop = false: the whole screen, no radii.
+static int window_check(rg_t *h, const std::string &w, bool crop, int radius_y, int radius_x, const void *out_dev) {
+    if (crop && (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1)) {
+        h->err = w + "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) + ", got (" +
+                 std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
+        return 1;
+    }
+    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    return 0;
+}
+// window_launch(leaf): leaf enqueues one kernel on a handle without groups and returns 0, or sets that handle's error and returns 1; on a handle with config
+// groups every group writes its envs straight into the handle's tensor (RgState::ext): the window has one size for every env, so a mixed-size batch is served too.
+// The mirrors are made current first (pending Redraws drawn by k_render: a bound observation tensor is then re-encoded in full by its next call).
+extern "C++" template <class Leaf> static int window_launch(rg_t *h, Leaf leaf) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sub.empty()) {
+        for (rg_handle *sh : h->sub) SUBCHK(h, sh, window_launch(sh, leaf));
+        return 0;
+    }
+    if (flush_render(h) || leaf(h)) return 1;
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+// The crops.  crop_check: every refusal, before anything is launched (or stepped).
+static int crop_check(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, const void *out_dev) {
     const std::string w = std::string(what) + ": ";
     if (kind < 0 || kind > 2) { h->err = w + "kind must be 0 (gray), 1 (symbol) or 2 (symbol ids), got " + std::to_string(kind); return 1; }
     if (rg_obs_dtype_bytes(dtype) < 0) { h->err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1), RG_OBS_BF16 (2) or RG_OBS_U8 (3), got " + std::to_string(dtype); return 1; }
     if (kind == 2 && dtype != RG_OBS_U8) { h->err = w + "kind 2 (symbol ids) takes dtype RG_OBS_U8 only, got dtype " + std::to_string(dtype); return 1; }
     if (kind != 2 && dtype == RG_OBS_U8) { h->err = w + "dtype RG_OBS_U8 is for kind 2 (symbol ids) only, got kind " + std::to_string(kind); return 1; }
     if (kind == 2 && (status_flag & 0x1ffu)) { h->err = w + "status_flag must be 0 for kind 2 (status values do not fit a byte; read the status mirror)"; return 1; }
-    if (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1) {
-        h->err = w + "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) + ", got (" +
-                 std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
-        return 1;
-    }
-    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    if (window_check(h, w, true, radius_y, radius_x, out_dev)) return 1;
     if (kind == 1)  // (kind 2 has no channel count: each env is judged by its own group's symbols)
         for (rg_handle *sh : h->sub)
             if (sh->cfg.symbols > h->planes_sym) {
@@ -977,30 +966,30 @@ static int crop_typed_check(rg_t *h, const char *what, int kind, int dtype, int 
             }
     return 0;
 }
-static int crop_typed_checked(rg_t *h, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
-    if (dtype == RG_OBS_F32) return rg_obs_crop(h, kind, radius_y, radius_x, status_flag, with_hist, static_cast<float *>(out_dev), centers_dev);
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->sub.empty()) {  // every group crops its envs straight into the handle's tensor (RgState::ext), as rg_obs_crop
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, crop_typed_checked(sh, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev));
-        return 0;
-    }
-    if (flush_render(h)) return 1;  // (rg_obs_crop's rule: pending Redraws drawn by k_render, a bound observation tensor re-encoded in full by its next call)
-    if (!rgk_crop_typed(&h->S, &h->cfg, kind, dtype, radius_y, radius_x, status_flag & 0x1ffu, with_hist ? 1 : 0, h->planes_sym, out_dev, centers_dev, h->d_err, h->stream,
-                        nullptr, nullptr)) {
-        h->err = "rg_obs_crop_typed: window too large";
+static int crop_checked(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
+    const int planes_sym = h->planes_sym;  // (the handle's one-hot depth, for every group)
+    return window_launch(h, [=](rg_t *l) {
+        if (rgk_crop_typed(&l->S, &l->cfg, kind, dtype, radius_y, radius_x, status_flag & 0x1ffu, with_hist ? 1 : 0, planes_sym, out_dev, centers_dev, l->d_err, l->stream, nullptr,
+                           nullptr))
+            return 0;
+        l->err = std::string(what) + ": window too large";
         return 1;
-    }
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    });
+}
+int rg_obs_crop(rg_t *h, int kind, int radius_y, int radius_x, uint32_t status_flag, int with_hist, float *out_dev, int32_t *centers_dev) {
+    if (kind != 0 && kind != 1) { h->err = "rg_obs_crop: kind must be 0 (gray) or 1 (symbol), got " + std::to_string(kind); return 1; }
+    if (crop_check(h, "rg_obs_crop", kind, RG_OBS_F32, radius_y, radius_x, status_flag, out_dev)) return 1;
+    return crop_checked(h, "rg_obs_crop", kind, RG_OBS_F32, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
 }
 int rg_obs_crop_typed(rg_t *h, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
-    if (crop_typed_check(h, "rg_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
-    return crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
+    if (crop_check(h, "rg_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
+    return crop_checked(h, "rg_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
 }
 int rg_step_obs_crop_typed(rg_t *h, const uint8_t *keys, int keys_on_device, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist,
                            void *out_dev, int32_t *centers_dev) {
-    if (crop_typed_check(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
-    return rg_step_prefix(h, keys, h->S.n, keys_on_device) ? 1 : crop_typed_checked(h, kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
+    if (crop_check(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, out_dev)) return 1;
+    if (rg_step_prefix(h, keys, h->S.n, keys_on_device)) return 1;
+    return crop_checked(h, "rg_step_obs_crop_typed", kind, dtype, radius_y, radius_x, status_flag, with_hist, out_dev, centers_dev);
 }
 // Pixels (rg_pixels.hip; the rule: rg_pixels.h).  pixels_check: every refusal, before anything is launched (or stepped); radius_y < 0 = the whole screen.
 int rg_tileset_default(int *th, uint8_t *font, uint8_t *palette) { rg_px_default(th, font, palette); return 0; }
@@ -1028,36 +1017,21 @@ int rg_tileset_set(rg_t *h, int th, const uint8_t *font_host, const uint8_t *pal
 static int pixels_check(rg_t *h, const char *what, bool crop, int channels, int radius_y, int radius_x, const void *out_dev) {
     const std::string w = std::string(what) + ": ";
     if (channels != 1 && channels != 3) { h->err = w + "channels must be 1 (gray) or 3 (RGB), got " + std::to_string(channels); return 1; }
-    if (crop && (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1)) {
-        h->err = w + "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1) + ", got (" +
-                 std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
-        return 1;
-    }
-    if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
+    if (window_check(h, w, crop, radius_y, radius_x, out_dev)) return 1;
     if (!crop && (!h->sub.empty() || h->mixed)) { h->err = w + "not for a handle with config groups or mixed sizes (rg_obs_pixels_crop serves them)"; return 1; }
     return 0;
 }
-static int pixels_launch(rg_t *h, const uint8_t *tiles, int th, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
-    if (!h->sub.empty()) {  // every group renders its envs straight into the handle's tensor (RgState::ext), as rg_obs_crop_typed
-        for (rg_handle *sh : h->sub) SUBCHK(h, sh, pixels_launch(sh, tiles, th, channels, radius_y, radius_x, out_dev, centers_dev));
-        return 0;
-    }
-    if (flush_render(h)) return 1;  // (rg_obs_crop's rule: pending Redraws drawn by k_render, a bound observation tensor re-encoded in full by its next call)
-    {
-        TimedLaunch t(h, 2, true);
-        if (!rgk_pixels(&h->S, &h->cfg, tiles, th, channels, radius_y, radius_x, out_dev, centers_dev, h->stream, t.start_ev(), t.stop_ev())) {
-            t.cancel();
-            h->err = "rg_obs_pixels: image too large";
-            return 1;
-        }
-    }
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
 static int pixels_checked(rg_t *h, int channels, int radius_y, int radius_x, uint8_t *out_dev, int32_t *centers_dev) {
-    HIPCHK(h, hipSetDevice(h->device));
     if (!h->tiles && rg_tileset_set(h, 0, nullptr, nullptr)) return 1;  // (no rg_tileset_set so far: the built-in)
-    return pixels_launch(h, h->tiles, h->tile_th, channels, radius_y, radius_x, out_dev, centers_dev);
+    const uint8_t *tiles = h->tiles;  // (the handle's tileset, for every group)
+    const int th = h->tile_th;
+    return window_launch(h, [=](rg_t *l) {
+        TimedLaunch t(l, 2, true);
+        if (rgk_pixels(&l->S, &l->cfg, tiles, th, channels, radius_y, radius_x, out_dev, centers_dev, l->stream, t.start_ev(), t.stop_ev())) return 0;
+        t.cancel();
+        l->err = "rg_obs_pixels: image too large";
+        return 1;
+    });
 }
 int rg_obs_pixels(rg_t *h, int channels, uint8_t *out_dev) {
     return pixels_check(h, "rg_obs_pixels", false, channels, -1, 0, out_dev) ? 1 : pixels_checked(h, channels, -1, 0, out_dev, nullptr);

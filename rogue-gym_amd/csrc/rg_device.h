@@ -80,3 +80,24 @@ __device__ __forceinline__ void unpack_rect(uint32_t r, int &x0, int &y0, int &x
     x0 = r & 0xff; y0 = (r >> 8) & 0xff; x1 = (r >> 16) & 0xff; y1 = r >> 24;
 }
 
+// LDS-only workgroup barrier: unlike __syncthreads() it does not drain vmcnt, so global loads requested ahead of it stay in flight
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// one 16-byte piece of a tensor
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+// the 16 bits of T nearest to the finite f32 `f` (ties to even; binary16 overflows to infinity): what torch.Tensor.to(T) gives
+template <int DT>
+__device__ __forceinline__ uint32_t cvt16(float f) {
+    if (DT == RG_OBS_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);  // v_cvt_f16_f32
+    const uint32_t u = __float_as_uint(f);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+// host: one kernel launch.  With an event pair (rg_timing; ev1 alone: a completion event another stream waits for) the dispatch itself stamps the events
+// with its begin and end; without one it is a plain launch.
+template <class... P, class... A>
+static inline void rg_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const A &...args) {
+    if (ev0 || ev1) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, ev0, ev1, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+}
+

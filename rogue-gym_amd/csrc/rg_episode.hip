@@ -8,8 +8,6 @@
 #include "rg_device.h"
 #include "rg_episode.h"
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 #define EP_THREADS 256
 #define EP_GS 16   // lanes per env of the scout instance: four 16-byte loads per lane cover 512 cells, and 8 cells make exactly one byte of `seen`
 

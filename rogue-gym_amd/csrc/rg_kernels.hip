@@ -3284,8 +3284,7 @@ int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const u
     const bool enc = !bnd && S->enc_out && c->width <= 32 && gen_mode_of(c) == 0;  // (the ENC instance below: its helper blocks come last)
     const dim3 grid((parity >= 0 ? STAIR_BLOCKS + nb : nb) + (enc ? S->enc_helpers : 0)), block(WAVE);
     // (ev0 / ev1: optional events stamped with this dispatch's own begin and end -- rg_timing; ev1 alone: the completion event k_regen's stream waits for)
-#define RG_LAUNCH_STEP(K) do { if (ev0 || ev1) hipExtLaunchKernelGGL(K, grid, block, (uint32_t)smem, st, ev0, ev1, 0, *S, SP_dev, *c, keys, use_spares, stage_off, epw, parity); \
-                               else hipLaunchKernelGGL(K, grid, block, smem, st, *S, SP_dev, *c, keys, use_spares, stage_off, epw, parity); } while (0)
+    auto launch = [&](auto kernel) { rg_launch(kernel, grid, block, smem, st, ev0, ev1, *S, SP_dev, *c, keys, use_spares, stage_off, epw, parity); };
     if (gen_mode_of(c) == 2) {
         // the LDS monster table of a > 64-room dungeon (256 B per room and wave) goes beyond the 64 KB a kernel gets by default: raise the kernel's limit once
         // (the attribute is per DEVICE: a process may hold handles on several; a failure stays in hipGetLastError, which rg_step_prefix checks right after)
@@ -3295,13 +3294,12 @@ int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const u
         if (dev < 0 || dev >= 64 || smem > raised[dev]) {
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_step_huge), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess && dev >= 0 && dev < 64) raised[dev] = smem;
         }
-        RG_LAUNCH_STEP(k_step_huge);
-    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) RG_LAUNCH_STEP(k_step_w32<true>); else if (S->enc_out) RG_LAUNCH_STEP((k_step_w32<false, true>)); else RG_LAUNCH_STEP(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
-    else if (n32 && c->width <= 64) RG_LAUNCH_STEP(k_step<1>);                        // ... a 32-column grid with 33..64 rooms (e.g. 32x48 with 8x5) steps here
-    else if (n32) { if (bnd) RG_LAUNCH_STEP((k_step<2, true>)); else RG_LAUNCH_STEP(k_step<2>); }
-    else if (c->width <= 128) RG_LAUNCH_STEP(k_step<3>);
-    else RG_LAUNCH_STEP(k_step<4>);
-#undef RG_LAUNCH_STEP
+        launch(k_step_huge);
+    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) launch(k_step_w32<true>); else if (S->enc_out) launch(k_step_w32<false, true>); else launch(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
+    else if (n32 && c->width <= 64) launch(k_step<1>);                        // ... a 32-column grid with 33..64 rooms (e.g. 32x48 with 8x5) steps here
+    else if (n32) { if (bnd) launch(k_step<2, true>); else launch(k_step<2>); }
+    else if (c->width <= 128) launch(k_step<3>);
+    else launch(k_step<4>);
     return (int)grid.x;
 }
 void rgk_debug_descend(const RgState *S, const RgConfig *c, hipStream_t st) {
@@ -3334,13 +3332,11 @@ void rgk_regen(const RgState *SP, const RgConfig *c, int bulk, int spares, const
 #endif
     const dim3 grid((SP->n + epb - 1) / epb);
     // (ev0 / ev1: optional events stamped with this dispatch's own begin and end -- rg_timing, kernel 4)
-#define RG_LAUNCH_REGEN(K) do { if (ev0 || ev1) hipExtLaunchKernelGGL(K, grid, dim3(WAVE), (uint32_t)smem, st, ev0, ev1, 0, *SP, *c, epb, max_claims, spares); \
-                                else hipLaunchKernelGGL(K, grid, dim3(WAVE), smem, st, *SP, *c, epb, max_claims, spares); } while (0)
+    auto launch = [&](auto kernel) { rg_launch(kernel, grid, dim3(WAVE), smem, st, ev0, ev1, *SP, *c, epb, max_claims, spares); };
     switch (gen_mode_of(c)) {
-    case 0: RG_LAUNCH_REGEN(k_regen<0>); break;
-    case 1: RG_LAUNCH_REGEN(k_regen<1>); break;
-    default: RG_LAUNCH_REGEN(k_regen_huge);
+    case 0: launch(k_regen<0>); break;
+    case 1: launch(k_regen<1>); break;
+    default: launch(k_regen_huge);
     }
-#undef RG_LAUNCH_REGEN
 }
 }

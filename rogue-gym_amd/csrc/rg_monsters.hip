@@ -8,8 +8,6 @@
 #include "rg_device.h"
 #include "rg_monsters.h"
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 #define MON_THREADS 256
 #define MON_BATCH 4   // slots whose words and cell gathers are in flight together
 

@@ -234,9 +234,6 @@ __device__ __forceinline__ bool monster_shown(const RgConfig &c, const ObsTabs *
     return show;
 }
 
-// LDS-only workgroup barrier: unlike __syncthreads() it does not drain vmcnt, so the prefetched global loads of the next env stay in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // GROUPS: the batch is one config group of a handle with several (RgState::ext maps its envs to the handle's env order, and the one-hot depth is the
 // handle's): compiled separately so that the ordinary kernel carries none of it (its 72 registers = 7 waves per SIMD are what its bandwidth rests on)
 // BOUND (rg_obs_bind): `out` is the handle's bound observation tensor and its contents are current up to the last k_step: only the envs that k_step listed
@@ -771,166 +768,6 @@ __global__ void __launch_bounds__(256) k_encode_scalar(const uint8_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_obs_crop: the player-centred crop (rg_obs_crop).  Env e's window is [C][2ry+1][2rx+1], centred on its player cell, of the image the full encode
-// would write, padded with the encoding of ' ' (gray 0, one-hot channel 0, history 0, status planes their constant value).  The mirrors are current
-// (rg_api.cpp flushes the pending render first): this pass only reads them.
-// ---------------------------------------------------------------------------------------------
-// x / d for 0 <= x < 2^30 by a multiply and a shift (m = ceil(2^s / d), s = 30 + ceil(log2 d): exact on that range; computed on the host).  The five
-// divisors' shifts share one word, 6 bits each (kernel arguments live in SGPRs, and the crop kernel has few to spare)
-enum { CROP_D_CA, CROP_D_AREA, CROP_D_WC, CROP_D_BB, CROP_D_BW };
-__device__ __forceinline__ uint32_t mdiv(uint32_t x, uint32_t m, uint32_t shifts, int which) {
-    return (uint32_t)(((uint64_t)x * m) >> ((shifts >> (6 * which)) & 63));
-}
-struct RgCropArgs {
-    int ry, rx, hc, wc, area, ca;     // radii, window height and width, window cells, floats per env (C x area)
-    int run, bh, bw, bb;              // envs per wave, the staged box (rows, columns, cells: bh * bw)
-    int planes, nst, with_hist, nplanes;  // glyph planes (1 or the handle's one-hot depth), status planes, history plane, C
-    uint32_t sflag;
-    uint32_t m[5], shifts;            // multipliers and shifts of x / ca, x / area, x / wc, x / bb, x / bw (CROP_D_*)
-};
-// One wave owns a RUN of a.run consecutive envs (a multiple of 4): their images are one contiguous stretch of the tensor, 16-byte aligned whatever the
-// parity of the window, so the lanes stream it as whole-line non-temporal float4 stores.  Each env's window is staged in LDS first as the BOX of
-// min(2ry+1, H) x min(2rx+1, W) mirror cells that holds every screen cell of the window (the window clamped into the screen): glyphs (gray) or symbol
-// ids (one-hot) and, with the history plane, visited bytes.  Every output plane is expanded from LDS; a window cell outside the screen is ' ' / 0 without a read.
-// GROUPS (a config group of a handle with several): env e's image goes to the handle's env S.ext[e] -- scalar stores, one env's run apart from the next.
-// InvalidTileError (the one-hot kind): raised for a glyph without a symbol INSIDE the window only; box cells outside it are not checked.
-#define CROP_UNROLL 8
-template <int KIND>
-__global__ void __launch_bounds__(WAVE) k_obs_crop(const uint16_t *__restrict__ p_pos, const int32_t *__restrict__ status, const uint8_t *__restrict__ screen,
-                                                  const uint8_t *__restrict__ hist, uint32_t *__restrict__ flags, const int32_t *__restrict__ ext, int n, int W, int H,
-                                                  int symbols, RgCropArgs a, float *__restrict__ out, int32_t *__restrict__ centers, uint32_t *__restrict__ err_any) {
-    extern __shared__ __align__(16) uint8_t smem[];
-    float *lutf = reinterpret_cast<float *>(smem);             // glyph -> gray value (KIND 0)
-    uint8_t *luts = smem + 512;                                 // glyph -> symbol id (KIND 1)
-    int4 *geo = reinterpret_cast<int4 *>(smem + 640);           // [run] {player y, player x, box row 0, box column 0}
-    float *stf = reinterpret_cast<float *>(smem + 640 + 16 * a.run);   // [run][9] status plane values
-    uint8_t *box = smem + 640 + 52 * a.run;                     // [run][bb] staged glyphs (gray) or symbol ids (one-hot)
-    uint8_t *hbox = box + (size_t)a.run * a.bb;                 // [run][bb] staged visited bytes (with_hist)
-    const int lane = threadIdx.x, HW = W * H, R = a.run;
-    for (int g = lane; g < 128; g += WAVE) {
-        const uint32_t sy = tile_to_sym((uint32_t)g);
-        luts[g] = (uint8_t)sy;
-        lutf[g] = (float)(uint8_t)sy / (float)(uint8_t)symbols;  // python/src/lib.rs:84 (same single division as k_obs)
-    }
-    const uint32_t smax = (uint32_t)symbols - 1;  // construct_symbol_map fills channels 0..symbols-2 (symbol.rs:51-71)
-    const int nruns = (n + R - 1) / R;
-    for (int run = blockIdx.x; run < nruns; run += gridDim.x) {
-        const int base = run * R, cnt = n - base < R ? n - base : R;
-        lds_barrier();  // the previous run's LDS reads done (and, the first time, the tables written)
-        if (lane < cnt) {
-            const int e = base + lane;
-            const uint32_t pos = p_pos[e];
-            const int cx = POS_X(pos), cy = POS_Y(pos);
-            const int oy = min(max(cy - a.ry, 0), H - a.bh), ox = min(max(cx - a.rx, 0), W - a.bw);
-            geo[lane] = make_int4(cy, cx, oy, ox);
-            int p = 0;
-            for (int b = 0; b < 9; b++)
-                if (a.sflag & (1u << b)) stf[lane * 9 + p++] = (float)status[(size_t)e * 10 + kStatusIdx[b]];
-            if (centers) {
-                const int xe = ext ? ext[e] : e;
-                centers[2 * (size_t)xe] = cy;
-                centers[2 * (size_t)xe + 1] = cx;
-            }
-        }
-        lds_barrier();
-        // ---- stage the boxes: CROP_UNROLL independent byte loads per lane in flight, then the LDS writes (one-hot: the symbol id, not the glyph) ----
-        const int tot = cnt * a.bb;
-        auto box_cell = [&](int k, int &r, int &y, int &x) {
-            r = (int)mdiv((uint32_t)k, a.m[CROP_D_BB], a.shifts, CROP_D_BB);
-            const int t = k - r * a.bb, j = (int)mdiv((uint32_t)t, a.m[CROP_D_BW], a.shifts, CROP_D_BW);
-            const int4 gg = geo[r];
-            y = gg.z + j; x = gg.w + (t - j * a.bw);
-        };
-        for (int k0 = 0; k0 < tot; k0 += WAVE * CROP_UNROLL) {
-            uint32_t gv[CROP_UNROLL], hv[CROP_UNROLL];
-#pragma unroll
-            for (int u = 0; u < CROP_UNROLL; u++) {
-                const int kk = k0 + u * WAVE + lane;
-                gv[u] = hv[u] = 0;
-                if (KIND == 0 || kk < tot) {  // (gray: past the end a repeat of the last cell, not a branch -- either form keeps its instance within the SGPRs)
-                    int r, y, x;
-                    box_cell(min(kk, tot - 1), r, y, x);
-                    const size_t off = (size_t)(base + r) * HW + y * W + x;
-                    gv[u] = screen[off];
-                    if (a.with_hist) hv[u] = hist[off];
-                }
-            }
-            uint32_t bad = 0;  // bit u: staged cell u is a glyph without a symbol inside its window (InvalidTileError, e.g. 'Z'; the one-hot kind)
-#pragma unroll
-            for (int u = 0; u < CROP_UNROLL; u++) {
-                const int k = k0 + u * WAVE + lane;
-                if (k >= tot) continue;
-                const uint32_t g = gv[u] & 0x7f;
-                box[k] = KIND ? luts[g] : (uint8_t)g;
-                if (a.with_hist) hbox[k] = (uint8_t)hv[u];
-                if (KIND == 1 && luts[g] >= smax) {
-                    int r, y, x;
-                    box_cell(k, r, y, x);
-                    const int4 gg = geo[r];
-                    bad |= (abs(y - gg.x) <= a.ry && abs(x - gg.y) <= a.rx) ? 1u << u : 0u;
-                }
-            }
-            if (KIND == 1 && bad) {  // (rare: outside the loop, which then holds no atomics)
-#pragma unroll 1
-                for (int u = 0; u < CROP_UNROLL; u++)
-                    if ((bad >> u) & 1) {
-                        int r, y, x;
-                        box_cell(k0 + u * WAVE + lane, r, y, x);
-                        atomicOr(&flags[base + r], RG_FLAG_ERR_TILE);
-                    }
-                atomicOr(err_any, RG_FLAG_ERR_TILE);
-            }
-        }
-        lds_barrier();
-        // ---- expand: a lane's 4 consecutive floats of the run, decoded once into (env r, plane p, window row j, column i) and stepped from there;
-        //      every value from LDS.  (Three multiply-shift divisions per float were the pass's VALU bound on the one-hot kind.) ----
-        auto value = [&](int r, int p, int j, int i) -> float {
-            const int4 gg = geo[r];
-            const int y = gg.x - a.ry + j, x = gg.y - a.rx + i;
-            const bool inside = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            const int bi = r * a.bb + (y - gg.z) * a.bw + (x - gg.w);
-            if (p < a.planes) {
-                if (KIND == 0) return lutf[inside ? box[bi] : (uint32_t)' '];
-                const uint32_t sy = inside ? box[bi] : 0u;  // (' ' is symbol 0)
-                return (sy == (uint32_t)p && (uint32_t)p < smax) ? 1.f : 0.f;
-            }
-            if (p < a.planes + a.nst) return stf[r * 9 + (p - a.planes)];
-            return (inside && hbox[bi]) ? 1.f : 0.f;
-        };
-        const uint32_t totf = (uint32_t)cnt * (uint32_t)a.ca;
-        float *o = out + (size_t)base * a.ca;
-        for (uint32_t q = lane; 4 * q < totf; q += WAVE) {
-            const uint32_t f0 = 4 * q;
-            int r = (int)mdiv(f0, a.m[CROP_D_CA], a.shifts, CROP_D_CA);
-            const int rem = (int)f0 - r * a.ca;
-            int p = (int)mdiv((uint32_t)rem, a.m[CROP_D_AREA], a.shifts, CROP_D_AREA);
-            const int cell = rem - p * a.area;
-            int j = (int)mdiv((uint32_t)cell, a.m[CROP_D_WC], a.shifts, CROP_D_WC), i = cell - j * a.wc;
-            float vs[4];
-            int rs[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                rs[t] = r;
-                vs[t] = f0 + t < totf ? value(r, p, j, i) : 0.f;
-                if (++i == a.wc) { i = 0; if (++j == a.hc) { j = 0; if (++p == a.nplanes) { p = 0; ++r; } } }
-            }
-            if (!ext && f0 + 3 < totf) {
-                float4 v; v.x = vs[0]; v.y = vs[1]; v.z = vs[2]; v.w = vs[3];
-                store_obs(reinterpret_cast<float4 *>(o + f0), v);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const uint32_t f = f0 + t;
-                    if (f >= totf) break;
-                    float *dst = ext ? out + (size_t)ext[base + rs[t]] * a.ca + (f - (uint32_t)rs[t] * a.ca) : o + f;
-                    __builtin_nontemporal_store(vs[t], dst);
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // k_redraw: RunTime::draw_screen of the envs with a pending Redraw into the screen / history mirrors, and nothing else -- the staged path of k_obs without
 // its encode, for the typed pass below (which then streams every env from its mirror).  Same mirrors, history rule and flag words as k_obs leaves.
 // ---------------------------------------------------------------------------------------------
@@ -1015,17 +852,9 @@ __global__ void __launch_bounds__(OBS_THREADS) k_redraw(RgState S, RgConfig c) {
 // (The kernel takes the few arrays it reads, not RgState / RgConfig by value, and draws nothing: with the Redraw path of k_obs fused in, every instance
 // spilled 36 to 60 SGPRs.)
 #define OBS_T_ITEMS 4
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_obs16(u4v *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
     u4v v = {a, b, c, d};
     __builtin_nontemporal_store(v, p);
-}
-// the 16 bits of T nearest to the finite f32 `f` (ties to even; binary16 overflows to infinity): what torch.Tensor.to(T) gives
-template <int DT>
-__device__ __forceinline__ uint32_t cvt16(float f) {
-    if (DT == RG_OBS_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);  // v_cvt_f16_f32
-    const uint32_t u = __float_as_uint(f);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 // bytes of `w` that are not zero -> 1
 __device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
@@ -1136,13 +965,6 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs_typed(const uint8_t *__rest
 // ---------------------------------------------------------------------------------------------
 // host-callable launchers (used by rg_api.cpp)
 // ---------------------------------------------------------------------------------------------
-static void host_magic(RgCropArgs &a, int which, uint32_t d) {  // (crop kernel: mdiv)
-    uint32_t l = 0;
-    while ((1u << l) < d) l++;
-    const uint32_t s = 30 + l;
-    a.m[which] = (uint32_t)(((1ull << s) + d - 1) / d);
-    a.shifts |= s << (6 * which);
-}
 extern "C" {
 void rgk_render(const RgState *S, const RgConfig *c, hipStream_t st) {
     int blocks = S->n < 8192 ? S->n : 8192;
@@ -1182,19 +1004,16 @@ int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, 
         if (const char *ev = getenv("RG_OBS_BLOCKS")) if (atoi(ev) > 0) cap = atoi(ev);
 #endif
         if (sblocks > cap) sblocks = cap;
-        if (ev0 || ev1) hipExtLaunchKernelGGL(k_obs_stream, dim3(sblocks), dim3(WAVE), 0, st, ev0, ev1, 0, *S, *c, out, hi_prio);
-        else hipLaunchKernelGGL(k_obs_stream, dim3(sblocks), dim3(WAVE), 0, st, *S, *c, out, hi_prio);
+        rg_launch(k_obs_stream, dim3(sblocks), dim3(WAVE), 0, st, ev0, ev1, *S, *c, out, hi_prio);
         return 1;
     }
-#define RG_LAUNCH_OBS(...) do { if (ev0 || ev1) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(bthreads), (uint32_t)smem, st, ev0, ev1, 0, *S, *c, sflag, with_hist, out, err_any, tpe, epb, planes_sym, hi_prio); \
-                               else hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(bthreads), smem, st, *S, *c, sflag, with_hist, out, err_any, tpe, epb, planes_sym, hi_prio); } while (0)
-    if (bound && !groups && !kind) RG_LAUNCH_OBS(k_obs<0, false, true>);       // (rg_obs_bind: the in-place pass over the last k_step's list)
-    else if (bound && !groups) RG_LAUNCH_OBS(k_obs<1, false, true>);
-    else if (!kind && !groups) RG_LAUNCH_OBS(k_obs<0, false>);
-    else if (!kind) RG_LAUNCH_OBS(k_obs<0, true>);
-    else if (!groups) RG_LAUNCH_OBS(k_obs<1, false>);
-    else RG_LAUNCH_OBS(k_obs<1, true>);
-#undef RG_LAUNCH_OBS
+    auto launch = [&](auto kernel) { rg_launch(kernel, dim3(blocks), dim3(bthreads), smem, st, ev0, ev1, *S, *c, sflag, with_hist, out, err_any, tpe, epb, planes_sym, hi_prio); };
+    if (bound && !groups && !kind) launch(k_obs<0, false, true>);       // (rg_obs_bind: the in-place pass over the last k_step's list)
+    else if (bound && !groups) launch(k_obs<1, false, true>);
+    else if (!kind && !groups) launch(k_obs<0, false>);
+    else if (!kind) launch(k_obs<0, true>);
+    else if (!groups) launch(k_obs<1, false>);
+    else launch(k_obs<1, true>);
     return 1;
 }
 // whether rgk_obs serves this handle's plain gray image (no status planes, no history plane, not bound) with k_obs_stream -- of the conditions under which
@@ -1212,8 +1031,7 @@ int rgk_obs_tail_capable(const RgState *S, const RgConfig *c) {
 void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     int blocks = (S->n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
     if (blocks > OBS_RESID_WAVES) blocks = OBS_RESID_WAVES;
-    if (ev0 || ev1) hipExtLaunchKernelGGL(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, 0, *S, *c, out);
-    else hipLaunchKernelGGL(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, *S, *c, out);
+    rg_launch(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, *S, *c, out);
 }
 void rgk_encode(const uint8_t *screen, const uint8_t *hist, const int32_t *status, uint32_t *flags, uint32_t *err_any, int n, int hw, size_t rs, size_t rst,
                 int symbols, int planes_sym, uint32_t sflag, int with_hist, int kind, float *out, const int32_t *ext, hipStream_t st) {
@@ -1257,35 +1075,6 @@ void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int
 void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_gather_keys, dim3((n + 255) / 256), dim3(256), 0, st, keys, ext, dst, n);
 }
-// the player-centred crop (rg_obs_crop; radii and arguments checked by the caller): one wave per run of envs, persistent grid.  Returns 0 if the
-// window's size does not fit the kernel's index arithmetic (cannot happen within the documented radii).
-int rgk_obs_crop(const RgState *S, const RgConfig *c, int kind, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, float *out, int32_t *centers,
-                 uint32_t *err_any, hipStream_t st) {
-    RgCropArgs a;
-    const int hc = 2 * ry + 1;
-    a.ry = ry; a.rx = rx; a.hc = hc; a.wc = 2 * rx + 1; a.area = hc * a.wc;
-    a.planes = kind ? planes_sym : 1; a.nst = __builtin_popcount(sflag); a.with_hist = with_hist ? 1 : 0; a.sflag = sflag;
-    a.nplanes = a.planes + a.nst + a.with_hist;
-    a.ca = a.nplanes * a.area;
-    a.bh = hc < c->height ? hc : c->height; a.bw = a.wc < c->width ? a.wc : c->width; a.bb = a.bh * a.bw;
-    // envs per wave: a multiple of 4 (every run starts 16-byte aligned), doubled while a run writes under 4 KB and stages under 16 KB of LDS
-    a.run = 4;
-    const size_t stage = (size_t)a.bb * (1 + a.with_hist);
-    while (a.run < 64 && (size_t)a.run * a.ca * 4 < 4096 && (size_t)a.run * 2 * stage <= 16384) a.run *= 2;
-    if ((uint64_t)a.run * a.ca >= (1ull << 30) || (uint64_t)a.run * a.bb >= (1ull << 30)) return 0;
-    a.shifts = 0;
-    host_magic(a, CROP_D_CA, (uint32_t)a.ca); host_magic(a, CROP_D_AREA, (uint32_t)a.area); host_magic(a, CROP_D_WC, (uint32_t)a.wc);
-    host_magic(a, CROP_D_BB, (uint32_t)a.bb); host_magic(a, CROP_D_BW, (uint32_t)a.bw);
-    const size_t smem = 640 + 52 * (size_t)a.run + (size_t)a.run * stage;  // (at most 62 KB: a run of 4 with the whole 160 x 48 screen staged twice)
-    const int nruns = (S->n + a.run - 1) / a.run;
-    const int blocks = nruns < OBS_STREAM_WAVES ? nruns : OBS_STREAM_WAVES;
-    // (the few state arrays it reads, not RgState / RgConfig by value: their kernel arguments cost the one-hot instance SGPR spills)
-    if (kind) hipLaunchKernelGGL(k_obs_crop<1>, dim3(blocks), dim3(WAVE), smem, st, S->p_pos, S->status, S->screen, S->hist, S->flags, S->ext, S->n, c->width, c->height,
-                                 c->symbols, a, out, centers, err_any);
-    else hipLaunchKernelGGL(k_obs_crop<0>, dim3(blocks), dim3(WAVE), smem, st, S->p_pos, S->status, S->screen, S->hist, S->flags, S->ext, S->n, c->width, c->height,
-                            c->symbols, a, out, centers, err_any);
-    return 1;
-}
 // the Redraw sweep in front of the typed pass (k_redraw): returns 0 where it does not apply (more rooms than the LDS overlay tables hold: the caller runs k_render)
 int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st) {
     const int hw = c->width * c->height;
@@ -1312,16 +1101,15 @@ int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint
     const int nruns = (S->n + run - 1) / run, cap = B <= WAVE ? OBS_STREAM_WAVES : 4096;  // persistent grid
     const int blocks = nruns < cap ? nruns : cap;
     const int planes = kind == 1 ? planes_sym : 1;
-#define RG_LAUNCH_TYPED(...) do { if (ev0 || ev1) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(B), 0, st, ev0, ev1, 0, S->screen, S->hist, S->status, S->flags, err_any, S->n, hw, \
-                                                                        (int)c->symbols, planes, sflag, with_hist, run, static_cast<u4v *>(out)); \
-                                  else hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(B), 0, st, S->screen, S->hist, S->status, S->flags, err_any, S->n, hw, (int)c->symbols, planes, sflag, \
-                                                          with_hist, run, static_cast<u4v *>(out)); } while (0)
-    if (kind == 2) RG_LAUNCH_TYPED(k_obs_typed<2, RG_OBS_U8>);
-    else if (kind == 0 && dtype == RG_OBS_F16) RG_LAUNCH_TYPED(k_obs_typed<0, RG_OBS_F16>);
-    else if (kind == 0) RG_LAUNCH_TYPED(k_obs_typed<0, RG_OBS_BF16>);
-    else if (dtype == RG_OBS_F16) RG_LAUNCH_TYPED(k_obs_typed<1, RG_OBS_F16>);
-    else RG_LAUNCH_TYPED(k_obs_typed<1, RG_OBS_BF16>);
-#undef RG_LAUNCH_TYPED
+    auto launch = [&](auto kernel) {
+        rg_launch(kernel, dim3(blocks), dim3(B), 0, st, ev0, ev1, S->screen, S->hist, S->status, S->flags, err_any, S->n, hw, (int)c->symbols, planes, sflag, with_hist, run,
+                  static_cast<u4v *>(out));
+    };
+    if (kind == 2) launch(k_obs_typed<2, RG_OBS_U8>);
+    else if (kind == 0 && dtype == RG_OBS_F16) launch(k_obs_typed<0, RG_OBS_F16>);
+    else if (kind == 0) launch(k_obs_typed<0, RG_OBS_BF16>);
+    else if (dtype == RG_OBS_F16) launch(k_obs_typed<1, RG_OBS_F16>);
+    else launch(k_obs_typed<1, RG_OBS_BF16>);
     return 1;
 }
 // shader-clock probe: one wave spins for `spin` iterations and reports {s_memtime ticks (shader clock), s_memrealtime ticks (constant 100 MHz)}

@@ -3,16 +3,11 @@
 //   k_pixels : one instance; channels, tile height, window and screen size are run-time arguments
 //
 // The child of k_crop_typed (rg_crop_typed.hip: a wave per run of envs on a persistent grid, the window's box of mirror cells staged in LDS, the run's images
-// one contiguous stretch of the tensor written in 16-byte pieces, `ext` for config groups).  A translation unit of its own, with its own copies of the few
-// helpers it shares, so that the code generation of the other kernels -- their register counts are pinned by the resource tests -- is not touched by
-// anything here.  Built with -Os like the other observation passes.
+// one contiguous stretch of the tensor written in 16-byte pieces, `ext` for config groups).  Built with -Os like the other observation passes.
 #include "rg_device.h"
 #include "rg_pixels.h"
 
-// LDS-only workgroup barrier (rg_obs.hip): the blocks here are one wave
-static __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// x / d for 0 <= x < 2^30 by a multiply and a shift (rg_obs.hip mdiv: m = ceil(2^s / d), s = 30 + l, l = ceil(log2 d), computed on the host; here the shift
+// x / d for 0 <= x < 2^30 by a multiply and a shift (k_crop_typed's mdiv: m = ceil(2^s / d), s = 30 + l, l = ceil(log2 d), computed on the host; here the shift
 // kept is l): floor(x m / 2^s) = floor(floor(4 x m / 2^32) / 2^l), and 4 x fits 32 bits -- one v_mul_hi_u32 and two shifts, no 64-bit product
 enum { PX_D_UPE, PX_D_PU, PX_D_WC, PX_D_TH, PX_D_BB, PX_D_BW, PX_DIVS };
 static __device__ __forceinline__ uint32_t mdiv(uint32_t x, uint32_t m, uint32_t l) { return __umulhi(x << 2, m) >> l; }
@@ -25,7 +20,6 @@ struct PixelArgs {
     uint8_t s[PX_DIVS + 2];
 };
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
 #define PX_UNROLL 8
@@ -195,11 +189,7 @@ int rgk_pixels(const RgState *S, const RgConfig *c, const uint8_t *tiles, int th
     if (!smem || smem > PX_LDS_MAX) return 0;
     const int nruns = (S->n + a.run - 1) / a.run;
     const int blocks = nruns < PX_WAVES ? nruns : PX_WAVES;
-    if (ev0 || ev1)
-        hipExtLaunchKernelGGL(k_pixels, dim3(blocks), dim3(WAVE), (uint32_t)smem, st, ev0, ev1, 0, S->p_pos, S->screen, S->ext, S->n, (int)c->width, (int)c->height, tiles, a, out,
-                              centers);
-    else
-        hipLaunchKernelGGL(k_pixels, dim3(blocks), dim3(WAVE), smem, st, S->p_pos, S->screen, S->ext, S->n, (int)c->width, (int)c->height, tiles, a, out, centers);
+    rg_launch(k_pixels, dim3(blocks), dim3(WAVE), smem, st, ev0, ev1, S->p_pos, S->screen, S->ext, S->n, (int)c->width, (int)c->height, tiles, a, out, centers);
     return 1;
 }
 }

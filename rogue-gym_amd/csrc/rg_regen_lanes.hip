@@ -706,8 +706,7 @@ int rgk_regen_lanes(const RgState *SP, const RgConfig *c, uint32_t *q, int32_t *
     if (bulk) waves = (n_sp + L - 1) / L;
     if (waves < 1) waves = 1;
     const dim3 grid(waves);
-    if (ev0 || ev1) hipExtLaunchKernelGGL(k_regen_lanes, grid, dim3(WAVE), (uint32_t)p.smem, st, ev0, ev1, 0, *SP, *c, q, list, L, p.lane_stride, p.tab_off, p.stk_off, SP->maze_cap, slots, prio, prof);
-    else hipLaunchKernelGGL(k_regen_lanes, grid, dim3(WAVE), p.smem, st, *SP, *c, q, list, L, p.lane_stride, p.tab_off, p.stk_off, SP->maze_cap, slots, prio, prof);
+    rg_launch(k_regen_lanes, grid, dim3(WAVE), p.smem, st, ev0, ev1, *SP, *c, q, list, L, p.lane_stride, p.tab_off, p.stk_off, SP->maze_cap, slots, prio, prof);
     return 1;
 }
 }

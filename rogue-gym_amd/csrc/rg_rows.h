@@ -6,8 +6,6 @@
 #include <type_traits>
 #include "rg_device.h"
 
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 // one-lane DPP shifts (as rg_kernels.hip has them for itself).  Whole wave: lane i <- lane i -+ 1 ...
 static __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }  // lane i <- lane i-1
 static __device__ __forceinline__ uint32_t wave_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false); }  // lane i <- lane i+1

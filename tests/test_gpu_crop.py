@@ -1,6 +1,7 @@
 """Player-centred cropped observations (rg_obs_crop; HipVecRogueEnv(crop=...)).  The expected crop is always built in torch from the library's own full
 encode (which tests/test_gpu_obs_oracle.py pins to the oracle at every step; that module also checks the crop itself against the oracle): the full image padded with the encoding of a blank cell ' ', then gathered at the window centres.  Benchmark shape,
-the 80x24 dungeon with descents, edges, pending Redraws, the bound observation tensor, config groups and mixed sizes, refusals and the 'Z' rule."""
+the 80x24 dungeon with descents, edges, pending Redraws, the bound observation tensor, config groups and mixed sizes, refusals and the 'Z' rule, and
+batches and config groups that end in a short run of envs, between guard bytes."""
 import ctypes as C
 
 import numpy as np
@@ -401,3 +402,78 @@ def test_crop_refusals_and_invalid_tiles(goldens):
     with pytest.raises(RuntimeError, match="Invalid tile"):
         hip.sync()
     h.close()
+
+
+GUARD = 64  # bytes of a known pattern on either side of a crop tensor
+
+
+def guarded_crop_call(h, kind, ry, rx, flag, with_hist):
+    """rg_obs_crop into a tensor that lies between two guards of GUARD bytes of 0xA5 inside one allocation (the tensor itself starts as NaNs):
+    (crop f32 [n, C, 2ry+1, 2rx+1], centres i32 [n, 2]); the guards are checked to be untouched."""
+    torch = torch_mod()
+    c = h.L.rg_obs_channels(h.h, kind, flag, int(with_hist))
+    dev = "cuda:%d" % h.device
+    shape = (h.n, c, 2 * ry + 1, 2 * rx + 1)
+    nbytes = 4 * int(np.prod(shape))
+    raw = torch.full((GUARD + nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    raw[GUARD:GUARD + nbytes] = 0xFF
+    out = raw[GUARD:GUARD + nbytes].view(torch.float32).view(shape)
+    assert out.data_ptr() % 16 == 0
+    cen = torch.full((h.n, 2), -1, dtype=torch.int32, device=dev)
+    h.check(h.L.rg_obs_crop(h.h, kind, ry, rx, flag, int(with_hist), C.c_void_p(out.data_ptr()), C.c_void_p(cen.data_ptr())))
+    assert bool((raw[:GUARD] == 0xA5).all()), "the crop wrote in front of its tensor"
+    assert bool((raw[GUARD + nbytes:] == 0xA5).all()), "the crop wrote past its tensor"
+    return out, cen
+
+
+# radius_y, radius_x, status flag, history plane
+SHORT_RUN_WINDOWS = ((0, 0, 0, False), (1, 1, 0, False), (5, 5, 0, False), (3, 4, FULL, True))
+
+
+@pytest.mark.parametrize("n", [1, 7, 67])
+def test_crop_short_last_run(goldens, n):
+    """Env counts that are no multiple of the run length (a wave serves 4 or more envs), so the batch ends in a short run whose last 16-byte piece is
+    written element by element: both kinds, four windows, after each of a dozen random steps, against the padded full image; nothing is written
+    outside the tensor."""
+    from parity_util import ACTION_KEYS, HipBatch
+
+    hip = HipBatch(goldens["configs"]["mini"], range(700, 700 + n), max_steps=80)
+    rng = np.random.RandomState(n)
+    for t in range(12):
+        hip.step(ACTION_KEYS[rng.randint(0, len(ACTION_KEYS), n)])
+        for kind in (0, 1):
+            for ry, rx, flag, with_hist in SHORT_RUN_WINDOWS:
+                got, cen = guarded_crop_call(hip.h, kind, ry, rx, flag, with_hist)
+                check_crop(hip.h, kind, ry, rx, flag, with_hist, got, cen, "n=%d t=%d kind=%d window=(%d, %d)" % (n, t, kind, ry, rx))
+    hip.sync()
+    hip.h.close()
+
+
+def test_crop_short_runs_of_config_groups(goldens):
+    """Ten envs of three screen sizes on one handle, in groups of 3, 5 and 2 envs: every group's only run is short and every element is stored by itself
+    at the handle's env index.  Each env's crop equals the crop of its own full image; nothing is written outside the tensor."""
+    torch = torch_mod()
+    from rogue_gym.envs import DungeonType, ImageSetting, StatusFlag
+    from rogue_gym.envs.device import HipVecRogueEnv
+
+    enemies = {"enemies": list(range(10))}
+    shapes = [dict(goldens["configs"]["mini"], enemies=enemies), {"width": 80, "height": 24, "enemies": enemies},
+              {"width": 48, "height": 20, "dungeon": {"style": "rogue", "room_num_x": 3, "room_num_y": 2}, "enemies": enemies}]
+    order = [0, 1, 2, 1, 0, 1, 2, 1, 0, 1]
+    cfgs = [dict(shapes[k], seed=6100 + i) for i, k in enumerate(order)]
+    gen = torch.Generator().manual_seed(7)
+    for setting, kind, flag, crop in ((ImageSetting(DungeonType.GRAY, StatusFlag.FULL, True), 0, FULL, (3, 4)),
+                                      (ImageSetting(DungeonType.SYMBOL, StatusFlag.EMPTY, False), 1, 0, (5, 5))):
+        env = HipVecRogueEnv(cfgs, max_steps=80, image_setting=setting, crop=crop)
+        assert env._h.mixed_sizes
+        planes = env._h.symbols if kind else 1
+        with_hist = bool(setting.includes_hist)
+        for t in range(12):
+            env.step_keys(random_keys(env, gen))
+            exp, _ = _ragged_expected(env, setting, crop[0], crop[1], kind, planes, with_hist)
+            got, cen = guarded_crop_call(env._h, kind, crop[0], crop[1], flag, with_hist)
+            assert torch.equal(cen, env.crop_center), (kind, t)
+            assert torch.equal(got.cpu(), exp), "groups kind=%d t=%d" % (kind, t)
+            assert torch.equal(env.obs.cpu(), exp), "groups kind=%d t=%d (the env's own crop)" % (kind, t)
+        env.check_errors()
+        env.close()

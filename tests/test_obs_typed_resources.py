@@ -8,7 +8,8 @@ from test_kernel_resources import kernel_metadata
 # kind, RG_OBS_* type of every compiled instance: gray and one-hot in f16 (1) and bf16 (2), symbol ids in u8 (3)
 TYPED = [(0, 1), (0, 2), (1, 1), (1, 2), (2, 3)]
 
-# vgpr_count, sgpr_spill_count of the pre-existing kernels of rg_obs.hip in a build of the commit before the typed kernels (same compiler, same flags)
+# vgpr_count, sgpr_spill_count of the pre-existing kernels of rg_obs.hip in a build of the commit before the typed kernels (same compiler, same flags).
+# The f32 crop is the RG_OBS_F32 instance of k_crop_typed (rg_crop_typed.hip): no more registers than the kernel it replaced (k_obs_crop: 40 and 44).
 BEFORE = {
     r"k_obsILi0ELb0ELb0E": (79, 0),
     r"k_obsILi0ELb0ELb1E": (81, 2),
@@ -17,8 +18,8 @@ BEFORE = {
     r"k_obsILi1ELb0ELb1E": (95, 13),
     r"k_obsILi1ELb1ELb0E": (102, 14),
     r"k_obs_stream": (61, 0),
-    r"k_obs_cropILi0E": (40, 0),
-    r"k_obs_cropILi1E": (44, 0),
+    r"k_crop_typedILi0ELi0E": (38, 0),
+    r"k_crop_typedILi1ELi0E": (44, 0),
     r"\d+k_gray": (49, 0),
     r"\d+k_symbol": (50, 0),
     r"\d+k_render": (26, 0),

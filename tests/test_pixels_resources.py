@@ -55,8 +55,6 @@ PINNED = {  # kernel-name fragment -> vgpr_count of the units this change does n
     '_Z10k_monstersILi16EEv7MonView': 136,
     '_Z10k_monstersILi4EEv7MonView': 58,
     '_Z10k_monstersILi8EEv7MonView': 81,
-    '_Z10k_obs_cropILi0EEvPKtPKiPKhS5_PjS3_iiii10RgCropArgsPfPiS6_': 40,
-    '_Z10k_obs_cropILi1EEvPKtPKiPKhS5_PjS3_iiii10RgCropArgsPfPiS6_': 44,
     '_Z10k_step_w32ILb0ELb0EEv7RgStatePKS0_8RgConfigPKhiiii': 247,
     '_Z10k_step_w32ILb0ELb1EEv7RgStatePKS0_8RgConfigPKhiiii': 248,
     '_Z10k_step_w32ILb1ELb0EEv7RgStatePKS0_8RgConfigPKhiiii': 251,
@@ -70,8 +68,10 @@ PINNED = {  # kernel-name fragment -> vgpr_count of the units this change does n
     '_Z12k_build_listILi0EEv7RgState8RgConfigPKiPKjPh': 126,
     '_Z12k_build_listILi1EEv7RgState8RgConfigPKiPKjPh': 127,
     '_Z12k_build_listILi2EEv7RgState8RgConfigPKiPKjPh': 133,
+    '_Z12k_crop_typedILi0ELi0EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 38,   # (the f32 crop: an instance of k_crop_typed since k_obs_crop was folded into it)
     '_Z12k_crop_typedILi0ELi1EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 40,
     '_Z12k_crop_typedILi0ELi2EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 40,
+    '_Z12k_crop_typedILi1ELi0EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 44,
     '_Z12k_crop_typedILi1ELi1EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 46,
     '_Z12k_crop_typedILi1ELi2EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 46,
     '_Z12k_crop_typedILi2ELi3EEvPKtPKiPKhS5_PjS3_iiii13CropTypedArgsPhPiS6_': 44,

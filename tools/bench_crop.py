@@ -1,4 +1,4 @@
-"""Step + full image against step + player-centred crop (rg_obs_crop, rogue-gym_amd/csrc/rg_obs.hip k_obs_crop).
+"""Step + full image against step + player-centred crop (rg_obs_crop, rogue-gym_amd/csrc/rg_crop_typed.hip k_crop_typed with RG_OBS_F32 elements).
 
 Three workloads, each on ONE handle with the same seeds and the same uniform-random policy (a pre-generated table of 512 key rows, cycled):
 65 536 mini envs gray with a 9x9 crop, 32 768 default 80x24 envs gray with an 11x11 crop, 32 768 nohide 80x24 envs one-hot symbol with an 11x11

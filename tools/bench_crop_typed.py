@@ -1,4 +1,5 @@
-"""Step + typed player-centred crop (rg_obs_crop_typed, rogue-gym_amd/csrc/rg_crop_typed.hip k_crop_typed) against step + f32 crop (rg_obs_crop).
+"""Step + typed player-centred crop (rg_obs_crop_typed) against step + f32 crop (rg_obs_crop): the instances of k_crop_typed in
+rogue-gym_amd/csrc/rg_crop_typed.hip, the f32 crop being its RG_OBS_F32 case.
 
 Three workloads, each on ONE handle with the same seeds and the same uniform-random policy (a pre-generated table of 512 key rows, cycled): 65 536
 mini envs gray, 32 768 default 80x24 envs gray, 32 768 nohide 80x24 envs one-hot symbol; the window is 11x11 everywhere.  Two kinds of rows, one JSON
