@@ -1,5 +1,5 @@
 // rg_action_mask.h -- which keys of KeyMap::ai do anything for an env right now: THE statement of the rule (rg_action_mask / rg_action_mask_host) and the
-// stateless draw among the legal keys (rg_sample_index).  Host and device: k_action_mask (rg_action_mask.hip) and rg_action_mask_host (rg_api.cpp) both
+// stateless draw among the legal keys (rg_sample_index).  Host and device: k_action_mask (rg_action_mask.hip) and rg_action_mask_host (rg_readers_host.h) both
 // call rg_key_legal's pieces, so the rule is written once.  file:line citations name the reference's sources.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -16,12 +16,7 @@
 #include "../../include/rogue_gym_hip.h"
 #include "rg_state.h"
 #include "rg_state_io.h"
-#include "rg_action_mask.h"
-#include "rg_path.h"
-#include "rg_route.h"
-#include "rg_episode.h"
-#include "rg_monsters.h"
-#include "rg_objects.h"
+#include "rg_readers_host.h"  // the rule headers of the readers of game state, their argument checks and their CPU twins
 #include "rg_pixels.h"
 
 // The few RCCL declarations this file needs, spelled out: librccl is bound with dlopen at run time, so building the single-GPU library must not
@@ -799,16 +794,19 @@ int rg_obs_channels(const rg_t *h, int symbol, uint32_t status_flag, int with_hi
     return (symbol ? h->planes_sym : 1) + __builtin_popcount(status_flag & 0x1ffu) + (with_hist ? 1 : 0);
 }
 
+// a symbol image's channel count is env 0's symbols: a config group with more is refused, `w` being what the refusal starts with
+static int symbols_check(rg_t *h, const std::string &w, const rg_handle *sh) {
+    if (sh->cfg.symbols <= h->planes_sym) return 0;
+    h->err = w + "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
+             "), which sets the channel count (python/src/lib.rs:281-285)";
+    return 1;
+}
 static int obs_common(rg_t *h, uint32_t status_flag, int with_hist, int kind, float *out_dev) {
     if (refuse_mixed(h, kind ? "rg_obs_symbol" : "rg_obs_gray")) return 1;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->sub.empty()) {  // every group encodes its envs straight into the handle's tensor (RgState::ext)
         for (rg_handle *sh : h->sub) {
-            if (kind && sh->cfg.symbols > h->planes_sym) {
-                h->err = "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
-                         "), which sets the channel count (python/src/lib.rs:281-285)";
-                return 1;
-            }
+            if (kind && symbols_check(h, "", sh)) return 1;
             SUBCHK(h, sh, obs_common(sh, status_flag, with_hist, kind, out_dev));
         }
         return 0;
@@ -873,15 +871,19 @@ int rg_obs_bind(rg_t *h, int kind, uint32_t status_flag, int with_hist, float *o
     h->bound_out = out_dev; h->bound_kind = kind; h->bound_valid = false; h->bound_steps = 0;
     return 0;
 }
-// Typed observations (f16 / bf16 images, u8 symbol ids).  typed_check: every refusal, before anything is launched (or stepped).
+// Typed observations (f16 / bf16 images, u8 symbol ids).  typed_check: every refusal, before anything is launched (or stepped); kind_dtype_check: those the typed crops share.
 int rg_obs_dtype_bytes(int dtype) { return dtype == RG_OBS_F32 ? 4 : (dtype == RG_OBS_F16 || dtype == RG_OBS_BF16) ? 2 : dtype == RG_OBS_U8 ? 1 : -1; }
-static int typed_check(rg_t *h, const char *what, int kind, int dtype, uint32_t status_flag, const void *out_dev) {
-    const std::string w = std::string(what) + ": ";
+static int kind_dtype_check(rg_t *h, const std::string &w, int kind, int dtype, uint32_t status_flag) {
     if (kind < 0 || kind > 2) { h->err = w + "kind must be 0 (gray), 1 (symbol) or 2 (symbol ids), got " + std::to_string(kind); return 1; }
     if (rg_obs_dtype_bytes(dtype) < 0) { h->err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1), RG_OBS_BF16 (2) or RG_OBS_U8 (3), got " + std::to_string(dtype); return 1; }
     if (kind == 2 && dtype != RG_OBS_U8) { h->err = w + "kind 2 (symbol ids) takes dtype RG_OBS_U8 only, got dtype " + std::to_string(dtype); return 1; }
     if (kind != 2 && dtype == RG_OBS_U8) { h->err = w + "dtype RG_OBS_U8 is for kind 2 (symbol ids) only, got kind " + std::to_string(kind); return 1; }
     if (kind == 2 && (status_flag & 0x1ffu)) { h->err = w + "status_flag must be 0 for kind 2 (status values do not fit a byte; read the status mirror)"; return 1; }
+    return 0;
+}
+static int typed_check(rg_t *h, const char *what, int kind, int dtype, uint32_t status_flag, const void *out_dev) {
+    const std::string w = std::string(what) + ": ";
+    if (kind_dtype_check(h, w, kind, dtype, status_flag)) return 1;
     if (!out_dev || ((uintptr_t)out_dev & 15)) { h->err = w + "out_dev must be a non-null, 16-byte aligned device pointer"; return 1; }
     if (dtype == RG_OBS_F32) return 0;  // (the f32 call: its own rules)
     if (!h->sub.empty() || h->mixed) { h->err = w + "not for a handle with config groups or mixed sizes"; return 1; }
@@ -951,19 +953,11 @@ extern "C++" template <class Leaf> static int window_launch(rg_t *h, Leaf leaf) 
 // The crops.  crop_check: every refusal, before anything is launched (or stepped).
 static int crop_check(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, const void *out_dev) {
     const std::string w = std::string(what) + ": ";
-    if (kind < 0 || kind > 2) { h->err = w + "kind must be 0 (gray), 1 (symbol) or 2 (symbol ids), got " + std::to_string(kind); return 1; }
-    if (rg_obs_dtype_bytes(dtype) < 0) { h->err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1), RG_OBS_BF16 (2) or RG_OBS_U8 (3), got " + std::to_string(dtype); return 1; }
-    if (kind == 2 && dtype != RG_OBS_U8) { h->err = w + "kind 2 (symbol ids) takes dtype RG_OBS_U8 only, got dtype " + std::to_string(dtype); return 1; }
-    if (kind != 2 && dtype == RG_OBS_U8) { h->err = w + "dtype RG_OBS_U8 is for kind 2 (symbol ids) only, got kind " + std::to_string(kind); return 1; }
-    if (kind == 2 && (status_flag & 0x1ffu)) { h->err = w + "status_flag must be 0 for kind 2 (status values do not fit a byte; read the status mirror)"; return 1; }
+    if (kind_dtype_check(h, w, kind, dtype, status_flag)) return 1;
     if (window_check(h, w, true, radius_y, radius_x, out_dev)) return 1;
     if (kind == 1)  // (kind 2 has no channel count: each env is judged by its own group's symbols)
         for (rg_handle *sh : h->sub)
-            if (sh->cfg.symbols > h->planes_sym) {
-                h->err = w + "symbol image: a config of the batch has more symbols (" + std::to_string(sh->cfg.symbols) + ") than env 0's (" + std::to_string(h->planes_sym) +
-                         "), which sets the channel count (python/src/lib.rs:281-285)";
-                return 1;
-            }
+            if (symbols_check(h, w, sh)) return 1;
     return 0;
 }
 static int crop_checked(rg_t *h, const char *what, int kind, int dtype, int radius_y, int radius_x, uint32_t status_flag, int with_hist, void *out_dev, int32_t *centers_dev) {
@@ -1051,10 +1045,9 @@ int rg_pixels_host(int th, const uint8_t *font, const uint8_t *palette, int chan
                    uint8_t *out) {
     return rg_px_host(g_create_err, th, font, palette, channels, H, W, screen, cy, cx, radius_y, radius_x, out);
 }
-// Legal-action masks (rg_action_mask.hip; the rule: rg_action_mask.h).  mask_keys_check: the key list of a call, every refusal before anything is launched;
-// on success `list` holds the n_keys keys the call judges.
-// The readers of game state (rg_action_mask, rg_path, rg_route, rg_monsters, rg_objects): launch(leaf) enqueues one kernel on a handle without groups; on a handle
-// with config groups every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do.
+// The readers of game state (rg_action_mask, rg_path, rg_route, rg_monsters, rg_objects: the kernel in the .hip unit and the rule in the header of that name, the
+// argument checks and the CPU twins rg_*_host in rg_readers_host.h).  launch(leaf) enqueues one kernel on a handle without groups; on a handle with config groups
+// every group writes its envs' rows straight into the handle's tensors (RgState::ext), as the crops do.
 // Game state only: the pending render is not flushed, mirrors, flag words, a bound observation tensor and the RNG streams stay as they are.
 extern "C++" template <class Launch> static int reader_launch(rg_t *h, Launch launch) {
     HIPCHK(h, hipSetDevice(h->device));
@@ -1066,344 +1059,56 @@ extern "C++" template <class Launch> static int reader_launch(rg_t *h, Launch la
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-// The grid and the player's cell of a *_host entry: the refusals they share, `what` being the entry's name
-static int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
-    const std::string w = std::string(what) + ": ";
-    if (!cells) { err = w + "cells must not be NULL"; return 1; }
-    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
-        err = w + "height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" + std::to_string(height) +
-              ", " + std::to_string(width) + ")";
-        return 1;
-    }
-    return 0;
-}
-static int player_check(std::string &err, const char *what, int px, int py, int height, int width) {
-    if (px < 0 || py < 0 || px >= width || py >= height) {
-        err = std::string(what) + ": the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
-              std::to_string(height) + " grid";
-        return 1;
-    }
-    return 0;
-}
-static int mask_keys_check(std::string &err, const char *what, const uint8_t *keys, int &n_keys, uint8_t list[RG_MASK_MAX_KEYS]) {
-    const std::string w = std::string(what) + ": ";
-    if (!keys) { keys = reinterpret_cast<const uint8_t *>(RG_ACTION_KEYS); n_keys = (int)(sizeof(RG_ACTION_KEYS) - 1); }
-    if (n_keys < 1 || n_keys > RG_MASK_MAX_KEYS) { err = w + "n_keys must satisfy 1 <= n_keys <= " + std::to_string(RG_MASK_MAX_KEYS) + ", got " + std::to_string(n_keys); return 1; }
-    for (int k = 0; k < n_keys; k++) {
-        if (rg_key_bit(keys[k]) == RG_LB_NONE) {
-            char hex[8];
-            snprintf(hex, sizeof hex, "0x%02x", keys[k]);
-            err = w + "keys[" + std::to_string(k) + "] = " + hex + (keys[k] >= 0x20 && keys[k] < 0x7f ? " ('" + std::string(1, (char)keys[k]) + "')" : std::string()) +
-                  " is not a key of KeyMap::ai (input.rs:73-100)";
-            return 1;
-        }
-        list[k] = keys[k];
-    }
-    return 0;
-}
-static int action_mask_checked(rg_t *h, const uint8_t *list, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
-    return reader_launch(h, [=](rg_t *l) { rgk_action_mask(&l->S, &l->cfg, list, n_keys, mask_dev, sample_dev, seed, draw, l->stream, nullptr, nullptr); });
-}
 int rg_action_mask(rg_t *h, const uint8_t *keys, int n_keys, uint8_t *mask_dev, uint8_t *sample_dev, uint64_t seed, uint64_t draw) {
     uint8_t list[RG_MASK_MAX_KEYS];
     if (mask_keys_check(h->err, "rg_action_mask", keys, n_keys, list)) return 1;
     if (!mask_dev && !sample_dev) { h->err = "rg_action_mask: mask_dev and sample_dev are both NULL"; return 1; }
     if ((uintptr_t)mask_dev & 15) { h->err = "rg_action_mask: mask_dev must be a 16-byte aligned device pointer"; return 1; }
-    return action_mask_checked(h, list, n_keys, mask_dev, sample_dev, seed, draw);
+    return reader_launch(h, [=](rg_t *l) { rgk_action_mask(&l->S, &l->cfg, list, n_keys, mask_dev, sample_dev, seed, draw, l->stream, nullptr, nullptr); });
 }
 int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys, uint8_t *out) {
-    uint8_t list[RG_MASK_MAX_KEYS];
-    if (mask_keys_check(g_create_err, "rg_action_mask_host", keys, n_keys, list)) return 1;
-    if (!cells || !out) { g_create_err = "rg_action_mask_host: cells and out must not be NULL"; return 1; }
-    if (player_check(g_create_err, "rg_action_mask_host", px, py, height, width)) return 1;  // (an empty grid has no cell inside it: the same refusal)
-    for (int k = 0; k < n_keys; k++) out[k] = (uint8_t)rg_key_legal(cells, height, width, px, py, dead, list[k]);
-    return 0;
+    return rgh_action_mask(g_create_err, cells, height, width, px, py, dead, keys, n_keys, out);
 }
 uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count) { return rg_sample_index_of(seed, env, draw, count); }
-// Shortest-path fields and teacher keys (rg_path.hip; the rule: rg_path.h).  path_goals_check: the goal set of a call, refused before anything is launched.
-static int path_goals_check(std::string &err, const char *what, uint32_t goals) {
-    if (goals == 0 || (goals & ~RG_PATH_GOALS_ALL)) {
-        err = std::string(what) + ": goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2) and RG_GOAL_CELL (4), got " + std::to_string(goals);
-        return 1;
-    }
-    return 0;
-}
-static int path_checked(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
-    return reader_launch(h, [=](rg_t *l) { rgk_path(&l->S, &l->cfg, goals, cells_dev, field_dev, dist_dev, key_dev, l->stream); });
-}
 int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
     if (path_goals_check(h->err, "rg_path", goals)) return 1;
     if ((goals & RG_GOAL_CELL) && !cells_dev) { h->err = "rg_path: cells_dev is NULL and goals has RG_GOAL_CELL"; return 1; }
     if (!field_dev && !dist_dev && !key_dev) { h->err = "rg_path: field_dev, dist_dev and key_dev are all NULL"; return 1; }
     if ((uintptr_t)field_dev & 15) { h->err = "rg_path: field_dev must be a 16-byte aligned device pointer"; return 1; }
     if (field_dev && !h->sub.empty()) { h->err = "rg_path: field_dev is refused on a handle with config groups (there is no [n_env][H][W] tensor); dist_dev and key_dev are served"; return 1; }
-    return path_checked(h, goals, cells_dev, field_dev, dist_dev, key_dev);
+    return reader_launch(h, [=](rg_t *l) { rgk_path(&l->S, &l->cfg, goals, cells_dev, field_dev, dist_dev, key_dev, l->stream); });
 }
-// A plain FIFO search from the goal cells over rg_path.h's pieces; the corner rule names the same two cells from either end of a move, so a predecessor of
-// cell b in direction d is the cell a = b - d with rg_can_move(a, d).
 int rg_path_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, int cell_y, int cell_x, uint16_t *field_out, int32_t *dist_out,
                  uint8_t *key_out) {
-    if (path_goals_check(g_create_err, "rg_path_host", goals)) return 1;
-    if (!field_out && !dist_out && !key_out) { g_create_err = "rg_path_host: field_out, dist_out and key_out are all NULL"; return 1; }
-    if (grid_check(g_create_err, "rg_path_host", cells, height, width) || player_check(g_create_err, "rg_path_host", px, py, height, width)) return 1;
-    const int hw = height * width;
-    std::vector<uint16_t> D((size_t)hw, (uint16_t)RG_PATH_INF);
-    std::vector<int> fifo;
-    fifo.reserve((size_t)hw);
-    for (int i = 0; i < hw; i++) {
-        const int x = i % width, y = i / width;
-        if (rg_path_goal(cells[i], goals, x == px && y == py, x == cell_x && y == cell_y)) { D[i] = 0; fifo.push_back(i); }
-    }
-    for (size_t head = 0; head < fifo.size(); head++) {
-        const int b = fifo[head], bx = b % width, by = b / width;
-        if (!rg_path_ok(cells[b])) continue;  // nobody can step onto it: not expanded
-        for (int d = 0; d < 8; d++) {
-            const int dx = rg_path_dx(d), dy = rg_path_dy(d), ax = bx - dx, ay = by - dy;
-            if (ax < 0 || ay < 0 || ax >= width || ay >= height) continue;
-            const int a = ay * width + ax;
-            if (D[a] != RG_PATH_INF || !rg_path_ok(cells[a]) || !rg_can_move(cells, height, width, ax, ay, dx, dy)) continue;
-            D[a] = (uint16_t)(D[b] + 1);
-            fifo.push_back(a);
-        }
-    }
-    const uint32_t dp = D[py * width + px];
-    uint32_t dirs = 0;
-    if (dp != 0 && dp != RG_PATH_INF)
-        for (int d = 0; d < 8; d++) {
-            const int dx = rg_path_dx(d), dy = rg_path_dy(d);
-            if (rg_can_move(cells, height, width, px, py, dx, dy) && D[(py + dy) * width + px + dx] == dp - 1) dirs |= 1u << d;
-        }
-    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
-    if (dist_out) *dist_out = rg_path_dist(dp);
-    if (key_out) *key_out = rg_path_key(dead, dp, (goals & RG_GOAL_STAIRS) && (cells[py * width + px] & C_SURF_MASK) == S_STAIR, dirs);
-    return 0;
-}
-// Search-aware and map-aware routes (rg_route.hip; the rule: rg_route.h).  route_args_check: the words of a call, refused before anything is launched.
-static int route_args_check(std::string &err, const char *what, uint32_t goals, uint32_t fallback, uint32_t mode, bool have_cells, const char *cells_name) {
-    const std::string w = std::string(what) + ": ";
-    if (goals == 0 || (goals & ~RG_ROUTE_GOALS_ALL)) {
-        err = w + "goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(goals);
-        return 1;
-    }
-    if (fallback & ~RG_ROUTE_GOALS_ALL) {
-        err = w + "fallback_goals must be 0 or an OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(fallback);
-        return 1;
-    }
-    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
-    if (((goals | fallback) & RG_GOAL_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
-        err = w + "RG_GOAL_FRONTIER in " + ((goals & RG_GOAL_FRONTIER) ? "goals" : "fallback_goals") + " needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " +
-              std::to_string(mode);
-        return 1;
-    }
-    if (((goals | fallback) & RG_GOAL_CELL) && !have_cells) {
-        err = w + cells_name + " is NULL and " + ((goals & RG_GOAL_CELL) ? "goals" : "fallback_goals") + " has RG_GOAL_CELL";
-        return 1;
-    }
-    return 0;
-}
-static int route_checked(rg_t *h, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
-    return reader_launch(h, [=](rg_t *l) { rgk_route(&l->S, &l->cfg, goals, fallback, mode, cells_dev, dist_dev, key_dev, tier_dev, l->stream); });
+    return rgh_path(g_create_err, cells, height, width, px, py, dead, goals, cell_y, cell_x, field_out, dist_out, key_out);
 }
 int rg_route(rg_t *h, uint32_t goals, uint32_t fallback_goals, uint32_t mode, const int32_t *cells_dev, int32_t *dist_dev, uint8_t *key_dev, uint8_t *tier_dev) {
     if (route_args_check(h->err, "rg_route", goals, fallback_goals, mode, cells_dev != nullptr, "cells_dev")) return 1;
     if (!dist_dev && !key_dev && !tier_dev) { h->err = "rg_route: dist_dev, key_dev and tier_dev are all NULL"; return 1; }
-    return route_checked(h, goals, fallback_goals, mode, cells_dev, dist_dev, key_dev, tier_dev);
+    return reader_launch(h, [=](rg_t *l) { rgk_route(&l->S, &l->cfg, goals, fallback_goals, mode, cells_dev, dist_dev, key_dev, tier_dev, l->stream); });
 }
-// One FIFO search per tier over rg_route.h's pieces, as rg_path_host's: a predecessor of cell b in direction d is the cell a = b - d, itself pass, with the
-// two corner cells of a diagonal asked for `corner`.
 int rg_route_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, uint32_t fallback_goals, uint32_t mode, int cell_y, int cell_x,
                   uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out) {
-    if (route_args_check(g_create_err, "rg_route_host", goals, fallback_goals, mode, true, "cells")) return 1;
-    if (!field_out && !dist_out && !key_out && !tier_out) { g_create_err = "rg_route_host: field_out, dist_out, key_out and tier_out are all NULL"; return 1; }
-    if (grid_check(g_create_err, "rg_route_host", cells, height, width) || player_check(g_create_err, "rg_route_host", px, py, height, width)) return 1;
-    const int hw = height * width, pi = py * width + px;
-    auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < width && y < height && !rg_route_known(cells[y * width + x], y * width + x == pi); };
-    auto frontier_at = [&](int i) {
-        const int x = i % width, y = i / width;
-        return rg_route_frontier(cells[i], mode, i == pi, unknown_at(x - 1, y) || unknown_at(x + 1, y) || unknown_at(x, y - 1) || unknown_at(x, y + 1));
-    };
-    std::vector<uint16_t> D;
-    std::vector<int> fifo;
-    fifo.reserve((size_t)hw);
-    uint32_t dp = RG_PATH_INF, tier = RG_ROUTE_NO_TIER, gw = goals;
-    for (uint32_t t = 0; t < 2 && tier == RG_ROUTE_NO_TIER; t++) {
-        if (t && !fallback_goals) break;
-        gw = t ? fallback_goals : goals;
-        D.assign((size_t)hw, (uint16_t)RG_PATH_INF);
-        fifo.clear();
-        for (int i = 0; i < hw; i++) {
-            const int x = i % width, y = i / width;
-            if (rg_route_goal(cells[i], gw, mode, i == pi, x == cell_x && y == cell_y) || ((gw & RG_GOAL_FRONTIER) && frontier_at(i))) { D[i] = 0; fifo.push_back(i); }
-        }
-        // (without field_out the search ends once the player's cell has its distance: every cell one move closer has its own by then)
-        for (size_t head = 0; head < fifo.size() && (field_out || D[pi] == RG_PATH_INF); head++) {
-            const int b = fifo[head], bx = b % width, by = b / width;
-            if (!rg_route_pass(cells[b], mode, b == pi)) continue;  // nobody can step onto it: not expanded
-            for (int d = 0; d < 8; d++) {
-                const int dx = rg_path_dx(d), dy = rg_path_dy(d), ax = bx - dx, ay = by - dy;
-                if (ax < 0 || ay < 0 || ax >= width || ay >= height) continue;
-                const int a = ay * width + ax;
-                if (D[a] != RG_PATH_INF || !rg_route_pass(cells[a], mode, a == pi)) continue;
-                if (dx != 0 && dy != 0 && !(rg_route_corner(cells[ay * width + bx], mode, ay * width + bx == pi) && rg_route_corner(cells[by * width + ax], mode, by * width + ax == pi)))
-                    continue;
-                D[a] = (uint16_t)(D[b] + 1);
-                fifo.push_back(a);
-            }
-        }
-        dp = D[pi];
-        if (dp != RG_PATH_INF) tier = t;
-    }
-    uint32_t dirs = 0;
-    if (dp != 0 && dp != RG_PATH_INF)
-        for (int d = 0; d < 8; d++) {
-            const int dx = rg_path_dx(d), dy = rg_path_dy(d), x = px + dx, y = py + dy;
-            if (x < 0 || y < 0 || x >= width || y >= height) continue;
-            const uint32_t t = cells[y * width + x];
-            bool ok = rg_route_pass(t, mode, false) && !rg_route_secret(t) && D[y * width + x] == dp - 1;
-            if (dx != 0 && dy != 0) ok = ok && rg_route_corner(cells[py * width + x], mode, false) && rg_route_corner(cells[y * width + px], mode, false);
-            dirs |= (uint32_t)ok << d;
-        }
-    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
-    if (dist_out) *dist_out = rg_path_dist(dp);
-    if (key_out) *key_out = rg_route_key(dead, dp, gw, (cells[pi] & C_SURF_MASK) == S_STAIR, (gw & RG_GOAL_FRONTIER) && frontier_at(pi), dirs);
-    if (tier_out) *tier_out = (uint8_t)tier;
-    return 0;
-}
-// ---- monster tables and threat words (rg_monsters.h; k_monsters in rg_monsters.hip) ----
-// mon_args_check: the words of a call, refused before anything is launched or written
-static int mon_args_check(std::string &err, const char *what, uint32_t mode, int cap, bool have_table, bool have_threat, const char *table_name, const char *threat_name) {
-    const std::string w = std::string(what) + ": ";
-    if (mode != RG_MON_SHOWN && mode != RG_MON_ALL) { err = w + "mode must be RG_MON_SHOWN (0) or RG_MON_ALL (1), got " + std::to_string(mode); return 1; }
-    if (!have_table && !have_threat) { err = w + table_name + " and " + threat_name + " are both NULL"; return 1; }
-    if (have_table && (cap < 1 || cap > RG_MON_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_MON_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
-    return 0;
-}
-static int monsters_checked(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
-    return reader_launch(h, [=](rg_t *l) { rgk_monsters(&l->S, &l->cfg, mode, cap, table_dev, threat_dev, l->stream); });
+    return rgh_route(g_create_err, cells, height, width, px, py, dead, goals, fallback_goals, mode, cell_y, cell_x, field_out, dist_out, key_out, tier_out);
 }
 int rg_monsters(rg_t *h, uint32_t mode, int cap, int16_t *table_dev, int32_t *threat_dev) {
     if (mon_args_check(h->err, "rg_monsters", mode, cap, table_dev != nullptr, threat_dev != nullptr, "table_dev", "threat_dev")) return 1;
     if (((uintptr_t)table_dev | (uintptr_t)threat_dev) & 15) { h->err = "rg_monsters: table_dev and threat_dev must be 16-byte aligned device pointers"; return 1; }
-    return monsters_checked(h, mode, cap, table_dev, threat_dev);
+    return reader_launch(h, [=](rg_t *l) { rgk_monsters(&l->S, &l->cfg, mode, cap, table_dev, threat_dev, l->stream); });
 }
-// Every qualifier gets its key, the keys are sorted, the first cap become rows: the plain form of what k_monsters keeps in registers.
 int rg_monsters_host(const uint16_t *cells, int height, int width, int px, int py, int dead, int n_mon, const int32_t *mon_x, const int32_t *mon_y, const int32_t *mon_type,
                      const int32_t *mon_active, const int32_t *mon_hp, const int32_t *mon_alive, int room_num_x, int room_num_y, const uint32_t *room_rect,
                      const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out) {
-    std::string &err = g_create_err;
-    if (mon_args_check(err, "rg_monsters_host", mode, cap, table_out != nullptr, threat_out != nullptr, "table_out", "threat_out")) return 1;
-    if (grid_check(err, "rg_monsters_host", cells, height, width) || player_check(err, "rg_monsters_host", px, py, height, width)) return 1;
-    if (n_mon < 0 || n_mon > RG_MAX_ROOMS) { err = "rg_monsters_host: n_mon must satisfy 0 <= n_mon <= " + std::to_string(RG_MAX_ROOMS) + ", got " + std::to_string(n_mon); return 1; }
-    if (n_mon > 0 && (!mon_x || !mon_y || !mon_type || !mon_active || !mon_hp)) { err = "rg_monsters_host: mon_x, mon_y, mon_type, mon_active and mon_hp must not be NULL"; return 1; }
-    if (room_num_x < 1 || room_num_y < 1 || room_num_x > width || room_num_y > height || room_num_x * room_num_y > RG_MAX_ROOMS) {
-        err = "rg_monsters_host: room_num_x, room_num_y = (" + std::to_string(room_num_x) + ", " + std::to_string(room_num_y) + ") do not fit the grid";
-        return 1;
-    }
-    if (!room_rect || !room_meta) { err = "rg_monsters_host: room_rect and room_meta must not be NULL"; return 1; }
-    for (int i = 0; i < n_mon; i++) {
-        if (mon_alive && !mon_alive[i]) continue;
-        if (mon_x[i] < 0 || mon_y[i] < 0 || mon_x[i] >= width || mon_y[i] >= height) {
-            err = "rg_monsters_host: monster " + std::to_string(i) + " at (" + std::to_string(mon_x[i]) + ", " + std::to_string(mon_y[i]) + ") is outside the grid";
-            return 1;
-        }
-        if (mon_type[i] < 0 || mon_type[i] > 25) { err = "rg_monsters_host: mon_type[" + std::to_string(i) + "] = " + std::to_string(mon_type[i]) + " is not a tile index 0 .. 25"; return 1; }
-    }
-    RgMonEnv E = {px, py, height, 0, 0, 0, 0, 0, 0, 0, 0, false, false};
-    const int id = rg_mon_area(E, px, py, width, height, room_num_x, room_num_y);
-    if (id >= 0) rg_mon_room(E, room_rect[id], (uint32_t)room_meta[id]);
-    RgMonThreat T;
-    rg_mon_threat_init(T);
-    std::vector<std::pair<uint64_t, uint32_t>> list;
-    for (int i = 0; i < n_mon && !dead; i++) {
-        if (mon_alive && !mon_alive[i]) continue;
-        const int x = mon_x[i], y = mon_y[i];
-        const bool shown = rg_mon_shown(E, cells[y * width + x], x, y), q = mode == RG_MON_ALL || shown;
-        rg_mon_threat_add(T, px, py, x, y, shown, q);
-        if (q) list.emplace_back(rg_mon_key(px, py, x, y, shown, i), rg_mon_pay((uint32_t)('A' + mon_type[i]), mon_active[i] != 0, mon_hp[i]));
-    }
-    std::sort(list.begin(), list.end());
-    if (table_out)
-        for (int r = 0; r < cap; r++) {
-            uint32_t row[4];
-            rg_mon_row(r < (int)list.size() ? list[r].first : RG_MON_EMPTY_KEY, r < (int)list.size() ? list[r].second : 0u, px, py, mode, row);
-            memcpy(table_out + (size_t)r * RG_MON_COLS, row, 16);
-        }
-    if (threat_out) { threat_out[0] = T.adjacent; threat_out[1] = T.nearest; threat_out[2] = T.attack; threat_out[3] = T.count; }
-    return 0;
-}
-// ---- object tables by walking distance (rg_objects.h; k_objects in rg_objects.hip) ----
-// obj_args_check: the words of a call, refused before anything is launched or written
-static int obj_args_check(std::string &err, const char *what, uint32_t kinds, uint32_t mode, int cap, bool have_table, bool have_count, const char *table_name, const char *count_name) {
-    const std::string w = std::string(what) + ": ";
-    if (kinds == 0 || (kinds & ~RG_OBJ_KINDS_ALL)) {
-        err = w + "kinds must be a non-empty OR of RG_OBJ_STAIRS (1), RG_OBJ_GOLD (2), RG_OBJ_DOOR (4) and RG_OBJ_FRONTIER (8), got " + std::to_string(kinds);
-        return 1;
-    }
-    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
-    if ((kinds & RG_OBJ_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
-        err = w + "RG_OBJ_FRONTIER in kinds needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " + std::to_string(mode);
-        return 1;
-    }
-    if (!have_table && !have_count) { err = w + table_name + " and " + count_name + " are both NULL"; return 1; }
-    if (have_table && (cap < 1 || cap > RG_OBJ_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_OBJ_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
-    return 0;
+    return rgh_monsters(g_create_err, cells, height, width, px, py, dead, n_mon, mon_x, mon_y, mon_type, mon_active, mon_hp, mon_alive, room_num_x, room_num_y, room_rect, room_meta, mode,
+                        cap, table_out, threat_out);
 }
 int rg_objects(rg_t *h, uint32_t kinds, uint32_t mode, int cap, int16_t *table_dev, int32_t *count_dev) {
     if (obj_args_check(h->err, "rg_objects", kinds, mode, cap, table_dev != nullptr, count_dev != nullptr, "table_dev", "count_dev")) return 1;
     if (((uintptr_t)table_dev | (uintptr_t)count_dev) & 15) { h->err = "rg_objects: table_dev and count_dev must be 16-byte aligned device pointers"; return 1; }
     return reader_launch(h, [=](rg_t *l) { rgk_objects(&l->S, &l->cfg, kinds, mode, cap, table_dev, count_dev, l->stream); });
 }
-// One FIFO search from the player's cell over rg_route.h's moves: the queue's order is ascending walk, so the objects it meets are sorted by
-// (walk, y, x) within each walk and the first cap of them are the table.
 int rg_objects_host(const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t kinds, uint32_t mode, int cap, int16_t *table_out, int32_t *count_out) {
-    std::string &err = g_create_err;
-    if (obj_args_check(err, "rg_objects_host", kinds, mode, cap, table_out != nullptr, count_out != nullptr, "table_out", "count_out")) return 1;
-    if (grid_check(err, "rg_objects_host", cells, height, width) || player_check(err, "rg_objects_host", px, py, height, width)) return 1;
-    const int hw = height * width, pi = py * width + px;
-    auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < width && y < height && !rg_route_known(cells[y * width + x], y * width + x == pi); };
-    auto kind_at = [&](int i) {
-        const int x = i % width, y = i / width;
-        return rg_obj_kind(cells[i], kinds, mode, i == pi, unknown_at(x - 1, y) || unknown_at(x + 1, y) || unknown_at(x, y - 1) || unknown_at(x, y + 1));
-    };
-    int32_t count[4] = {0, 0, 0, 0};
-    std::vector<std::pair<uint32_t, uint32_t>> list;  // (walk << 16 | y << 8 | x, kind): the order of the table
-    if (!dead) {
-        std::vector<uint8_t> kind((size_t)hw);
-        for (int i = 0; i < hw; i++) {
-            kind[i] = (uint8_t)kind_at(i);
-            for (int k = 0; k < 4; k++) count[k] += (kind[i] >> k) & 1;
-        }
-        if (table_out) {
-            std::vector<uint16_t> D((size_t)hw, (uint16_t)RG_PATH_INF);
-            std::vector<int> fifo;
-            fifo.reserve((size_t)hw);
-            D[pi] = 0;
-            fifo.push_back(pi);
-            for (size_t head = 0; head < fifo.size(); head++) {
-                const int a = fifo[head], ax = a % width, ay = a / width;
-                if (kind[a]) list.emplace_back((uint32_t)D[a] << 16 | (uint32_t)ay << 8 | (uint32_t)ax, kind[a]);
-                for (int d = 0; d < 8; d++) {
-                    const int dx = rg_path_dx(d), dy = rg_path_dy(d), bx = ax + dx, by = ay + dy;
-                    if (bx < 0 || by < 0 || bx >= width || by >= height) continue;
-                    const int b = by * width + bx;
-                    if (D[b] != RG_PATH_INF || !rg_route_pass(cells[b], mode, b == pi)) continue;
-                    if (dx != 0 && dy != 0 && !(rg_route_corner(cells[ay * width + bx], mode, ay * width + bx == pi) && rg_route_corner(cells[by * width + ax], mode, by * width + ax == pi)))
-                        continue;
-                    D[b] = (uint16_t)(D[a] + 1);
-                    fifo.push_back(b);
-                }
-            }
-            std::sort(list.begin(), list.end());
-        }
-    }
-    if (table_out)
-        for (int r = 0; r < cap; r++) {
-            uint32_t row[4] = {0u, 0u, 0u, 0u};
-            if (r < (int)list.size()) rg_obj_row(list[r].second, px, py, (int)(list[r].first & 0xffu), (int)((list[r].first >> 8) & 0xffu), list[r].first >> 16, row);
-            memcpy(table_out + (size_t)r * RG_OBJ_COLS, row, 16);
-        }
-    if (count_out) memcpy(count_out, count, sizeof count);
-    return 0;
+    return rgh_objects(g_create_err, cells, height, width, px, py, dead, kinds, mode, cap, table_out, count_out);
 }
 // ---- episode accounting and the scout reward (rg_episode.h; k_episode in rg_episode.hip) ----
 int rg_episode_enable(rg_t *h, uint32_t what, int log_cap) {
@@ -1497,18 +1202,7 @@ int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint
     return 0;
 }
 int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out) {
-    if (!cells) { g_create_err = "rg_scout_host: cells must not be NULL"; return 1; }
-    if (!seen_inout) { g_create_err = "rg_scout_host: seen_inout must not be NULL"; return 1; }
-    if (grid_check(g_create_err, "rg_scout_host", cells, height, width)) return 1;
-    const int hw = height * width, sb = rg_ep_seen_bytes(hw);
-    int32_t fresh = 0;
-    for (int j = 0; j < sb; j++) {
-        uint32_t s = seen_inout[j];
-        fresh += __builtin_popcount(rg_ep_fresh(rg_ep_known_byte(cells, j, hw, width), s, false) & 0xffu);
-        seen_inout[j] = (uint8_t)(s & rg_ep_row_bits(j, hw, width));  // (bits that can never count are written 0, whatever the caller passed)
-    }
-    if (fresh_out) *fresh_out = fresh;
-    return 0;
+    return rgh_scout(g_create_err, cells, height, width, seen_inout, fresh_out);
 }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }

@@ -1,5 +1,5 @@
 // rg_episode.h -- episode accounting and the scout reward: THE statement of the rule (rg_episode_update / rg_episode_cut / rg_scout_host), on top of
-// rg_route.h's notion of a known cell.  Host and device: k_episode (rg_episode.hip) and rg_scout_host (rg_api.cpp) both call the pieces below.
+// rg_route.h's notion of a known cell.  Host and device: k_episode (rg_episode.hip) and rg_scout_host (rg_readers_host.h) both call the pieces below.
 //
 // k_step rebuilds a finished env in the launch that ends its episode: afterwards only reward[e] and done[e] = 1 are left of the old game -- the status
 // mirror shows level 1, the flag word has lost DEAD, the step counter is 0.  The lane state below is kept BESIDE the game state (it is not part of a state

@@ -1,5 +1,5 @@
 // rg_monsters.h -- the monsters of an env's level as an entity table, and the threat words: THE statement of the rule (rg_monsters / rg_monsters_host).
-// Host and device: k_monsters (rg_monsters.hip) and rg_monsters_host (rg_api.cpp) both call the pieces below, so the rule is written once.
+// Host and device: k_monsters (rg_monsters.hip) and rg_monsters_host (rg_readers_host.h) both call the pieces below, so the rule is written once.
 // file:line citations name the reference's sources.
 //
 // A monster of the env's current level is ALIVE when its slot has MF_ALIVE.  It is SHOWN when a Redraw at this moment would put its letter on the screen --

@@ -1,5 +1,5 @@
 // rg_objects.h -- the stairs, gold, doors and frontier cells of an env's level as an object table ordered by walking distance: THE statement of the rule
-// (rg_objects / rg_objects_host), on top of rg_route.h.  Host and device: k_objects (rg_objects.hip) and rg_objects_host (rg_api.cpp) both call the
+// (rg_objects / rg_objects_host), on top of rg_route.h.  Host and device: k_objects (rg_objects.hip) and rg_objects_host (rg_readers_host.h) both call the
 // pieces below, so the rule is written once.
 //
 // mode is rg_route's: RG_ROUTE_SECRETS walks THROUGH hidden / locked cells, RG_ROUTE_KNOWN reads the player's own map only (C_DRAWN / C_VISIBLE) -- with

@@ -1,5 +1,5 @@
 // rg_path.h -- shortest-path fields towards goal cells and the teacher key that follows them: THE statement of the rule (rg_path / rg_path_host).
-// Host and device: k_path (rg_path.hip) and rg_path_host (rg_api.cpp) both call the pieces below, and the move test itself is rg_action_mask.h's
+// Host and device: k_path (rg_path.hip) and rg_path_host (rg_readers_host.h) both call the pieces below, and the move test itself is rg_action_mask.h's
 // rg_walkable / rg_can_move (Floor::can_move_impl as the player), so nothing is stated twice.
 //
 // The field is PRIVILEGED: it sees stairs, gold and passages the player has not discovered.  It is a teacher, a shaping potential or a critic input,

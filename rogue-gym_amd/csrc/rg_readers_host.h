@@ -1,0 +1,304 @@
+// rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api.cpp) share with the *_host twins, and the
+// twins themselves (rgh_*; rg_action_mask_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host and rg_scout_host are one-line delegations in
+// rg_api.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
+// (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rg_action_mask.h"
+#include "rg_path.h"
+#include "rg_route.h"
+#include "rg_objects.h"
+#include "rg_monsters.h"
+#include "rg_episode.h"
+
+// ---- the argument checks: `what` is the entry's name ----
+static inline int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
+    const std::string w = std::string(what) + ": ";
+    if (!cells) { err = w + "cells must not be NULL"; return 1; }
+    if (height < 1 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        err = w + "height, width must satisfy 1 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" + std::to_string(height) +
+              ", " + std::to_string(width) + ")";
+        return 1;
+    }
+    return 0;
+}
+static inline int player_check(std::string &err, const char *what, int px, int py, int height, int width) {
+    if (px < 0 || py < 0 || px >= width || py >= height) {
+        err = std::string(what) + ": the player's cell (px, py) = (" + std::to_string(px) + ", " + std::to_string(py) + ") is outside the " + std::to_string(width) + " x " +
+              std::to_string(height) + " grid";
+        return 1;
+    }
+    return 0;
+}
+// the key list of a mask call; on success `list` holds the n_keys keys the call judges (NULL keys: RG_ACTION_KEYS)
+static inline int mask_keys_check(std::string &err, const char *what, const uint8_t *keys, int &n_keys, uint8_t list[RG_MASK_MAX_KEYS]) {
+    const std::string w = std::string(what) + ": ";
+    if (!keys) { keys = reinterpret_cast<const uint8_t *>(RG_ACTION_KEYS); n_keys = (int)(sizeof(RG_ACTION_KEYS) - 1); }
+    if (n_keys < 1 || n_keys > RG_MASK_MAX_KEYS) { err = w + "n_keys must satisfy 1 <= n_keys <= " + std::to_string(RG_MASK_MAX_KEYS) + ", got " + std::to_string(n_keys); return 1; }
+    for (int k = 0; k < n_keys; k++) {
+        if (rg_key_bit(keys[k]) == RG_LB_NONE) {
+            char hex[8];
+            snprintf(hex, sizeof hex, "0x%02x", keys[k]);
+            err = w + "keys[" + std::to_string(k) + "] = " + hex + (keys[k] >= 0x20 && keys[k] < 0x7f ? " ('" + std::string(1, (char)keys[k]) + "')" : std::string()) +
+                  " is not a key of KeyMap::ai (input.rs:73-100)";
+            return 1;
+        }
+        list[k] = keys[k];
+    }
+    return 0;
+}
+static inline int path_goals_check(std::string &err, const char *what, uint32_t goals) {
+    if (goals == 0 || (goals & ~RG_PATH_GOALS_ALL)) {
+        err = std::string(what) + ": goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2) and RG_GOAL_CELL (4), got " + std::to_string(goals);
+        return 1;
+    }
+    return 0;
+}
+static inline int route_args_check(std::string &err, const char *what, uint32_t goals, uint32_t fallback, uint32_t mode, bool have_cells, const char *cells_name) {
+    const std::string w = std::string(what) + ": ";
+    if (goals == 0 || (goals & ~RG_ROUTE_GOALS_ALL)) {
+        err = w + "goals must be a non-empty OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(goals);
+        return 1;
+    }
+    if (fallback & ~RG_ROUTE_GOALS_ALL) {
+        err = w + "fallback_goals must be 0 or an OR of RG_GOAL_STAIRS (1), RG_GOAL_GOLD (2), RG_GOAL_CELL (4) and RG_GOAL_FRONTIER (8), got " + std::to_string(fallback);
+        return 1;
+    }
+    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
+    if (((goals | fallback) & RG_GOAL_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
+        err = w + "RG_GOAL_FRONTIER in " + ((goals & RG_GOAL_FRONTIER) ? "goals" : "fallback_goals") + " needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " +
+              std::to_string(mode);
+        return 1;
+    }
+    if (((goals | fallback) & RG_GOAL_CELL) && !have_cells) {
+        err = w + cells_name + " is NULL and " + ((goals & RG_GOAL_CELL) ? "goals" : "fallback_goals") + " has RG_GOAL_CELL";
+        return 1;
+    }
+    return 0;
+}
+static inline int mon_args_check(std::string &err, const char *what, uint32_t mode, int cap, bool have_table, bool have_threat, const char *table_name, const char *threat_name) {
+    const std::string w = std::string(what) + ": ";
+    if (mode != RG_MON_SHOWN && mode != RG_MON_ALL) { err = w + "mode must be RG_MON_SHOWN (0) or RG_MON_ALL (1), got " + std::to_string(mode); return 1; }
+    if (!have_table && !have_threat) { err = w + table_name + " and " + threat_name + " are both NULL"; return 1; }
+    if (have_table && (cap < 1 || cap > RG_MON_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_MON_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
+    return 0;
+}
+static inline int obj_args_check(std::string &err, const char *what, uint32_t kinds, uint32_t mode, int cap, bool have_table, bool have_count, const char *table_name, const char *count_name) {
+    const std::string w = std::string(what) + ": ";
+    if (kinds == 0 || (kinds & ~RG_OBJ_KINDS_ALL)) {
+        err = w + "kinds must be a non-empty OR of RG_OBJ_STAIRS (1), RG_OBJ_GOLD (2), RG_OBJ_DOOR (4) and RG_OBJ_FRONTIER (8), got " + std::to_string(kinds);
+        return 1;
+    }
+    if (mode & ~RG_ROUTE_MODE_ALL) { err = w + "mode must be an OR of RG_ROUTE_SECRETS (1) and RG_ROUTE_KNOWN (2), got " + std::to_string(mode); return 1; }
+    if ((kinds & RG_OBJ_FRONTIER) && !(mode & RG_ROUTE_KNOWN)) {
+        err = w + "RG_OBJ_FRONTIER in kinds needs RG_ROUTE_KNOWN in mode (the frontier is of the player's own map), got mode " + std::to_string(mode);
+        return 1;
+    }
+    if (!have_table && !have_count) { err = w + table_name + " and " + count_name + " are both NULL"; return 1; }
+    if (have_table && (cap < 1 || cap > RG_OBJ_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_OBJ_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
+    return 0;
+}
+
+// ---- the grid search of the path, route and objects twins ----
+// A plain FIFO search over the eight moves of rg_path_dx / rg_path_dy: on return D[i] is the number of moves between cell i and the nearest cell that
+// source(i) names, RG_PATH_INF where there is none.  The step from the popped cell b in direction d reaches a = b - d; the corner rule of a diagonal names the
+// same two cells, (ay, bx) and (by, ax), from either end of the move, so one loop searches towards the sources (path, route) and away from them (objects).
+// visit(b): called as a cell is popped, false ends the search; expand(b): the popped cell may be stepped from (a source is in the queue whatever its word);
+// enter(a): a neighbour without a distance may get one; corner(i): what a diagonal asks of each of its two corner cells.
+template <class Source, class Expand, class Enter, class Corner, class Visit>
+static inline void rg_grid_search(int H, int W, std::vector<uint16_t> &D, Source source, Expand expand, Enter enter, Corner corner, Visit visit) {
+    std::vector<int> fifo;
+    fifo.reserve((size_t)H * W);
+    D.assign((size_t)H * W, (uint16_t)RG_PATH_INF);
+    for (int i = 0; i < H * W; i++)
+        if (source(i)) { D[i] = 0; fifo.push_back(i); }
+    for (size_t head = 0; head < fifo.size(); head++) {
+        const int b = fifo[head], bx = b % W, by = b / W;
+        if (!visit(b)) return;
+        if (!expand(b)) continue;
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d), ax = bx - dx, ay = by - dy;
+            if (ax < 0 || ay < 0 || ax >= W || ay >= H) continue;
+            const int a = ay * W + ax;
+            if (D[a] != RG_PATH_INF || !enter(a)) continue;
+            if (dx != 0 && dy != 0 && !(corner(ay * W + bx) && corner(by * W + ax))) continue;
+            D[a] = (uint16_t)(D[b] + 1);
+            fifo.push_back(a);
+        }
+    }
+}
+// rg_route_frontier's unknown_beside for cell i: some in-grid orthogonal neighbour is not on the player's map; pi = the player's cell
+static inline bool rg_unknown_beside(const uint16_t *cells, int H, int W, int pi, int i) {
+    const int x = i % W, y = i / W;
+    auto unknown_at = [&](int x, int y) { return x >= 0 && y >= 0 && x < W && y < H && !rg_route_known(cells[y * W + x], y * W + x == pi); };
+    return unknown_at(x - 1, y) || unknown_at(x + 1, y) || unknown_at(x, y - 1) || unknown_at(x, y + 1);
+}
+
+// ---- the twins ----
+static inline int rgh_action_mask(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys, uint8_t *out) {
+    uint8_t list[RG_MASK_MAX_KEYS];
+    if (mask_keys_check(err, "rg_action_mask_host", keys, n_keys, list)) return 1;
+    if (!cells || !out) { err = "rg_action_mask_host: cells and out must not be NULL"; return 1; }
+    if (player_check(err, "rg_action_mask_host", px, py, height, width)) return 1;  // (an empty grid has no cell inside it: the same refusal)
+    for (int k = 0; k < n_keys; k++) out[k] = (uint8_t)rg_key_legal(cells, height, width, px, py, dead, list[k]);
+    return 0;
+}
+// The search runs from the goal cells over rg_path.h's pieces: rg_can_move(a -> b) taken apart into its target (expand), its start (enter) and its corners.
+static inline int rgh_path(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, int cell_y, int cell_x, uint16_t *field_out,
+                           int32_t *dist_out, uint8_t *key_out) {
+    if (path_goals_check(err, "rg_path_host", goals)) return 1;
+    if (!field_out && !dist_out && !key_out) { err = "rg_path_host: field_out, dist_out and key_out are all NULL"; return 1; }
+    if (grid_check(err, "rg_path_host", cells, height, width) || player_check(err, "rg_path_host", px, py, height, width)) return 1;
+    const int hw = height * width;
+    std::vector<uint16_t> D;
+    auto goal = [&](int i) { return rg_path_goal(cells[i], goals, i == py * width + px, i % width == cell_x && i / width == cell_y); };
+    auto ok = [&](int i) { return rg_path_ok(cells[i]); };  // (a goal nobody can step onto is not expanded)
+    rg_grid_search(height, width, D, goal, ok, ok, [&](int i) { return rg_walkable(cells[i]); }, [](int) { return true; });
+    const uint32_t dp = D[py * width + px];
+    uint32_t dirs = 0;
+    if (dp != 0 && dp != RG_PATH_INF)
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d);
+            if (rg_can_move(cells, height, width, px, py, dx, dy) && D[(py + dy) * width + px + dx] == dp - 1) dirs |= 1u << d;
+        }
+    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
+    if (dist_out) *dist_out = rg_path_dist(dp);
+    if (key_out) *key_out = rg_path_key(dead, dp, (goals & RG_GOAL_STAIRS) && (cells[py * width + px] & C_SURF_MASK) == S_STAIR, dirs);
+    return 0;
+}
+// One search per tier over rg_route.h's pieces, from the tier's goal cells.
+static inline int rgh_route(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t goals, uint32_t fallback_goals, uint32_t mode,
+                            int cell_y, int cell_x, uint16_t *field_out, int32_t *dist_out, uint8_t *key_out, uint8_t *tier_out) {
+    if (route_args_check(err, "rg_route_host", goals, fallback_goals, mode, true, "cells")) return 1;
+    if (!field_out && !dist_out && !key_out && !tier_out) { err = "rg_route_host: field_out, dist_out, key_out and tier_out are all NULL"; return 1; }
+    if (grid_check(err, "rg_route_host", cells, height, width) || player_check(err, "rg_route_host", px, py, height, width)) return 1;
+    const int hw = height * width, pi = py * width + px;
+    auto frontier_at = [&](int i) { return rg_route_frontier(cells[i], mode, i == pi, rg_unknown_beside(cells, height, width, pi, i)); };
+    auto pass = [&](int i) { return rg_route_pass(cells[i], mode, i == pi); };  // (a goal nobody can step onto is not expanded)
+    auto corner = [&](int i) { return rg_route_corner(cells[i], mode, i == pi); };
+    std::vector<uint16_t> D;
+    uint32_t dp = RG_PATH_INF, tier = RG_ROUTE_NO_TIER, gw = goals;
+    for (uint32_t t = 0; t < 2 && tier == RG_ROUTE_NO_TIER; t++) {
+        if (t && !fallback_goals) break;
+        gw = t ? fallback_goals : goals;
+        auto goal = [&](int i) {
+            return rg_route_goal(cells[i], gw, mode, i == pi, i % width == cell_x && i / width == cell_y) || ((gw & RG_GOAL_FRONTIER) && frontier_at(i));
+        };
+        // (without field_out the search ends once the player's cell has its distance: every cell one move closer has its own by then)
+        rg_grid_search(height, width, D, goal, pass, pass, corner, [&](int) { return field_out || D[pi] == RG_PATH_INF; });
+        dp = D[pi];
+        if (dp != RG_PATH_INF) tier = t;
+    }
+    uint32_t dirs = 0;
+    if (dp != 0 && dp != RG_PATH_INF)
+        for (int d = 0; d < 8; d++) {
+            const int dx = rg_path_dx(d), dy = rg_path_dy(d), x = px + dx, y = py + dy;
+            if (x < 0 || y < 0 || x >= width || y >= height) continue;
+            const uint32_t t = cells[y * width + x];
+            bool ok = rg_route_pass(t, mode, false) && !rg_route_secret(t) && D[y * width + x] == dp - 1;
+            if (dx != 0 && dy != 0) ok = ok && rg_route_corner(cells[py * width + x], mode, false) && rg_route_corner(cells[y * width + px], mode, false);
+            dirs |= (uint32_t)ok << d;
+        }
+    if (field_out) memcpy(field_out, D.data(), (size_t)hw * sizeof(uint16_t));
+    if (dist_out) *dist_out = rg_path_dist(dp);
+    if (key_out) *key_out = rg_route_key(dead, dp, gw, (cells[pi] & C_SURF_MASK) == S_STAIR, (gw & RG_GOAL_FRONTIER) && frontier_at(pi), dirs);
+    if (tier_out) *tier_out = (uint8_t)tier;
+    return 0;
+}
+// Every qualifier gets its key, the keys are sorted, the first cap become rows: the plain form of what k_monsters keeps in registers.
+static inline int rgh_monsters(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, int n_mon, const int32_t *mon_x, const int32_t *mon_y,
+                               const int32_t *mon_type, const int32_t *mon_active, const int32_t *mon_hp, const int32_t *mon_alive, int room_num_x, int room_num_y,
+                               const uint32_t *room_rect, const int32_t *room_meta, uint32_t mode, int cap, int16_t *table_out, int32_t *threat_out) {
+    if (mon_args_check(err, "rg_monsters_host", mode, cap, table_out != nullptr, threat_out != nullptr, "table_out", "threat_out")) return 1;
+    if (grid_check(err, "rg_monsters_host", cells, height, width) || player_check(err, "rg_monsters_host", px, py, height, width)) return 1;
+    if (n_mon < 0 || n_mon > RG_MAX_ROOMS) { err = "rg_monsters_host: n_mon must satisfy 0 <= n_mon <= " + std::to_string(RG_MAX_ROOMS) + ", got " + std::to_string(n_mon); return 1; }
+    if (n_mon > 0 && (!mon_x || !mon_y || !mon_type || !mon_active || !mon_hp)) { err = "rg_monsters_host: mon_x, mon_y, mon_type, mon_active and mon_hp must not be NULL"; return 1; }
+    if (room_num_x < 1 || room_num_y < 1 || room_num_x > width || room_num_y > height || room_num_x * room_num_y > RG_MAX_ROOMS) {
+        err = "rg_monsters_host: room_num_x, room_num_y = (" + std::to_string(room_num_x) + ", " + std::to_string(room_num_y) + ") do not fit the grid";
+        return 1;
+    }
+    if (!room_rect || !room_meta) { err = "rg_monsters_host: room_rect and room_meta must not be NULL"; return 1; }
+    for (int i = 0; i < n_mon; i++) {
+        if (mon_alive && !mon_alive[i]) continue;
+        if (mon_x[i] < 0 || mon_y[i] < 0 || mon_x[i] >= width || mon_y[i] >= height) {
+            err = "rg_monsters_host: monster " + std::to_string(i) + " at (" + std::to_string(mon_x[i]) + ", " + std::to_string(mon_y[i]) + ") is outside the grid";
+            return 1;
+        }
+        if (mon_type[i] < 0 || mon_type[i] > 25) { err = "rg_monsters_host: mon_type[" + std::to_string(i) + "] = " + std::to_string(mon_type[i]) + " is not a tile index 0 .. 25"; return 1; }
+    }
+    RgMonEnv E = {px, py, height, 0, 0, 0, 0, 0, 0, 0, 0, false, false};
+    const int id = rg_mon_area(E, px, py, width, height, room_num_x, room_num_y);
+    if (id >= 0) rg_mon_room(E, room_rect[id], (uint32_t)room_meta[id]);
+    RgMonThreat T;
+    rg_mon_threat_init(T);
+    std::vector<std::pair<uint64_t, uint32_t>> list;
+    for (int i = 0; i < n_mon && !dead; i++) {
+        if (mon_alive && !mon_alive[i]) continue;
+        const int x = mon_x[i], y = mon_y[i];
+        const bool shown = rg_mon_shown(E, cells[y * width + x], x, y), q = mode == RG_MON_ALL || shown;
+        rg_mon_threat_add(T, px, py, x, y, shown, q);
+        if (q) list.emplace_back(rg_mon_key(px, py, x, y, shown, i), rg_mon_pay((uint32_t)('A' + mon_type[i]), mon_active[i] != 0, mon_hp[i]));
+    }
+    std::sort(list.begin(), list.end());
+    if (table_out)
+        for (int r = 0; r < cap; r++) {
+            uint32_t row[4];
+            rg_mon_row(r < (int)list.size() ? list[r].first : RG_MON_EMPTY_KEY, r < (int)list.size() ? list[r].second : 0u, px, py, mode, row);
+            memcpy(table_out + (size_t)r * RG_MON_COLS, row, 16);
+        }
+    if (threat_out) { threat_out[0] = T.adjacent; threat_out[1] = T.nearest; threat_out[2] = T.attack; threat_out[3] = T.count; }
+    return 0;
+}
+// One search from the player's cell over rg_route.h's moves, only when a table is asked for: the objects it meets, sorted by (walk, y, x), and the first cap
+// of them are the table.
+static inline int rgh_objects(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, uint32_t kinds, uint32_t mode, int cap, int16_t *table_out,
+                              int32_t *count_out) {
+    if (obj_args_check(err, "rg_objects_host", kinds, mode, cap, table_out != nullptr, count_out != nullptr, "table_out", "count_out")) return 1;
+    if (grid_check(err, "rg_objects_host", cells, height, width) || player_check(err, "rg_objects_host", px, py, height, width)) return 1;
+    const int hw = height * width, pi = py * width + px;
+    int32_t count[4] = {0, 0, 0, 0};
+    std::vector<std::pair<uint32_t, uint32_t>> list;  // (walk << 16 | y << 8 | x, kind): the order of the table
+    if (!dead) {
+        std::vector<uint8_t> kind((size_t)hw);
+        for (int i = 0; i < hw; i++) {
+            kind[i] = (uint8_t)rg_obj_kind(cells[i], kinds, mode, i == pi, rg_unknown_beside(cells, height, width, pi, i));
+            for (int k = 0; k < 4; k++) count[k] += (kind[i] >> k) & 1;
+        }
+        if (table_out) {
+            std::vector<uint16_t> D;
+            auto listed = [&](int i) { if (kind[i]) list.emplace_back((uint32_t)D[i] << 16 | (uint32_t)(i / width) << 8 | (uint32_t)(i % width), kind[i]); return true; };
+            // (the player's own cell starts the search whatever its word; any other cell is in the queue only because it passed)
+            rg_grid_search(height, width, D, [&](int i) { return i == pi; }, [](int) { return true; }, [&](int i) { return rg_route_pass(cells[i], mode, i == pi); },
+                           [&](int i) { return rg_route_corner(cells[i], mode, i == pi); }, listed);
+            std::sort(list.begin(), list.end());
+        }
+    }
+    if (table_out)
+        for (int r = 0; r < cap; r++) {
+            uint32_t row[4] = {0u, 0u, 0u, 0u};
+            if (r < (int)list.size()) rg_obj_row(list[r].second, px, py, (int)(list[r].first & 0xffu), (int)((list[r].first >> 8) & 0xffu), list[r].first >> 16, row);
+            memcpy(table_out + (size_t)r * RG_OBJ_COLS, row, 16);
+        }
+    if (count_out) memcpy(count_out, count, sizeof count);
+    return 0;
+}
+// the scout reward of one step: the cells known for the first time, `seen` advanced
+static inline int rgh_scout(std::string &err, const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out) {
+    if (!cells) { err = "rg_scout_host: cells must not be NULL"; return 1; }
+    if (!seen_inout) { err = "rg_scout_host: seen_inout must not be NULL"; return 1; }
+    if (grid_check(err, "rg_scout_host", cells, height, width)) return 1;
+    const int hw = height * width, sb = rg_ep_seen_bytes(hw);
+    int32_t fresh = 0;
+    for (int j = 0; j < sb; j++) {
+        uint32_t s = seen_inout[j];
+        fresh += __builtin_popcount(rg_ep_fresh(rg_ep_known_byte(cells, j, hw, width), s, false) & 0xffu);
+        seen_inout[j] = (uint8_t)(s & rg_ep_row_bits(j, hw, width));  // (bits that can never count are written 0, whatever the caller passed)
+    }
+    if (fresh_out) *fresh_out = fresh;
+    return 0;
+}

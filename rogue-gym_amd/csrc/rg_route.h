@@ -1,5 +1,5 @@
 // rg_route.h -- search-aware and map-aware routes: THE statement of the rule (rg_route / rg_route_host), on top of rg_path.h and rg_action_mask.h.
-// Host and device: k_route (rg_route.hip) and rg_route_host (rg_api.cpp) both call the pieces below.
+// Host and device: k_route (rg_route.hip) and rg_route_host (rg_readers_host.h) both call the pieces below.
 //
 // rg_path's rule has one notion of "passable".  Here two orthogonal mode bits vary it: RG_ROUTE_SECRETS plans THROUGH hidden / locked cells and asks for
 // 's' when the next cell is one (Search touches the eight cells around the player, floor.rs:349-370); RG_ROUTE_KNOWN plans on the player's own map only
