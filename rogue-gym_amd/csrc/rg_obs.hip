@@ -593,11 +593,15 @@ __global__ void __launch_bounds__(WAVE) k_obs_stream(RgState S, RgConfig c, floa
 // ---------------------------------------------------------------------------------------------
 // One wave owns a run of OBS_RESID_RUN consecutive envs, persistent and one run ahead with the flag words and masks (lane i: env i of the run).  The mirror
 // words of the run's masked lines are requested together once those are known, then stored; then the run's Redraw envs, one at a time.
+// OBS_RESID_WAVES caps the grid (rgk_obs_resid_blocks).  54 VGPRs and 104 SGPRs: seven waves per SIMD as the compiler reports it, 7 168 resident one-wave
+// blocks on the chip.  The cap comes from the grid sweep of profiles/r11_experiments.txt, 65 536 envs, one MI355X only: the pass is flat between 6 144 and
+// 16 384 waves (11.1 - 11.7 us) and a latency chain below (about 1 us more for every further run a wave walks); 10 240 waves -- 1.6 runs per wave, 1.4
+// residency rounds -- gave the best `value`, +0.7 % against a wave per run (16 384).
 #ifndef OBS_RESID_RUN
 #define OBS_RESID_RUN 4
 #endif
 #ifndef OBS_RESID_WAVES
-#define OBS_RESID_WAVES 16384
+#define OBS_RESID_WAVES 10240
 #endif
 __global__ void __launch_bounds__(WAVE) k_obs_resid(RgState S, RgConfig c, float *__restrict__ out) {
     __shared__ float lutf[128];                              // glyph -> gray value
@@ -1028,10 +1032,20 @@ int rgk_obs_tail_capable(const RgState *S, const RgConfig *c) {
     return 1;
 }
 // the fix-up pass behind a step launch that pre-streamed the images (S->enc_rows is that launch's): its Redraw envs and the image lines its turns touched
+// its grid: one-wave blocks, never more than there are runs, at most OBS_RESID_WAVES of them (each then loops over runs gridDim.x apart, one run ahead
+// with the flag words).  Development builds: RG_OBS_RESID_BLOCKS > 0 takes the cap's place, read at every launch (the grid sweep, and the tests that let
+// one wave walk every run).
+int rgk_obs_resid_blocks(int n) {
+    const int nruns = (n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
+    int cap = OBS_RESID_WAVES;
+#ifdef RG_DEV_KNOBS
+    if (const char *ev = getenv("RG_OBS_RESID_BLOCKS")) if (atoi(ev) > 0) cap = atoi(ev);
+#endif
+    const int blocks = nruns < cap ? nruns : cap;
+    return blocks < 1 ? 1 : blocks;
+}
 void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-    int blocks = (S->n + OBS_RESID_RUN - 1) / OBS_RESID_RUN;
-    if (blocks > OBS_RESID_WAVES) blocks = OBS_RESID_WAVES;
-    rg_launch(k_obs_resid, dim3(blocks), dim3(WAVE), 0, st, ev0, ev1, *S, *c, out);
+    rg_launch(k_obs_resid, dim3(rgk_obs_resid_blocks(S->n)), dim3(WAVE), 0, st, ev0, ev1, *S, *c, out);
 }
 void rgk_encode(const uint8_t *screen, const uint8_t *hist, const int32_t *status, uint32_t *flags, uint32_t *err_any, int n, int hw, size_t rs, size_t rst,
                 int symbols, int planes_sym, uint32_t sflag, int with_hist, int kind, float *out, const int32_t *ext, hipStream_t st) {
