@@ -142,6 +142,20 @@ print("HipVecRogueEnv(scout=True): reward + scout %.0f over 200 explorer steps; 
       % (total.item(), len(ep["env"]), (ep["cause"] == 1).sum(), (ep["cause"] == 2).sum(), ep["ret"].mean(), ep["length"].mean(), ep["scout"].mean()))
 venv.close()
 
+# 3i'. count-based novelty on the device: a hash of what each env shows and how often it has shown it -- in its running episode (visit_count) and over every
+#      env and episode (visit_count_global).  The bonus is one tensor op of the learner's: 1 / sqrt(count), or NovelD's / BeBold's `first visit` gate -----------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], max_steps=100, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0,
+                      novelty="screen", novelty_scope="both", novelty_slots=256, novelty_global_slots=1 << 21, guide="explore")
+bonus = gate = 0.0
+for t in range(200):
+    venv.step_keys(venv.guide_keys)
+    bonus = bonus + venv.visit_count_global.float().rsqrt().sum()   # a lifetime count bonus
+    gate = gate + (venv.visit_count == 1).sum()                      # the episodic first-visit gate
+st = venv.novelty_stats()
+print("HipVecRogueEnv(novelty='screen'): %.0f of %d explorer steps showed a screen for the first time in their episode; count bonus %.0f; %d distinct states, %d visits dropped"
+      % (float(gate), 200 * 4096, float(bonus), st["occupied_global"], st["dropped_global"] + st["dropped_episode"]))
+venv.close()
+
 # 3j. the monsters as an entity table and four threat words, kept beside `obs`: what is next to me, where, which letter -- without parsing the image ----------
 ENEMIES = dict(MINI, enemies={"enemies": list(range(12))})
 venv = HipVecRogueEnv([dict(ENEMIES, seed=i) for i in range(4096)], max_steps=100, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0,

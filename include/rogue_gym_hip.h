@@ -414,6 +414,59 @@ int rg_episode_arrays(rg_t *h, rg_episode_arrays_t *out);
 int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint64_t *dropped);
 int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out);
 
+/* COUNT-BASED NOVELTY: a hash of what each env shows and visit counts of the hashed states, kept on the device beside the stepper -- the episodic count of
+ * RIDE, the `count == 1` gate of NovelD / BeBold, #Exploration's lifetime count.  A pass of its own behind the step: a handle that does not enable it
+ * launches and allocates nothing more.  The bonus itself (rsqrt of the count, the gate) is one tensor op of the learner's.  The rule -- key bytes, hash,
+ * tables -- is stated once in csrc/rg_novelty.h.
+ *   what: RG_NOV_POS hashes the player's cell (x, y as u16 LE, four zero bytes), RG_NOV_SCREEN rows 1 .. H-2 of the screen mirror as rg_screen returns it,
+ *     RG_NOV_CROP the (2 radius_y + 1) x (2 radius_x + 1) window of those rows around the player (rg_obs_crop's window; cells outside the rows or the columns
+ *     are ' ').  The dungeon level of the status mirror, `what` and the key length are hashed in; the hash is never 0.
+ *   scope: RG_NOV_EPISODE -- a table of `cap` slots per env (a power of two, 64 .. 65 536; 16 bytes each) that an episode end empties by raising the env's
+ *     generation: count[e] is how often env e has shown this state in its running episode, this visit included.  RG_NOV_GLOBAL -- one table of `gcap` slots
+ *     (a power of two, 1 024 .. 2^28) for the handle, shared by all envs and emptied by rg_novelty_clear only: gcount[e] is the state's count after EVERY
+ *     env's visit of the call has been added, so below capacity it does not depend on scheduling.  A visit that finds its table full (cap probes, or
+ *     min(gcap, 1 024) probes of the global table -- about 98 % occupied for a large one -- without a match or an empty slot) is DROPPED: its count is 0
+ *     and dropped_episode / dropped_global goes up.  Nothing waits for another lane.  A full global table makes every new state cost those 1 024 probes:
+ *     size gcap by the distinct states expected (N x a few hundred for RG_NOV_SCREEN on procedurally generated levels), read rg_novelty_stats.
+ *   rg_novelty_enable allocates (16 B x cap x N and 16 B x gcap), then counts every env's present state as a first visit.  Refused with a message that names
+ *     the argument, nothing allocated: a handle created without auto-reset, a handle with config groups, a second enable, an unknown what or scope, radii
+ *     outside rg_obs_crop's range with RG_NOV_CROP or non-zero otherwise, a cap or gcap that is not a power of two in range (the cap of a scope that is off
+ *     is not looked at).
+ *   rg_novelty_update, once after a step, for the envs that step played (all, or the first n_keys of rg_step_prefix): done[e] != 0 raises the env's
+ *     generation first; then the state now standing in the lane is hashed and counted in each enabled table.
+ *   rg_novelty_cut, after rg_reset, rg_reset_envs, rg_reset_mask or rg_state_load (the tables are not part of a state record), for the listed envs: the
+ *     generation is raised, then the present state is counted.  env_ids / k / ids_on_device / mask_dev and their refusals as rg_episode_cut.
+ *   rg_novelty_arrays: device pointers valid until rg_destroy -- hash u64 [N], count i32 [N] (NULL without RG_NOV_EPISODE), gcount i32 [N] (NULL without
+ *     RG_NOV_GLOBAL).  Every array has 64 envs of slack behind env N-1 that no launch writes.
+ *   rg_novelty_stats (waits for the stream): out[0] occupied_global, the slots of the global table in use; [1] dropped_global; [2] dropped_episode;
+ *     [3] calls, the update and cut calls since the enable or the last clear.
+ *   rg_novelty_table_read (waits for the stream): the occupied global slots, sorted by hash, into hashes_host / counts_host of `cap` entries each; *n = their
+ *     number.  With hashes_host and counts_host NULL only *n is stored; a cap below *n is refused.  A learner's visitation histogram; the sum of the counts
+ *     plus dropped_global is the number of visits offered.
+ *   rg_novelty_clear empties the global table and zeroes the four counters.  The episodic tables stay.
+ *   rg_novelty_hash_host (stateless, needs no device): the rule on ONE screen u8 [height][width] with the player at (px, py) on dungeon level `level`.
+ *     Refused, the message read through rg_last_error(NULL): screen or hash NULL, sizes out of range, the player outside the grid, an unknown what, radii as
+ *     above.  rg_novelty_finish_host is the hash's last step alone, mix(acc + mix(salt)) with 0 -> 1.  rg_novelty_insert_host is the episodic insert on a
+ *     host table: slots = `cap` slots of {u64 hash, u32 gen, u32 count}, 16-byte aligned; *count = the visit's count, 0 = dropped.
+ * Enable, update and cut are asynchronous on the handle's stream.  They read mirrors and game state as the step left them and flush the pending render first,
+ * exactly as rg_screen does: behind an observation call the mirrors are drawn already. */
+#define RG_NOV_POS    1
+#define RG_NOV_SCREEN 2
+#define RG_NOV_CROP   3
+#define RG_NOV_EPISODE 1u
+#define RG_NOV_GLOBAL  2u
+typedef struct rg_novelty_arrays_t { uint64_t *hash; int32_t *count; int32_t *gcount; } rg_novelty_arrays_t;
+int rg_novelty_enable(rg_t *h, int what, uint32_t scope, int radius_y, int radius_x, int cap, int gcap);
+int rg_novelty_update(rg_t *h);
+int rg_novelty_cut(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, const uint8_t *mask_dev);
+int rg_novelty_arrays(rg_t *h, rg_novelty_arrays_t *out);
+int rg_novelty_stats(rg_t *h, uint64_t *out);
+int rg_novelty_table_read(rg_t *h, uint64_t *hashes_host, uint32_t *counts_host, int cap, int *n);
+int rg_novelty_clear(rg_t *h);
+int rg_novelty_hash_host(int what, int level, int height, int width, const uint8_t *screen, int px, int py, int radius_y, int radius_x, uint64_t *hash);
+uint64_t rg_novelty_finish_host(uint64_t acc, uint64_t salt);
+int rg_novelty_insert_host(void *slots, int cap, uint32_t gen, uint64_t hash, uint32_t *count);
+
 /* MONSTER TABLES AND THREAT WORDS: the nearest monsters of every env as an entity list, and four words that say how close they are.  The monster tables are
  * device-resident and bit-exact with the reference; this is one small pass behind the step that hands them out in a form a policy, a shaping term or a
  * teacher can use, without parsing the image.  The rule is stated once in csrc/rg_monsters.h.

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds librogue_gym_hip.so for gfx950 in-tree (cross-compiles without a GPU).  The translation units and their -O levels: units.sh.
+# Builds librogue_gym_hip.so and librogue_gym_novelty.so for gfx950 in-tree (cross-compiles without a GPU).  The translation units and their -O levels: units.sh.
 set -e
 cd "$(dirname "$0")"
 . ./units.sh
@@ -13,5 +13,12 @@ for u in $UNITS; do
     hipcc $F ${u##*:} -c $src -o $obj
     OBJS="$OBJS $obj"
 done
-hipcc --offload-arch=gfx950 -shared $OBJS -o "$OUT"
+NOBJS=
+for u in $NOVELTY_UNITS; do
+    src=${u%%:*}; obj=../build/${src%.*}.o
+    hipcc $F ${u##*:} -c $src -o $obj
+    NOBJS="$NOBJS $obj"
+done
+hipcc --offload-arch=gfx950 -shared $NOBJS -o ../librogue_gym_novelty.so
+hipcc --offload-arch=gfx950 -shared $OBJS -L.. -lrogue_gym_novelty '-Wl,-rpath,$ORIGIN' -o "$OUT"
 echo "built $OUT"

@@ -67,6 +67,7 @@ void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fal
                hipStream_t st);
 void rgk_episode(const RgState *S, const RgConfig *c, const RgEpisode *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, int record, uint32_t serial,
                  hipStream_t st);
+void rgk_novelty(const RgState *S, const RgConfig *c, const RgNovelty *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, hipStream_t st);
 void rgk_monsters(const RgState *S, const RgConfig *c, uint32_t mode, int cap, int16_t *table, int32_t *threat, hipStream_t st);
 void rgk_objects(const RgState *S, const RgConfig *c, uint32_t kinds, uint32_t mode, int cap, int16_t *table, int32_t *count, hipStream_t st);
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
@@ -162,6 +163,11 @@ struct rg_handle {
     RgEpisode ep = {};
     uint32_t ep_serial = 0;                            // update / cut calls since the enable
     int32_t *ep_ids = nullptr;                         // [n] a cut's host-side env ids, uploaded
+    // count-based novelty (rg_novelty_*; rg_novelty.h): off until rg_novelty_enable, which allocates the arrays and the tables
+    bool nov_on = false;
+    RgNovelty nov = {};
+    uint64_t nov_calls = 0;                            // update / cut calls since the enable or the last clear
+    int32_t *nov_ids = nullptr;                        // [n] a cut's host-side env ids, uploaded
     // the tileset of the pixel passes (rg_tileset_set; rg_pixels.h): the font, then the ink table; allocated at the first call.  Config groups read the parent's
     uint8_t *tiles = nullptr; int tile_th = 0;
 };
@@ -1204,6 +1210,138 @@ int rg_episode_log_read(rg_t *h, rg_episode_rec *out_host, int cap, int *n, uint
 int rg_scout_host(const uint16_t *cells, int height, int width, uint8_t *seen_inout, int32_t *fresh_out) {
     return rgh_scout(g_create_err, cells, height, width, seen_inout, fresh_out);
 }
+// ---- count-based novelty (rg_novelty.h; k_nov_* in rg_novelty.hip) ----
+int rg_novelty_enable(rg_t *h, int what, uint32_t scope, int radius_y, int radius_x, int cap, int gcap) {
+    const std::string w = "rg_novelty_enable: ";
+    if (!h->sub.empty()) { h->err = w + "not for a handle with config groups (one handle per config)"; return 1; }
+    if (!h->cfg.auto_reset) { h->err = w + "the handle was created without auto-reset: its episodes do not end inside rg_step"; return 1; }
+    if (h->nov_on) { h->err = w + "novelty is enabled already"; return 1; }
+    if (nov_key_check(h->err, w, what, radius_y, radius_x)) return 1;
+    if (scope == 0 || (scope & ~(RG_NOV_EPISODE | RG_NOV_GLOBAL))) { h->err = w + "scope must be RG_NOV_EPISODE (1), RG_NOV_GLOBAL (2) or both (3), got " + std::to_string(scope); return 1; }
+    if ((scope & RG_NOV_EPISODE) && !rg_nov_pow2_in(cap, RG_NOV_CAP_MIN, RG_NOV_CAP_MAX)) {
+        h->err = w + "cap must be a power of two, " + std::to_string(RG_NOV_CAP_MIN) + " <= cap <= " + std::to_string(RG_NOV_CAP_MAX) + ", got " + std::to_string(cap);
+        return 1;
+    }
+    if ((scope & RG_NOV_GLOBAL) && !rg_nov_pow2_in(gcap, RG_NOV_GCAP_MIN, RG_NOV_GCAP_MAX)) {
+        h->err = w + "gcap must be a power of two, " + std::to_string(RG_NOV_GCAP_MIN) + " <= gcap <= " + std::to_string(RG_NOV_GCAP_MAX) + ", got " + std::to_string(gcap);
+        return 1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->S.n, m = n + RG_NOV_SLACK, had = h->allocs.size();
+    RgNovelty A = {};
+    A.what = what; A.ry = radius_y; A.rx = radius_x;
+    bool ok = dev_alloc(h, &A.hash, m) && dev_alloc(h, &A.gen, n) && dev_alloc(h, &A.stat, 4) && dev_alloc(h, &h->nov_ids, n);
+    if (ok && (scope & RG_NOV_EPISODE)) { A.cap = cap; ok = dev_alloc(h, &A.count, m) && dev_alloc(h, &A.tab, n * (size_t)cap); }
+    if (ok && (scope & RG_NOV_GLOBAL)) { A.gcap = gcap; ok = dev_alloc(h, &A.gcount, m) && dev_alloc(h, &A.gslot, n) && dev_alloc(h, &A.gtab, (size_t)gcap); }
+    if (!ok) {  // (a table that does not fit: what this call allocated goes back, the handle is as before)
+        while (h->allocs.size() > had) { (void)hipFree(h->allocs.back()); h->allocs.pop_back(); }
+        h->nov_ids = nullptr;
+        h->err = w + h->err;
+        return 1;
+    }
+    h->nov = A;
+    h->nov_on = true;
+    h->nov_calls = 0;
+    // (the allocations were zeroed on the null stream, which the handle's stream may not wait for)
+    HIPCHK(h, hipDeviceSynchronize());
+    if (flush_render(h)) return 1;
+    rgk_novelty(&h->S, &h->cfg, &h->nov, h->S.n, nullptr, nullptr, 1, h->stream);  // every env: generation 1, its present state a first visit
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+static int novelty_on(rg_handle *h, const char *what) {
+    if (!h->nov_on) { h->err = std::string(what) + ": novelty is not enabled (rg_novelty_enable)"; return 1; }
+    return 0;
+}
+int rg_novelty_update(rg_t *h) {
+    if (novelty_on(h, "rg_novelty_update")) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (flush_render(h)) return 1;
+    rgk_novelty(&h->S, &h->cfg, &h->nov, h->S.n_keys, nullptr, nullptr, 0, h->stream);  // the envs the last step played
+    HIPCHK(h, hipGetLastError());
+    h->nov_calls++;
+    return 0;
+}
+int rg_novelty_cut(rg_t *h, const int32_t *env_ids, int k, int ids_on_device, const uint8_t *mask_dev) {
+    if (novelty_on(h, "rg_novelty_cut")) return 1;
+    if (env_ids && mask_dev) { h->err = "rg_novelty_cut: both env_ids and mask_dev are given: a list or a mask, not both"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t *ids = nullptr;
+    int slots = h->S.n;
+    if (env_ids) {
+        if (k < 0 || k > h->S.n) { h->err = "rg_novelty_cut: k = " + std::to_string(k) + " env_ids for " + std::to_string(h->S.n) + " envs"; return 1; }
+        if (!ids_on_device) {  // checked before anything is launched (two lanes on one table would race)
+            std::vector<uint8_t> seen((size_t)h->S.n, 0);
+            for (int i = 0; i < k; i++) {
+                const int32_t e = env_ids[i];
+                if (e < 0 || e >= h->S.n) { h->err = "rg_novelty_cut: env_ids[" + std::to_string(i) + "] = " + std::to_string(e) + " out of range [0, " + std::to_string(h->S.n) + ")"; return 1; }
+                if (seen[e]) { h->err = "rg_novelty_cut: env_ids holds " + std::to_string(e) + " twice"; return 1; }
+                seen[e] = 1;
+            }
+            if (k) HIPCHK(h, hipMemcpyAsync(h->nov_ids, env_ids, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));  // (pageable source: staged before the call returns)
+            ids = h->nov_ids;
+        } else ids = env_ids;
+        slots = k;
+    }
+    if (flush_render(h)) return 1;
+    rgk_novelty(&h->S, &h->cfg, &h->nov, slots, ids, mask_dev, 1, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->nov_calls++;
+    return 0;
+}
+int rg_novelty_arrays(rg_t *h, rg_novelty_arrays_t *out) {
+    if (novelty_on(h, "rg_novelty_arrays")) return 1;
+    if (!out) { h->err = "rg_novelty_arrays: out is NULL"; return 1; }
+    *out = rg_novelty_arrays_t{h->nov.hash, h->nov.count, h->nov.gcount};
+    return 0;
+}
+int rg_novelty_stats(rg_t *h, uint64_t *out) {
+    if (novelty_on(h, "rg_novelty_stats")) return 1;
+    if (!out) { h->err = "rg_novelty_stats: out is NULL"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(st, h->nov.stat, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out[0] = st[0]; out[1] = st[1]; out[2] = st[2]; out[3] = h->nov_calls;
+    return 0;
+}
+int rg_novelty_table_read(rg_t *h, uint64_t *hashes_host, uint32_t *counts_host, int cap, int *n) {
+    if (novelty_on(h, "rg_novelty_table_read")) return 1;
+    if (!n) { h->err = "rg_novelty_table_read: n is NULL"; return 1; }
+    *n = 0;
+    if (!h->nov.gtab) return 0;  // no global table: nothing to read
+    if ((hashes_host == nullptr) != (counts_host == nullptr)) { h->err = "rg_novelty_table_read: hashes_host and counts_host go together"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<std::pair<uint64_t, uint32_t>> rows;
+    const size_t piece = (size_t)1 << 20;  // slots per copy: 16 MB of host memory at a time, whatever gcap is
+    std::vector<RgNovSlot> buf(std::min(piece, (size_t)h->nov.gcap));
+    for (size_t at = 0; at < (size_t)h->nov.gcap; at += piece) {
+        const size_t cnt = std::min(piece, (size_t)h->nov.gcap - at);
+        HIPCHK(h, hipMemcpy(buf.data(), h->nov.gtab + at, cnt * sizeof(RgNovSlot), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cnt; i++)
+            if (buf[i].hash) rows.emplace_back(buf[i].hash, buf[i].count);
+    }
+    *n = (int)rows.size();
+    if (!hashes_host) return 0;
+    if (cap < (int)rows.size()) { h->err = "rg_novelty_table_read: cap = " + std::to_string(cap) + " entries for " + std::to_string(rows.size()) + " occupied slots"; return 1; }
+    std::sort(rows.begin(), rows.end());
+    for (size_t i = 0; i < rows.size(); i++) { hashes_host[i] = rows[i].first; counts_host[i] = rows[i].second; }
+    return 0;
+}
+int rg_novelty_clear(rg_t *h) {
+    if (novelty_on(h, "rg_novelty_clear")) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->nov.gtab) HIPCHK(h, hipMemsetAsync(h->nov.gtab, 0, (size_t)h->nov.gcap * sizeof(RgNovSlot), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->nov.stat, 0, 4 * sizeof(unsigned long long), h->stream));
+    h->nov_calls = 0;
+    return 0;
+}
+int rg_novelty_hash_host(int what, int level, int height, int width, const uint8_t *screen, int px, int py, int radius_y, int radius_x, uint64_t *hash) {
+    return rgh_nov_hash(g_create_err, what, level, height, width, screen, px, py, radius_y, radius_x, hash);
+}
+uint64_t rg_novelty_finish_host(uint64_t acc, uint64_t salt) { return rg_nov_finish(acc, salt); }
+int rg_novelty_insert_host(void *slots, int cap, uint32_t gen, uint64_t hash, uint32_t *count) { return rgh_nov_insert(g_create_err, slots, cap, gen, hash, count); }
 int rg_obs_gray(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 0, out_dev); }
 int rg_obs_symbol(rg_t *h, uint32_t status_flag, int with_hist, float *out_dev) { return obs_common(h, status_flag, with_hist, 1, out_dev); }
 

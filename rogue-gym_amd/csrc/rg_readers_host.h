@@ -1,6 +1,6 @@
 // rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api.cpp) share with the *_host twins, and the
-// twins themselves (rgh_*; rg_action_mask_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host and rg_scout_host are one-line delegations in
-// rg_api.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
+// twins themselves (rgh_*; rg_action_mask_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
+// rg_novelty_insert_host are one-line delegations in rg_api.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
 // (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
 #pragma once
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "rg_objects.h"
 #include "rg_monsters.h"
 #include "rg_episode.h"
+#include "rg_novelty.h"
 
 // ---- the argument checks: `what` is the entry's name ----
 static inline int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
@@ -300,5 +301,48 @@ static inline int rgh_scout(std::string &err, const uint16_t *cells, int height,
         seen_inout[j] = (uint8_t)(s & rg_ep_row_bits(j, hw, width));  // (bits that can never count are written 0, whatever the caller passed)
     }
     if (fresh_out) *fresh_out = fresh;
+    return 0;
+}
+// ---- count-based novelty (rg_novelty.h) ----
+// what the enable and the hash twin ask of `what` and the radii; `w` = the entry's name and a colon
+static inline int nov_key_check(std::string &err, const std::string &w, int what, int radius_y, int radius_x) {
+    if (what != RG_NOV_POS && what != RG_NOV_SCREEN && what != RG_NOV_CROP) {
+        err = w + "what must be RG_NOV_POS (1), RG_NOV_SCREEN (2) or RG_NOV_CROP (3), got " + std::to_string(what);
+        return 1;
+    }
+    if (what == RG_NOV_CROP ? (radius_y < 0 || radius_y > RG_MAX_H - 1 || radius_x < 0 || radius_x > RG_MAX_W - 1) : (radius_y != 0 || radius_x != 0)) {
+        err = w + (what == RG_NOV_CROP ? "radius_y, radius_x must satisfy 0 <= radius_y <= " + std::to_string(RG_MAX_H - 1) + " and 0 <= radius_x <= " + std::to_string(RG_MAX_W - 1)
+                                       : std::string("radius_y, radius_x must be 0 unless what is RG_NOV_CROP")) +
+              ", got (" + std::to_string(radius_y) + ", " + std::to_string(radius_x) + ")";
+        return 1;
+    }
+    return 0;
+}
+// the hash of one screen: the words one after the other
+static inline int rgh_nov_hash(std::string &err, int what, int level, int height, int width, const uint8_t *screen, int px, int py, int radius_y, int radius_x, uint64_t *hash) {
+    const std::string w = "rg_novelty_hash_host: ";
+    if (!screen) { err = w + "screen must not be NULL"; return 1; }
+    if (!hash) { err = w + "hash must not be NULL"; return 1; }
+    if (height < 3 || width < 1 || height > RG_MAX_H || width > RG_MAX_W) {
+        err = w + "height, width must satisfy 3 <= height <= " + std::to_string(RG_MAX_H) + " and 1 <= width <= " + std::to_string(RG_MAX_W) + ", got (" + std::to_string(height) + ", " +
+              std::to_string(width) + ")";
+        return 1;
+    }
+    if (level < 0) { err = w + "level must not be negative, got " + std::to_string(level); return 1; }
+    if (nov_key_check(err, w, what, radius_y, radius_x) || player_check(err, "rg_novelty_hash_host", px, py, height, width)) return 1;
+    const uint32_t L = rg_nov_key_len(what, height, width, radius_y, radius_x), m = (L + 7) / 8;
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i < m; i++)
+        acc += rg_nov_term(what == RG_NOV_POS ? rg_nov_pos_word(px, py) : rg_nov_key_word(what, screen, height, width, px, py, radius_y, radius_x, L, i), i);
+    *hash = rg_nov_finish(acc, rg_nov_salt((uint32_t)what, level, L));
+    return 0;
+}
+// the episodic insert on a table in host memory
+static inline int rgh_nov_insert(std::string &err, void *slots, int cap, uint32_t gen, uint64_t hash, uint32_t *count) {
+    const std::string w = "rg_novelty_insert_host: ";
+    if (!slots || ((uintptr_t)slots & 15)) { err = w + "slots must be a non-null, 16-byte aligned pointer"; return 1; }
+    if (!count) { err = w + "count must not be NULL"; return 1; }
+    if (!rg_nov_pow2_in(cap, 1, RG_NOV_CAP_MAX)) { err = w + "cap must be a power of two, 1 <= cap <= " + std::to_string(RG_NOV_CAP_MAX) + ", got " + std::to_string(cap); return 1; }
+    *count = rg_nov_insert(static_cast<RgNovSlot *>(slots), (uint32_t)cap, gen, hash);
     return 0;
 }

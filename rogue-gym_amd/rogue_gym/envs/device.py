@@ -47,7 +47,8 @@ class HipVecRogueEnv:
                  persistent_obs: bool = False, crop=None, obs_dtype=None, symbol_ids: bool = False, action_mask: bool = False, guide=None, guide_secrets: bool = False,
                  episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4,
                  objects=None, object_kinds: str = "stairs+gold+door", object_cap: int = 8, object_secrets: bool = False,
-                 pixels=None, pixel_crop=None, tileset=None):
+                 pixels=None, pixel_crop=None, tileset=None,
+                 novelty=None, novelty_scope: str = "episode", novelty_crop=None, novelty_slots: int = 1024, novelty_global_slots: int = 1 << 22):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -122,7 +123,19 @@ class HipVecRogueEnv:
         window of 8 x 8 tiles is 88 x 88 pixels, 7.7 KB per env in gray, the form to train on; the whole-screen RGB image of an 80 x 24 env is 368 KB.
         With a crop it works on every env this class builds; the whole screen not on batches with config groups or mixed sizes.  Rewritten in place by
         everything that refreshes `obs`: one launch more per step, no host trip.  A learner does `.float() / 255` itself.  None: both attributes are None
-        and nothing is added to any call.  render_pixels() and frame() work either way."""
+        and nothing is added to any call.  render_pixels() and frame() work either way.
+
+        novelty (None, "pos", "screen" or "crop"): count-based novelty on the device (rg_novelty_update, a small pass behind every step, no host trip) -- visit
+        counts of hashed states, the signal of RIDE's episodic count, of the `count == 1` gate of NovelD / BeBold and of lifetime count bonuses.  What is
+        hashed: "pos" the player's cell, "screen" the rows of the screen that show tiles, "crop" their player-centred window of novelty_crop = r or (ry, rx);
+        the dungeon level is hashed in.  `novelty_hash` int64 [N] is the hash (the u64 bit pattern), kept current with `obs`.  novelty_scope "episode":
+        `visit_count` int32 [N], how often the env has shown this state in its running episode, this step included, from a table of novelty_slots slots per
+        env (a power of two, 64 .. 65 536; 16 B x slots x N of device memory -- 1 GB at 1 024 slots and 65 536 envs); "global": `visit_count_global` int32 [N],
+        the count over every env and episode of this object since it was built or novelty_clear() was called, from one table of novelty_global_slots
+        slots (a power of two, 1 024 .. 2^28), as it stands after the whole step; "both": both.  A visit that finds its table full counts 0 and is
+        reported by novelty_stats().  step*, reset, reset_envs, load_state and clone_state keep all three current.  The bonus is one tensor op of the
+        learner's: visit_count.float().rsqrt(), or visit_count == 1.  None: the three attributes are None and nothing is added to any call.  Not for
+        batches with config groups."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -221,10 +234,73 @@ class HipVecRogueEnv:
                 with torch.cuda.device(self.device):
                     self.pixel_center = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
         self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
+        self._novelty_check(novelty, novelty_scope, novelty_crop, novelty_slots, novelty_global_slots)
         self.persistent_obs = bool(persistent_obs)
         if self.persistent_obs:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         self._encode()
+        self._novelty_setup()  # (behind the first encode: the mirrors are drawn)
+
+    def _novelty_check(self, what, scope, crop, slots, gslots):
+        """The arguments of rg_novelty_enable from the constructor's; the enable itself follows the first encode."""
+        self.novelty, self.novelty_hash, self.visit_count, self.visit_count_global = what, None, None, None
+        self._nov_args = None
+        if what is None:
+            if crop is not None:
+                raise ValueError("novelty_crop needs novelty='crop'")
+            return
+        if not isinstance(what, str) or what not in inner.NOVELTY_WHAT:
+            raise ValueError("novelty must be None, 'pos', 'screen' or 'crop', got %r" % (what,))
+        if not isinstance(scope, str) or scope not in inner.NOVELTY_SCOPE:
+            raise ValueError("novelty_scope must be 'episode', 'global' or 'both', got %r" % (scope,))
+        if (what == "crop") != (crop is not None):
+            raise ValueError("novelty_crop goes with novelty='crop' and only with it, got novelty=%r, novelty_crop=%r" % (what, crop))
+        ry, rx = (0, 0) if crop is None else self._crop_radii(crop)
+        self._nov_args = (inner.NOVELTY_WHAT[what], inner.NOVELTY_SCOPE[scope], ry, rx, operator.index(slots), operator.index(gslots))
+
+    def _novelty_setup(self):
+        if self._nov_args is None:
+            return
+        torch = self.torch
+        L, h, n = self._h.L, self._h.h, self.num_envs
+        self._h.check(L.rg_novelty_enable(h, *self._nov_args))
+        a = inner.RgNoveltyArrays()
+        self._h.check(L.rg_novelty_arrays(h, C.byref(a)))
+        with torch.cuda.device(self.device):
+            def view(ptr, typestr):
+                return None if not ptr else torch.as_tensor(_DevArray(ptr, (n,), typestr), device=self.device)
+            self.novelty_hash, self.visit_count, self.visit_count_global = view(a.hash, "<i8"), view(a.count, "<i4"), view(a.gcount, "<i4")
+
+    def _novelty_cut(self, ptr=None, k=0, on_dev=0, mask=None):
+        """The envs a reset or a load replaced (a list, a mask, or every env) start a new episode and count the state they show now."""
+        if self._nov_args is not None:
+            self._h.check(self._h.L.rg_novelty_cut(self._h.h, ptr, k, on_dev, None if mask is None else C.c_void_p(mask.data_ptr())))
+
+    def novelty_stats(self):
+        """dict of occupied_global (slots of the global table in use), dropped_global, dropped_episode (visits that found their table full) and calls.  It
+        waits for the stream.  Needs novelty."""
+        if self._nov_args is None:
+            raise ValueError("novelty_stats needs novelty")
+        out = (C.c_uint64 * 4)()
+        self._h.check(self._h.L.rg_novelty_stats(self._h.h, out))
+        return dict(zip(inner.NOVELTY_STATS, (int(v) for v in out)))
+
+    def novelty_table(self):
+        """(hashes numpy uint64 [K], counts numpy uint32 [K]): the occupied slots of the global table sorted by hash -- a visitation histogram.  It waits for
+        the stream.  Needs novelty with scope 'global' or 'both'."""
+        if self._nov_args is None or not self._nov_args[1] & inner.RG_NOV_GLOBAL:
+            raise ValueError("novelty_table needs novelty with novelty_scope 'global' or 'both'")
+        L, h, n = self._h.L, self._h.h, C.c_int(0)
+        self._h.check(L.rg_novelty_table_read(h, None, None, 0, C.byref(n)))
+        hashes, counts = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint32)
+        self._h.check(L.rg_novelty_table_read(h, hashes.ctypes.data, counts.ctypes.data, hashes.size, C.byref(n)))
+        return hashes[:n.value], counts[:n.value]
+
+    def novelty_clear(self):
+        """Empty the global table and zero the counters of novelty_stats(); the episodic tables stay.  Needs novelty."""
+        if self._nov_args is None:
+            raise ValueError("novelty_clear needs novelty")
+        self._h.check(self._h.L.rg_novelty_clear(self._h.h))
 
     _EP_NAMES = ("ep_return", "ep_length", "ep_depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen_bits")
 
@@ -561,7 +637,9 @@ class HipVecRogueEnv:
         self._h.check(self._h.L.rg_reset(self._h.h))
         if self._episodes:  # the running episodes end here, cause 3
             self._h.check(self._h.L.rg_episode_cut(self._h.h, None, 0, 0, None, 1))
-        return self._encode()
+        obs = self._encode()
+        self._novelty_cut()
+        return obs
 
     def reset_envs(self, env_ids=None, mask=None, seeds=None):
         """Rebuild the chosen envs as reset() rebuilds every env (rg_reset_envs / rg_reset_mask) and return the observation batch, re-encoded; every
@@ -582,7 +660,9 @@ class HipVecRogueEnv:
             self._h.check(L.rg_reset_mask(h, C.c_void_p(mask.data_ptr())))  # (a bool tensor is one byte per element, 0 / 1)
             if self._episodes:
                 self._h.check(L.rg_episode_cut(h, None, 0, 0, C.c_void_p(mask.data_ptr()), 1))
-            return self._encode()
+            obs = self._encode()
+            self._novelty_cut(mask=mask)
+            return obs
         ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
         if on_dev and torch.unique(_keep).numel() != k:
             raise ValueError("reset_envs: duplicate env_ids")
@@ -601,7 +681,10 @@ class HipVecRogueEnv:
         self._h.check(L.rg_reset_envs(h, ptr, k, on_dev))
         if self._episodes and k:
             self._h.check(L.rg_episode_cut(h, ptr, k, on_dev, None, 1))
-        return self._encode()
+        obs = self._encode()
+        if k:
+            self._novelty_cut(ptr, k, on_dev)
+        return obs
 
     def seed(self, seeds):
         seeds = [int(s) for s in seeds]
@@ -634,6 +717,8 @@ class HipVecRogueEnv:
             obs = self.obs
         if self._episodes:  # the accounting of this step, on the mirrors and cells as it left them
             self._h.check(self._h.L.rg_episode_update(self._h.h))
+        if self._nov_args is not None:  # the visit of the state this step left, behind the observation: the mirrors are drawn
+            self._h.check(self._h.L.rg_novelty_update(self._h.h))
         return obs, self.reward, self.done
 
     def step(self, actions):
@@ -832,7 +917,10 @@ class HipVecRogueEnv:
             raise ValueError("load_state: %d records for %d envs" % (records.shape[0], k))
         if k:
             self._h.check(self._h.L.rg_state_load(self._h.h, C.c_void_p(records.data_ptr()), int(records.shape[1]), ptr, k, on_dev))
-        return self._encode()
+        obs = self._encode()
+        if k:  # (the visit tables are not part of a record: the loaded envs start a new episode of counts)
+            self._novelty_cut(ptr, k, on_dev)
+        return obs
 
     def clone_state(self, src_ids, dst_ids):
         """Copy the states of src_ids into dst_ids (through a scratch record batch, so overlapping id sets are well defined): e.g. one

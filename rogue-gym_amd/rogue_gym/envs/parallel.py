@@ -12,7 +12,7 @@ from typing import Dict, Iterable, List, Tuple, Union
 
 import numpy as np
 
-from rogue_gym_python._rogue_gym import ParallelGameState, StateBatch, Tileset
+from rogue_gym_python._rogue_gym import ParallelGameState, StateBatch, Tileset, VisitCounter
 
 from ._gym_compat import Discrete
 from .rogue_env import ImageSetting, RogueEnv
@@ -36,6 +36,7 @@ class ParallelRogueEnv:
         self.observation_space = image_setting.detect_space(height, width, self.game.symbols())
         self.states: StateBatch = self.game.states()
         self._infos = [{}] * self.num_workers
+        self._visits, self._visit_key = None, None
 
     def get_key_to_action(self) -> Dict[str, str]:
         return self.ACTION_MEANINGS
@@ -62,6 +63,8 @@ class ParallelRogueEnv:
         m = min(len(before), len(after))
         gained = np.maximum(after.gold[:m].astype(np.int64) - before.gold[:m].astype(np.int64), 0)
         self.states = after
+        if self._visits is not None and m == len(after):  # (a stepped prefix leaves the counts where they are)
+            self._visits.visit(after.screen, after.dungeon_level, after.is_terminal)
         return after, gained.tolist(), after.is_terminal.tolist(), self._infos
 
     def images(self, states: StateBatch = None) -> np.ndarray:
@@ -96,8 +99,22 @@ class ParallelRogueEnv:
         """(table int16 [N, cap, 8], count int32 [N, 4]): RogueEnv.objects for the whole batch; without known=True it is privileged."""
         return self.game.object_tables(kinds, known, secrets, cap)
 
+    def visit_counts(self, what: str = "screen", crop=None) -> np.ndarray:
+        """int32 [N]: RogueEnv.visit_count for the whole batch -- how often each env's running episode has shown the state it is in now.  The first call
+        starts the counting (the present states are first visits); from then on every step() counts, an env whose step ended its episode starts a new
+        one with the state of its new game, and reset() starts all anew.  Not for batches that mix screen sizes.  On device tensors:
+        HipVecRogueEnv(novelty=...)."""
+        if self._visits is None or self._visit_key != (what, crop):
+            if isinstance(self.states.screen, list):
+                raise ValueError("visit_counts: the envs of this batch differ in screen size")
+            self._visits, self._visit_key = VisitCounter(self.num_workers, what, crop), (what, crop)
+            self._visits.visit(self.states.screen, self.states.dungeon_level, True)
+        return self._visits.counts.copy()
+
     def reset(self) -> StateBatch:
         batch = self.states = self.game.reset()
+        if self._visits is not None:
+            self._visits.visit(batch.screen, batch.dungeon_level, True)
         return batch
 
     def seed(self, seeds: List[int]) -> None:

@@ -13,7 +13,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from rogue_gym_python import _rogue_gym as rogue_gym_inner
-from rogue_gym_python._rogue_gym import GameState, PlayerState, StateBatch
+from rogue_gym_python._rogue_gym import GameState, PlayerState, StateBatch, VisitCounter
 
 from ._gym_compat import Box, Discrete, Env
 
@@ -186,6 +186,7 @@ class RogueEnv(Env):
         for key in self._keys_of(action):
             self.game.react(ord(key))
         state = self.result = self.game.prev()
+        self._visit(False)
         return state, state.gold - purse, state.is_terminal, {}
 
     def save_state(self) -> bytes:
@@ -198,6 +199,7 @@ class RogueEnv(Env):
         what they were.  The seed stays this env's: the next reset builds from it."""
         self.game.load_state(state)
         state = self.result = self.game.prev()
+        self._visit(True)
         return state
 
     def action_mask(self) -> np.ndarray:
@@ -237,6 +239,23 @@ class RogueEnv(Env):
         player's own map only; without it the answer is PRIVILEGED, as path_key is.  secrets=True walks through hidden and locked cells."""
         return self.game.objects(kinds, known, secrets, cap)
 
+    def _visit(self, new_episode: bool) -> None:
+        counter = getattr(self, "_visits", None)
+        if counter is not None:
+            counter.visit(self.result._map[None], [self.result.dungeon_level], new_episode)
+
+    def visit_count(self, what: str = "screen", crop=None) -> int:
+        """How often this episode has shown the state the game is in now, this time included: count-based novelty (the episodic count of RIDE, the
+        `count == 1` gate of NovelD).  what: "screen" hashes the rows of the screen that show tiles, "pos" the player's cell, "crop" the window of
+        crop = r or (ry, rx) around the player; the dungeon level is hashed in.  The first call starts the counting with the present state as a first
+        visit (an env that never asks pays nothing); from then on every step() counts the state it ends in, and reset() and load_state() start a new
+        episode of counts.  Another what or crop starts anew.  The hash is the rule of HipVecRogueEnv's device pass, on the host (rg_novelty_hash_host)."""
+        counter = getattr(self, "_visits", None)
+        if counter is None or self._visit_key != (what, crop):
+            self._visits, self._visit_key = VisitCounter(1, what, crop), (what, crop)
+            self._visit(True)
+        return int(self._visits.counts[0])
+
     def seed(self, seed: int) -> None:
         """Takes effect at the next reset."""
         self.game.set_seed(seed)
@@ -244,6 +263,7 @@ class RogueEnv(Env):
     def reset(self) -> PlayerState:
         self.game.reset()
         state = self.result = self.game.prev()
+        self._visit(True)
         return state
 
     def render(self, mode: str = "human", close: bool = False, tileset=None):

@@ -44,7 +44,17 @@ class RgEpisodeArrays(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("ret", "len", "depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen")] + [("seen_bytes", C.c_int32)]
 
 
+class RgNoveltyArrays(C.Structure):
+    """rg_novelty_arrays_t (include/rogue_gym_hip.h): device pointers."""
+    _fields_ = [(k, C.c_void_p) for k in ("hash", "count", "gcount")]
+
+
 RG_EP_STATS, RG_EP_SCOUT = 1, 2
+RG_NOV_POS, RG_NOV_SCREEN, RG_NOV_CROP = 1, 2, 3
+RG_NOV_EPISODE, RG_NOV_GLOBAL = 1, 2
+NOVELTY_WHAT = {"pos": RG_NOV_POS, "screen": RG_NOV_SCREEN, "crop": RG_NOV_CROP}
+NOVELTY_SCOPE = {"episode": RG_NOV_EPISODE, "global": RG_NOV_GLOBAL, "both": RG_NOV_EPISODE | RG_NOV_GLOBAL}
+NOVELTY_STATS = ("occupied_global", "dropped_global", "dropped_episode", "calls")   # the words of rg_novelty_stats
 RG_EP_DIED, RG_EP_TIME_LIMIT, RG_EP_CUT = 1, 2, 3
 RG_MON_SHOWN, RG_MON_ALL, RG_MON_MAX_CAP, RG_MON_COLS = 0, 1, 16, 8
 MONSTER_MODES = {"shown": RG_MON_SHOWN, "all": RG_MON_ALL}
@@ -68,6 +78,7 @@ _INT_FUNCS = (
     "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
     "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
+    "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host",
     "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
     "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host",
 )
@@ -139,6 +150,10 @@ def load_library():
         "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
         "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, C.POINTER(RgEpisodeArrays)],
         "rg_episode_log_read": [vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)], "rg_scout_host": [vp, i32, i32, vp, C.POINTER(i32)],
+        "rg_novelty_enable": [vp, i32, u32, i32, i32, i32, i32], "rg_novelty_update": [vp], "rg_novelty_cut": [vp, vp, i32, i32, vp],
+        "rg_novelty_arrays": [vp, C.POINTER(RgNoveltyArrays)], "rg_novelty_stats": [vp, C.POINTER(C.c_uint64)], "rg_novelty_table_read": [vp, vp, vp, i32, C.POINTER(i32)],
+        "rg_novelty_clear": [vp], "rg_novelty_hash_host": [i32, i32, i32, i32, vp, i32, i32, i32, i32, C.POINTER(C.c_uint64)],
+        "rg_novelty_finish_host": [C.c_uint64, C.c_uint64], "rg_novelty_insert_host": [vp, i32, u32, C.c_uint64, C.POINTER(u32)],
         "rg_monsters": [vp, u32, i32, vp, vp],
         "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
         "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
@@ -153,6 +168,7 @@ def load_library():
                 "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
                 "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
                 "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
+                "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host", "rg_novelty_finish_host",
                 "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
                 "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():
@@ -167,6 +183,8 @@ def load_library():
     L.rg_build_id.argtypes = []
     if hasattr(L, "rg_sample_index"):
         L.rg_sample_index.restype = C.c_uint32
+    if hasattr(L, "rg_novelty_finish_host"):
+        L.rg_novelty_finish_host.restype = C.c_uint64
     for name in _INT_FUNCS:
         if name in optional and not hasattr(L, name):
             continue
@@ -214,6 +232,43 @@ class Tileset:
         if L.rg_pixels_host(self.th, self.font.ctypes.data, self.palette.ctypes.data, ch, H, W, screen.ctypes.data, int(cy), int(cx), int(ry), int(rx), out.ctypes.data):
             raise RuntimeError("Error in rogue-gym: " + L.rg_last_error(None).decode())
         return out
+
+
+class VisitCounter:
+    """Episodic visit counts for the value API (RogueEnv.visit_count, ParallelRogueEnv.visit_counts): the hash is the library's rule on the host
+    (rg_novelty_hash_host, the twin of the device pass behind HipVecRogueEnv's visit_count), the memory a dict per env that a new episode empties.  what: "pos",
+    "screen" or "crop" with crop = r or (ry, rx); for "pos" and "crop" the player's cell is where the screen shows '@'."""
+
+    def __init__(self, n, what="screen", crop=None):
+        if not isinstance(what, str) or what not in NOVELTY_WHAT:
+            raise ValueError("what must be 'pos', 'screen' or 'crop', got %r" % (what,))
+        if (what == "crop") != (crop is not None):
+            raise ValueError("crop goes with what='crop' and only with it, got what=%r, crop=%r" % (what, crop))
+        ry, rx = (0, 0) if crop is None else (crop, crop) if isinstance(crop, int) else crop
+        self.what, self.radii, self.seen = NOVELTY_WHAT[what], (int(ry), int(rx)), [dict() for _ in range(n)]
+        self.hashes, self.counts = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+
+    def visit(self, screens, levels, new_episode):
+        """Count the states now standing in the envs: screens uint8 [n, H, W], levels [n]; new_episode [n] bool (or one bool for all): that env's memory is emptied first."""
+        L = load_library()
+        out = C.c_uint64(0)
+        new_episode = np.broadcast_to(np.asarray(new_episode, bool), (len(self.seen),))
+        for e, seen in enumerate(self.seen):
+            scr = np.ascontiguousarray(screens[e], np.uint8)
+            px = py = 0
+            if self.what != RG_NOV_SCREEN:
+                at = np.argwhere(scr == ord("@"))
+                if len(at) != 1:
+                    raise RuntimeError("Error in rogue-gym: the screen of env %d shows %d player glyphs" % (e, len(at)))
+                py, px = int(at[0][0]), int(at[0][1])
+            if L.rg_novelty_hash_host(self.what, int(levels[e]), scr.shape[0], scr.shape[1], scr.ctypes.data, px, py, self.radii[0], self.radii[1], C.byref(out)):
+                raise RuntimeError("Error in rogue-gym: " + L.rg_last_error(None).decode())
+            if new_episode[e]:
+                seen.clear()
+            k = int(out.value)
+            seen[k] = seen.get(k, 0) + 1
+            self.hashes[e], self.counts[e] = k, seen[k]
+        return self.counts
 
 
 def _default_device():
