@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(WAVE) k_action_mask(const uint16_t *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 // keys: 1 <= n_keys <= RG_MASK_MAX_KEYS keys of KeyMap::ai (checked by the caller); mask / sample: either may be NULL

@@ -3,7 +3,7 @@
 //   k_crop_typed<KIND, DT> : KIND 0 gray / 1 one-hot with DT = RG_OBS_F32 / RG_OBS_F16 / RG_OBS_BF16, KIND 2 symbol ids with RG_OBS_U8
 //
 // Env e's window is [C][2ry+1][2rx+1], centred on its player cell, of the image the full encode would write, padded with the encoding of ' ' (gray 0, one-hot
-// channel 0, history 0, status planes their constant value).  The mirrors are current (rg_api.cpp flushes the pending render first): this pass only reads them.
+// channel 0, history 0, status planes their constant value).  The mirrors are current (rg_api_obs.cpp flushes the pending render first): this pass only reads them.
 // The scheme: a wave per run of envs on a persistent grid, the window's box of mirror cells staged in LDS, every plane expanded from LDS in the output's type
 // (no value converted per cell) and stored as 16-byte pieces.  An f32 element is the value itself, a 16-bit one that value rounded to nearest even.
 // Built with -Os like rg_obs.hip.  file:line citations name the reference's sources, as in rg_obs.hip.
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(WAVE) k_crop_typed(const uint16_t *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 static void host_magic(CropTypedArgs &a, int which, uint32_t d) {  // (mdiv)
     uint32_t l = 0;

@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(EP_THREADS) k_episode(const EpView V, const Rg
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 // slots: the envs served (an update: the last step's n_keys; a cut: the list's length, or n).  ids / mask: a cut's, both device pointers, at most one of them.

@@ -3188,7 +3188,7 @@ __global__ void __launch_bounds__(WAVE) k_step_huge(RgState S, const RgState *__
 #undef RG_STEP_BLOCK_BODY
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launchers (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launchers: defined here against the prototypes the host units call them by
 // ---------------------------------------------------------------------------------------------
 static int gen_mode_of(const RgConfig *c) { const int nr = c->room_num_x * c->room_num_y; return nr <= 32 ? 0 : (nr <= 64 ? 1 : 2); }
 extern "C" {

@@ -1,0 +1,70 @@
+// rg_launch.h -- the host-callable launchers (rgk_*) of the .hip units, declared ONCE: every unit that defines one and every host unit that calls one includes
+// this file, so a definition whose parameter list differs from what a caller sees is a compile error ("conflicting types"), not a launch with garbage arguments.
+// Declarations only: no inline code, no macro.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rg_state.h"
+
+struct RgIoLayout;  // rg_state_io.h
+struct RgEpisode;   // rg_episode.h
+struct RgNovelty;   // rg_novelty.h
+
+extern "C" {
+// rg_kernels.hip
+void rgk_build(const RgState *S, const RgConfig *c, hipStream_t st);
+void rgk_reset_compact(const uint8_t *mask, int n, int32_t *list, uint32_t *cnt, hipStream_t st);
+void rgk_build_list(const RgState *S, const RgConfig *c, const int32_t *list, const uint32_t *cnt, uint8_t *mark, hipStream_t st);
+int rgk_step_epw(int n, int slots_per_simd);
+size_t rgk_step_lds_per_cu(const RgConfig *c);
+int rgk_step_bound_capable(const RgConfig *c);
+int rgk_step_tail_capable(const RgConfig *c);
+int rgk_step_enc_helpers(int n, int want);
+int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+void rgk_debug_descend(const RgState *S, const RgConfig *c, hipStream_t st);
+void rgk_regen_gate(const uint32_t *mark, uint32_t target, uint32_t *err_any, hipStream_t st);
+void rgk_regen(const RgState *SP, const RgConfig *c, int bulk, int spares, const uint32_t *mark, uint32_t target, uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// rg_regen_lanes.hip
+int rgk_regen_lanes_supported(const RgConfig *c, int maze_cap);
+int rgk_regen_lanes(const RgState *SP, const RgConfig *c, uint32_t *q, int32_t *list, int bulk, int waves, int slots, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// rg_obs.hip
+void rgk_render(const RgState *S, const RgConfig *c, hipStream_t st);
+int rgk_obs(const RgState *S, const RgConfig *c, uint32_t sflag, int with_hist, int kind, float *out, uint32_t *err_any, int planes_sym, int bound, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_obs_tail_capable(const RgState *S, const RgConfig *c);
+int rgk_obs_resid_blocks(int n);
+void rgk_obs_resid(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+void rgk_encode(const uint8_t *screen, const uint8_t *hist, const int32_t *status, uint32_t *flags, uint32_t *err_any, int n, int hw, size_t rs, size_t rst,
+                int symbols, int planes_sym, uint32_t sflag, int with_hist, int kind, float *out, const int32_t *ext, hipStream_t st);
+void rgk_export(const RgState *S, uint32_t *err_any, void *o_screen, void *o_hist, void *o_status, void *o_flags, uint32_t *o_err, hipStream_t st);
+void rgk_pack(const RgState *S, int with_hist, uint8_t *out, hipStream_t st);
+void rgk_scatter_rows(const void *src, void *dst, const int32_t *ext, int n, int row_bytes, hipStream_t st);
+void rgk_gather_keys(const uint8_t *keys, const int32_t *ext, uint8_t *dst, int n, hipStream_t st);
+int rgk_redraw(const RgState *S, const RgConfig *c, hipStream_t st);
+int rgk_obs_typed(const RgState *S, const RgConfig *c, int kind, int dtype, uint32_t sflag, int with_hist, int planes_sym, void *out, uint32_t *err_any, hipStream_t st, hipEvent_t ev0,
+                  hipEvent_t ev1);
+void rgk_probe_clock(unsigned long long *out, int spin, hipStream_t st);
+// rg_crop_typed.hip, rg_pixels.hip
+int rgk_crop_typed(const RgState *S, const RgConfig *c, int kind, int dtype, int ry, int rx, uint32_t sflag, int with_hist, int planes_sym, void *out, int32_t *centers,
+                   uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_pixels_lds(int H, int W, int th, int channels, int ry, int rx, int *run, int *staged);
+int rgk_pixels(const RgState *S, const RgConfig *c, const uint8_t *tiles, int th, int channels, int ry, int rx, uint8_t *out, int32_t *centers, hipStream_t st, hipEvent_t ev0,
+               hipEvent_t ev1);
+// the readers of game state: rg_action_mask.hip, rg_path.hip, rg_route.hip, rg_monsters.hip, rg_objects.hip
+void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
+                     hipEvent_t ev0, hipEvent_t ev1);
+void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
+void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
+               hipStream_t st);
+void rgk_monsters(const RgState *S, const RgConfig *c, uint32_t mode, int cap, int16_t *table, int32_t *threat, hipStream_t st);
+void rgk_objects(const RgState *S, const RgConfig *c, uint32_t kinds, uint32_t mode, int cap, int16_t *table, int32_t *count, hipStream_t st);
+// rg_episode.hip, rg_novelty.hip (librogue_gym_novelty.so)
+void rgk_episode(const RgState *S, const RgConfig *c, const RgEpisode *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, int record, uint32_t serial,
+                 hipStream_t st);
+void rgk_novelty(const RgState *S, const RgConfig *c, const RgNovelty *A, int slots, const int32_t *ids, const uint8_t *mask, int cut, hipStream_t st);
+const char *rgk_novelty_build_id(void);
+// rg_state_io.hip
+void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st);
+void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
+                    uint8_t *mark, hipStream_t st);
+void rgk_state_stairs(const RgState *S, const RgIoLayout *L, uint8_t *mark, hipStream_t st);
+}

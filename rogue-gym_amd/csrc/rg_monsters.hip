@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(MON_THREADS) k_monsters(const MonView V) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 // mode: RG_MON_SHOWN / RG_MON_ALL; cap: 1 .. RG_MON_MAX_CAP when table is given; table / threat: 16-byte aligned, either may be NULL (checked by the caller)

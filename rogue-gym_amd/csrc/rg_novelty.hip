@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(NOV_THREADS) k_nov_count(const NovView V, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 template <bool WIDE>
 static void launch_hash(int units, int slots, hipStream_t st, const NovView &V, const RgNovelty &A) {

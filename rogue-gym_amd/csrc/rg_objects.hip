@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4))) 
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launcher: defined here against the prototype the host units call it by
 // ---------------------------------------------------------------------------------------------
 template <int WN, int GS>
 static void launch_objects(const RgState *S, const RgConfig *c, uint32_t kinds, uint32_t mode, int cap, int16_t *table, int32_t *count, hipStream_t st) {

@@ -967,7 +967,7 @@ __global__ void __launch_bounds__(OBS_THREADS) k_obs_typed(const uint8_t *__rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launchers (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launchers: defined here against the prototypes the host units call them by
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 void rgk_render(const RgState *S, const RgConfig *c, hipStream_t st) {

@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(WAVE) k_pixels(const uint16_t *__restrict__ p_
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (used by rg_api.cpp)
+#include "rg_launch.h"  // host-callable launchers: defined here against the prototypes the host units call them by
 // ---------------------------------------------------------------------------------------------
 static void host_magic(PixelArgs &a, int which, uint32_t d) {  // (mdiv)
     uint32_t l = 0;

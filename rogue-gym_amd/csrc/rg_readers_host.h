@@ -1,6 +1,6 @@
-// rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api.cpp) share with the *_host twins, and the
+// rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api_*.cpp) share with the *_host twins, and the
 // twins themselves (rgh_*; rg_action_mask_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
-// rg_novelty_insert_host are one-line delegations in rg_api.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
+// rg_novelty_insert_host are one-line delegations in rg_api_readers.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
 // (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
 #pragma once
 #include <algorithm>
@@ -102,6 +102,22 @@ static inline int obj_args_check(std::string &err, const char *what, uint32_t ki
     }
     if (!have_table && !have_count) { err = w + table_name + " and " + count_name + " are both NULL"; return 1; }
     if (have_table && (cap < 1 || cap > RG_OBJ_MAX_CAP)) { err = w + "cap must satisfy 1 <= cap <= " + std::to_string(RG_OBJ_MAX_CAP) + ", got " + std::to_string(cap); return 1; }
+    return 0;
+}
+// the env-id list of a cut, a partial reset, a save / load or rg_seed_envs: k ids of [0, n); unique: none of them twice, so k <= n.  ids == NULL (the list lives on
+// the device): only k is judged
+static inline int rgh_env_ids_check(std::string &err, const char *what, const int32_t *ids, int k, int n, bool unique) {
+    const std::string w = std::string(what) + ": ";
+    if (k < 0 || (unique && k > n)) { err = w + "k = " + std::to_string(k) + " env_ids for " + std::to_string(n) + " envs"; return 1; }
+    if (!ids) return 0;
+    std::vector<uint8_t> seen(unique ? (size_t)n : 0, 0);
+    for (int i = 0; i < k; i++) {
+        const int32_t e = ids[i];
+        if (e < 0 || e >= n) { err = w + "env_ids[" + std::to_string(i) + "] = " + std::to_string(e) + " out of range [0, " + std::to_string(n) + ")"; return 1; }
+        if (!unique) continue;
+        if (seen[e]) { err = w + "env_ids holds " + std::to_string(e) + " twice"; return 1; }
+        seen[e] = 1;
+    }
     return 0;
 }
 

@@ -634,12 +634,12 @@ k_regen_lanes(RgState SP, RgConfig c, const uint32_t *__restrict__ q, const int3
 }
 
 // ---------------------------------------------------------------------------------------------
-// host-callable launcher (rg_api.cpp)
+#include "rg_launch.h"  // host-callable launchers: defined here against the prototypes the host units call them by
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 // Geometry of a launch for this config; lanes = 0 when the level-per-lane producer does not apply (more than 32 rooms: the room sets are 32-bit masks;
 // a grid so large that fewer than 16 lanes' worth fits the CU's LDS) -- the caller then keeps the wave-per-level producer.
-size_t rgk_step_lds_per_cu(const RgConfig *c);  // rg_kernels.hip
+// (the step kernels' share of that LDS: rg_kernels.hip's launcher of that name)
 struct RgLanesPlan { int lanes, lane_stride, tab_off, stk_off, smem; };
 static RgLanesPlan lanes_plan(const RgConfig *c, int maze_cap) {
     RgLanesPlan p = {0, 0, 0, 0, 0};

@@ -1,5 +1,5 @@
 // rg_state_io.h -- layout of a STATE RECORD: one env's running game as a fixed-size, position-independent byte string (rg_state_save / rg_state_load,
-// include/rogue_gym_hip.h).  The host computes the layout (rg_api.cpp state_layout); the kernels (rg_state_io.hip) take it as a kernel argument.
+// include/rogue_gym_hip.h).  The host computes the layout (rg_api_state.cpp state_layout); the kernels (rg_state_io.hip) take it as a kernel argument.
 //
 //   [0, 64)            header: u32 words {magic, RG_STATE_VERSION, R, H | W << 16, rooms, sections, fingerprint lo, fingerprint hi, klog cap, klog len, 0 ...}
 //   o_cell             cell    u16 [H*W]

@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(IO_THREADS) k_state_stairs(RgState S, RgIoLayo
         if (mine && on) S.stair_list[(size_t)w * S.n + base + __popcll(m & ((1ull << lane) - 1ull))] = e;
     }
 }
-
+#include "rg_launch.h"  // host-callable launchers: defined here against the prototypes the host units call them by
 extern "C" {
 void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, uint8_t *out, hipStream_t st) {
     if (k <= 0) return;

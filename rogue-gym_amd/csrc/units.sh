@@ -1,7 +1,14 @@
-# The translation units of librogue_gym_hip.so and the optimisation level of each, in link order; sourced by build.sh and tools/build_variant.sh.
-# The step kernels want -O3; the bandwidth-bound render/observation kernels are faster with -Os (less unrolling).
+# The translation units of librogue_gym_hip.so and the optimisation level of each, in link order: THE list, sourced by build.sh and tools/build_variant.sh and
+# read by __graft_entry__.build() (which sources this file in a shell and prints the variables).
+# The step kernels want -O3; the bandwidth-bound render/observation kernels are faster with -Os (less unrolling).  The host units (rg_api*.cpp: the C-ABI by
+# subsystem, DESIGN.md "The host layer") take -O2.
 UNITS="rg_kernels.hip:-O3 rg_regen_lanes.hip:-O3 rg_obs.hip:-Os rg_crop_typed.hip:-Os rg_pixels.hip:-Os rg_action_mask.hip:-Os rg_path.hip:-O3 rg_route.hip:-O3
-       rg_episode.hip:-O3 rg_monsters.hip:-O3 rg_objects.hip:-O3 rg_state_io.hip:-O3 rg_api.cpp:-O2 rg_config.cpp:-O2 rg_items.cpp:-O2"
+       rg_episode.hip:-O3 rg_monsters.hip:-O3 rg_objects.hip:-O3 rg_state_io.hip:-O3
+       rg_api.cpp:-O2 rg_api_obs.cpp:-O2 rg_api_readers.cpp:-O2 rg_api_episode.cpp:-O2 rg_api_state.cpp:-O2 rg_api_comm.cpp:-O2 rg_api_diag.cpp:-O2
+       rg_config.cpp:-O2 rg_items.cpp:-O2"
 # The novelty pass is a library of its own, librogue_gym_novelty.so, which librogue_gym_hip.so links (found beside it at run time): its kernels stay out of the
 # code objects whose kernel set tests/test_pixels_resources.py pins by name.
 NOVELTY_UNITS="rg_novelty.hip:-O3"
+# The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
+# Of the host units only the core reads the environment (tests/test_novelty_resources.py).
+KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"

@@ -327,7 +327,7 @@ def record_offsets(rec):
     return o_cell, off, H, W
 
 
-WORD_POS, WORD_FLAGS = 0, 10  # the SoA section's words, in state_prepare's order (rg_api.cpp): p_pos first, the flag word eleventh
+WORD_POS, WORD_FLAGS = 0, 10  # the SoA section's words, in state_prepare's order (rg_api_state.cpp): p_pos first, the flag word eleventh
 
 
 def inject(hip, grids, players, dead, check_every=1):

@@ -186,7 +186,7 @@ def listed(f, rows):
 
 
 # ---------------------------------------------------------------------------------------------
-# the monster words of a state record (the SoA section's words in state_prepare's order, rg_api.cpp): 13 scalars, 12 RNG words, mon_cnt, 9 dist-cache
+# the monster words of a state record (the SoA section's words in state_prepare's order, rg_api_state.cpp): 13 scalars, 12 RNG words, mon_cnt, 9 dist-cache
 # keys, dc_head, dc_len, dc_part, dc_own, then per room: rect, meta, mon_w0, mon_hp, mon_exp, gold_pos, gold_amt
 # ---------------------------------------------------------------------------------------------
 WORD_MON_CNT = 25

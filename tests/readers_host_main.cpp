@@ -357,6 +357,37 @@ static void check_refusals() {
     runs += n;
 }
 
+// the env-id list check of the cuts, the partial reset, the records and rg_seed_envs: each list on the heap at its exact size
+static void check_env_ids() {
+    const int n = 8;
+    std::string err;
+    auto ids = [](std::initializer_list<int32_t> l) { return std::vector<int32_t>(l); };
+    auto accepted = [&](const std::vector<int32_t> &l, int k, bool unique, const char *what) {
+        runs++;
+        EXPECT(rgh_env_ids_check(err, "rg_x", l.data(), k, n, unique) == 0 && err.empty(), "env ids %s: refused, \"%s\"", what, err.c_str());
+        err.clear();
+    };
+    auto refused = [&](const std::vector<int32_t> &l, int k, bool unique, const char *word, const char *what) {
+        runs++;
+        EXPECT(rgh_env_ids_check(err, "rg_x", l.data(), k, n, unique) == 1 && err.compare(0, 6, "rg_x: ") == 0 && err.find("env_ids") != std::string::npos &&
+                   err.find(word) != std::string::npos, "env ids %s: \"%s\"", what, err.c_str());
+        err.clear();
+    };
+    for (int unique = 0; unique < 2; unique++) {
+        accepted(ids({}), 0, unique, "k = 0");
+        accepted(ids({7, 6, 5, 4, 3, 2, 1, 0}), n, unique, "k = n, all distinct");
+        refused(ids({3, -1}), 2, unique, "out of range", "id -1");
+        refused(ids({0, n}), 2, unique, "out of range", "id n");
+        refused(ids({}), -1, unique, "k = -1", "k < 0");
+    }
+    accepted(ids({2, 5, 2}), 3, false, "a duplicate without unique");
+    refused(ids({2, 5, 2}), 3, true, "twice", "a duplicate with unique");
+    accepted(ids({0, 1, 2, 3, 4, 5, 6, 7, 0}), n + 1, false, "k = n + 1 without unique");
+    refused(ids({0, 1, 2, 3, 4, 5, 6, 7, 0}), n + 1, true, "k = 9", "k = n + 1 with unique");
+    runs++;  // a device-side list: only its length is judged
+    EXPECT(rgh_env_ids_check(err, "rg_x", nullptr, n, n, true) == 0 && rgh_env_ids_check(err, "rg_x", nullptr, n + 1, n, true) == 1, "env ids NULL list");
+}
+
 int main() {
     static const int sizes[8][2] = {{1, 1}, {1, 7}, {5, 1}, {16, 32}, {17, 33}, {24, 80}, {RG_MAX_H, RG_MAX_W}, {9, 11}};
     for (auto &s : sizes) {
@@ -378,6 +409,7 @@ int main() {
         }
     }
     check_refusals();
+    check_env_ids();
     printf("%d runs, %d mismatches\n", runs, bad);
     return bad ? 1 : 0;
 }

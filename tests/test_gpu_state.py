@@ -378,7 +378,72 @@ def test_stairs_and_next_level_structures_after_load(goldens):
 
 
 # ---------------------------------------------------------------------------------------------
-# 7. refusals
+# 7. host-side env-id lists share one staging buffer
+# ---------------------------------------------------------------------------------------------
+def test_host_id_lists_back_to_back_equal_device_lists(goldens):
+    """rg_episode_cut, rg_novelty_cut and rg_state_save upload their host-side env ids into ONE buffer of the handle.  Three calls with three lists and no
+    sync in between must serve the envs each was given: a second handle, same seeds and keys, is given the same lists as device tensors, which are not staged,
+    and the episode arrays, the novelty arrays and the saved records of the two are byte-equal."""
+    torch = torch_mod()
+    from episode_util import CUT
+    from novelty_util import SCREEN
+    from rogue_gym_python._rogue_gym import RgEpisodeArrays, RgNoveltyArrays
+
+    n, steps = 8, 8
+    lists = ([1, 5], [2, 6, 7], [0, 3, 3])   # the cut of the episodes, the cut of the novelty tables, the save (which takes a duplicate)
+    rng = np.random.RandomState(77)
+    keys = [ALL_KEYS[rng.randint(0, len(ALL_KEYS), n)] for _ in range(steps)]
+
+    def run(on_device):
+        hip = HipBatch(goldens["configs"]["mini"], [900 + i for i in range(n)], max_steps=5, auto_reset=True)   # (5 < steps: every env has auto-reset once)
+        hd, L = hip.h, hip.h.L
+        dev = "cuda:%d" % hd.device
+        hd.check(L.rg_episode_enable(hd.h, 3, 0))
+        hd.check(L.rg_novelty_enable(hd.h, SCREEN, 3, 0, 0, 64, 1024))
+        for k in keys:
+            hip.step(k)
+            hd.check(L.rg_episode_update(hd.h))
+            hd.check(L.rg_novelty_update(hd.h))
+        recs = torch.zeros((len(lists[2]), L.rg_state_record_bytes(hd.h)), dtype=torch.uint8, device=dev)
+        if on_device:
+            held = [torch.tensor(l, dtype=torch.int32, device=dev) for l in lists]
+            ptr = [C.c_void_p(t.data_ptr()) for t in held]
+        else:
+            held = [np.array(l, np.int32) for l in lists]
+            ptr = [a.ctypes.data for a in held]
+        torch.cuda.synchronize()
+        hd.check(L.rg_episode_cut(hd.h, ptr[0], len(lists[0]), int(on_device), None, 1))
+        hd.check(L.rg_novelty_cut(hd.h, ptr[1], len(lists[1]), int(on_device), None))
+        hd.check(L.rg_state_save(hd.h, ptr[2], len(lists[2]), int(on_device), C.c_void_p(recs.data_ptr())))
+        hip.sync()
+
+        def read(p, count, dtype):
+            out = np.empty(count, dtype)
+            hd.check(L.rg_dev_read(hd.h, C.c_void_p(p), out.ctypes.data, out.nbytes))
+            return out
+
+        e, v = RgEpisodeArrays(), RgNoveltyArrays()
+        hd.check(L.rg_episode_arrays(hd.h, C.byref(e)))
+        hd.check(L.rg_novelty_arrays(hd.h, C.byref(v)))
+        got = {k: read(getattr(e, k), n, t) for k, t in (("ret", "<f4"), ("len", "<i4"), ("depth", "<i4"), ("died", "|u1"), ("time_limit", "|u1"), ("last_return", "<f4"),
+                                                         ("last_length", "<i4"), ("last_depth", "<i4"), ("last_cause", "|u1"), ("scout", "<f4"))}
+        got["seen"] = read(e.seen, n * e.seen_bytes, "|u1")
+        got.update({"nov_" + k: read(getattr(v, k), n, t) for k, t in (("hash", "<u8"), ("count", "<i4"), ("gcount", "<i4"))})
+        got["records"] = recs.cpu().numpy()
+        hd.close()
+        return got
+
+    host, device = run(False), run(True)
+    assert sorted(host) == sorted(device)
+    for k in host:
+        assert host[k].tobytes() == device[k].tobytes(), k
+    assert np.array_equal(host["records"][1], host["records"][2]) and not np.array_equal(host["records"][0], host["records"][1])   # env 3 twice, env 0 once
+    cut = np.isin(np.arange(n), lists[0])
+    assert ((host["last_cause"] == CUT) == cut).all(), host["last_cause"]   # the recorded cut ended the episodes of its envs and of no other
+
+
+# ---------------------------------------------------------------------------------------------
+# 8. refusals
 # ---------------------------------------------------------------------------------------------
 def test_refusals(goldens):
     torch = torch_mod()

@@ -55,9 +55,8 @@ def test_the_novelty_sources_read_no_environment_variable():
     csrc = os.path.join(ROOT, "rogue-gym_amd", "csrc")
     for f in ("rg_novelty.h", "rg_novelty.hip"):
         assert "getenv" not in open(os.path.join(csrc, f)).read(), f
-    # the entry points' section of rg_api.cpp reads none either; the product-wide list of knobs is tests/test_cabi_load.py's, which this change leaves as it is
-    api = open(os.path.join(csrc, "rg_api.cpp")).read()
-    sec = api[api.index("// ---- count-based novelty"):api.index("int rg_obs_gray(")]
-    assert "rg_novelty_clear" in sec and "getenv" not in sec and "RG_DEV_ENV" not in sec
+    # the host unit of the entry points reads none either, anywhere in it; the product-wide list of knobs is tests/test_cabi_load.py's, which this change leaves as it is
+    unit = open(os.path.join(csrc, "rg_api_episode.cpp")).read()
+    assert "rg_novelty_clear" in unit and "getenv" not in unit and "RG_DEV_ENV" not in unit
     py = open(os.path.join(ROOT, "rogue-gym_amd", "rogue_gym", "envs", "device.py")).read()
     assert "environ" not in py and "getenv" not in py
