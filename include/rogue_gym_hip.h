@@ -467,6 +467,47 @@ int rg_novelty_hash_host(int what, int level, int height, int width, const uint8
 uint64_t rg_novelty_finish_host(uint64_t acc, uint64_t salt);
 int rg_novelty_insert_host(void *slots, int cap, uint32_t gen, uint64_t hash, uint32_t *count);
 
+/* CELL ARCHIVE: per hashed state ("cell", Go-Explore's word) the best state record any env has offered, kept on the device, and the way back into it -- the
+ * join of rg_state_save / rg_state_load and the novelty hash.  A pass of its own behind the step: a handle that does not enable it launches and allocates
+ * nothing more.  The rule -- offers, who beats whom, the table -- is stated once in csrc/rg_archive.h.
+ *   An OFFER is (key u64, score i32, steps u32, env).  A key of 0 is offered as 1.  A beats B iff score_A > score_B, or the scores are equal and
+ *     steps_A < steps_B; among offers of ONE call with equal (score, steps) the lowest env id wins.
+ *   rg_archive_enable(h, cells): one open-addressed table of `cells` slots (a power of two, 1 024 .. 2^24) and cells x R record bytes, R =
+ *     rg_state_record_bytes(h) -- 192 MB at 2^14 cells of the mini config.  Refused with a message that names the argument, nothing allocated: a handle with
+ *     config groups, a second enable, cells not a power of two in range, an allocation that fails.
+ *   rg_archive_update(h, key_dev, score_dev, mask_dev), asynchronous on the handle's stream, flushes the pending render first as rg_state_save does.  Every env
+ *     offers (mask_dev u8 [N] given: the envs with a non-zero byte).  key_dev NULL: the novelty hash (refused unless rg_novelty_enable was called); score_dev
+ *     NULL: the env's pack gold; steps is always the env's steps word.  For every key offered: seen grows by the number of offers; if the best offer of the
+ *     call beats the stored one strictly (an empty slot is beaten by anything; an equal (score, steps) from a later call replaces nothing) that env's state
+ *     record -- byte for byte what rg_state_save would write at this moment -- replaces the stored one and (score, steps, when) follow, when = the serial of
+ *     this call counted from 1.  slot[e] = the slot of env e's key, -1 if the probe found neither the key nor an empty slot within min(cells, 1 024)
+ *     probes (the offer is DROPPED and counted) or the env was masked out; stored[e] = 1 iff env e's record was written by this call.  Except for which slot
+ *     a key lands in, the table after a call does not depend on scheduling.
+ *   rg_archive_arrays: device pointers valid until rg_destroy.  Per slot [cells]: key u64 (0 = empty), score i32, steps u32, seen u32, chosen u32, when u32,
+ *     records u8 [cells][R].  Per env [N]: slot i32, stored u8, score_in i32 / steps_in u32 (what the last update read); these have 64 envs of slack
+ *     behind env N-1 that no launch writes.
+ *   rg_archive_restore(h, slot_ids, env_ids, k, ids_on_device): the records of slot_ids[0 .. k) are gathered into a staging buffer and loaded into env_ids
+ *     (NULL: envs 0 .. k-1 with k = N) by rg_state_load, whose rules and refusals hold; chosen of each slot whose record was taken grows by 1.  An empty
+ *     slot's all-zero record (or a device-side slot id out of range) is refused by the load's header check: the env is untouched, RG_FLAG_ERR_STATE is
+ *     raised, chosen stays.  Host slot ids out of range are refused before anything is launched.  A slot may be named more than once.  Behind it the caller
+ *     does what follows an rg_state_load (rg_novelty_cut, rg_episode_cut).
+ *   rg_archive_stats (waits for the stream): out[0] occupied slots, [1] dropped offers, [2] records written, [3] update calls since the enable or the last
+ *     clear.  rg_archive_clear empties the table, the records and the counters.
+ *   rg_archive_offer_host (stateless, needs no device): the probe and the beats rule for ONE offer on a host table of `cells` (a power of two, 1 .. 2^24)
+ *     slots of 32 bytes {u64 key, i32 score, u32 steps, u32 seen, u32 chosen, u32 when, u32 zero}, 8-byte aligned; serial != 0.  *slot = the key's slot or
+ *     -1 (dropped: nothing written); *stored = 1 iff the offer replaced the stored one.  Refusals are read through rg_last_error(NULL). */
+typedef struct rg_archive_arrays_t {
+    uint64_t *key; int32_t *score; uint32_t *steps; uint32_t *seen; uint32_t *chosen; uint32_t *when; uint8_t *records;
+    int32_t *slot; uint8_t *stored; int32_t *score_in; uint32_t *steps_in;
+} rg_archive_arrays_t;
+int rg_archive_enable(rg_t *h, int cells);
+int rg_archive_update(rg_t *h, const uint64_t *key_dev, const int32_t *score_dev, const uint8_t *mask_dev);
+int rg_archive_arrays(rg_t *h, rg_archive_arrays_t *out);
+int rg_archive_restore(rg_t *h, const int32_t *slot_ids, const int32_t *env_ids, int k, int ids_on_device);
+int rg_archive_stats(rg_t *h, uint64_t *out);
+int rg_archive_clear(rg_t *h);
+int rg_archive_offer_host(void *slots, int cells, uint64_t key, int32_t score, uint32_t steps, uint32_t serial, int32_t *slot, int32_t *stored);
+
 /* MONSTER TABLES AND THREAT WORDS: the nearest monsters of every env as an entity list, and four words that say how close they are.  The monster tables are
  * device-resident and bit-exact with the reference; this is one small pass behind the step that hands them out in a form a policy, a shaping term or a
  * teacher can use, without parsing the image.  The rule is stated once in csrc/rg_monsters.h.

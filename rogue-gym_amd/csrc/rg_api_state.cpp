@@ -1,5 +1,5 @@
-// rg_api_state.cpp -- state records, the partial reset and rg_seed_envs behind the C-ABI: the entry points that serve the envs a caller picks, and the staging of
-// their env-id lists (env_ids_stage, which the cuts of rg_api_episode.cpp share).
+// rg_api_state.cpp -- state records, the cell archive that keeps them per hashed state, the partial reset and rg_seed_envs behind the C-ABI: the entry points that
+// serve the envs a caller picks, and the staging of their env-id lists (env_ids_stage, which the cuts of rg_api_episode.cpp share).
 #include <cstring>
 
 #include "rg_handle.h"
@@ -151,6 +151,135 @@ int rg_state_load(rg_t *h, const uint8_t *rec_dev, size_t rec_bytes, const int32
     HIPCHK(h, hipGetLastError());
     h->bound_valid = false;  // the bound observation tensor does not show the restored screens: its next call encodes every env
     return 0;
+}
+
+// ---- the cell archive (rg_archive.h; k_arc_* in rg_archive.hip, librogue_gym_archive.so) ----
+int rg_archive_enable(rg_t *h, int cells) {
+    const std::string w = "rg_archive_enable: ";
+    if (!h->sub.empty()) { h->err = w + "not for a handle with config groups (no state records; one handle per config)"; return 1; }
+    if (h->arc_on) { h->err = w + "the archive is enabled already"; return 1; }
+    if (!rg_arc_pow2_in(cells, RG_ARC_CELLS_MIN, RG_ARC_CELLS_MAX)) {
+        h->err = w + "cells must be a power of two, " + std::to_string(RG_ARC_CELLS_MIN) + " <= cells <= " + std::to_string(RG_ARC_CELLS_MAX) + ", got " + std::to_string(cells);
+        return 1;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    RgIoLayout L;
+    state_layout(h, &L);
+    const size_t n = (size_t)h->S.n, m = n + RG_ARC_SLACK, c = (size_t)cells, had = h->allocs.size();
+    RgArchive A = {};
+    A.cells = cells; A.R = L.R;
+    const bool ok = dev_alloc(h, &A.key, c) && dev_alloc(h, &A.score, c) && dev_alloc(h, &A.steps, c) && dev_alloc(h, &A.seen, c) && dev_alloc(h, &A.chosen, c) &&
+                    dev_alloc(h, &A.when, c) && dev_alloc(h, &A.bid, c) && dev_alloc(h, &A.win, c) && dev_alloc(h, &A.slot, m) && dev_alloc(h, &A.stored, m) &&
+                    dev_alloc(h, &A.score_in, m) && dev_alloc(h, &A.steps_in, m) && dev_alloc(h, &A.list, n) && dev_alloc(h, &A.cnt, 4) && dev_alloc(h, &A.stat, 4) &&
+                    dev_alloc(h, &A.records, c * (size_t)L.R);
+    if (!ok) {  // (a table that does not fit: what this call allocated goes back, the handle is as before)
+        while (h->allocs.size() > had) { (void)hipFree(h->allocs.back()); h->allocs.pop_back(); }
+        (void)hipGetLastError();
+        h->err = w + "cells = " + std::to_string(cells) + " records of " + std::to_string(L.R) + " bytes: " + h->err;
+        return 1;
+    }
+    HIPCHK(h, hipMemset(A.slot, 0xff, n * sizeof(int32_t)));  // no env has a slot yet (the slack stays as allocated: zero)
+    h->arc = A;
+    h->arc_on = true;
+    h->arc_serial = 0;
+    HIPCHK(h, hipDeviceSynchronize());  // (the allocations were zeroed on the null stream, which the handle's stream may not wait for)
+    return 0;
+}
+static int archive_on(rg_handle *h, const char *what) {
+    if (!h->arc_on) { h->err = std::string(what) + ": the archive is not enabled (rg_archive_enable)"; return 1; }
+    return 0;
+}
+int rg_archive_update(rg_t *h, const uint64_t *key_dev, const int32_t *score_dev, const uint8_t *mask_dev) {
+    if (archive_on(h, "rg_archive_update")) return 1;
+    if (!key_dev) {
+        if (!h->nov_on) { h->err = "rg_archive_update: key_dev is NULL and novelty is not enabled (rg_novelty_enable): there is no hash to take"; return 1; }
+        key_dev = h->nov.hash;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (state_prepare(h) || flush_render(h)) return 1;  // (records hold drawn mirrors: no Redraw is pending in them)
+    RgIoLayout L;
+    state_layout(h, &L);
+    rgk_archive_update(&h->S, &L, h->io_desc, h->io_guard, &h->arc, key_dev, score_dev, mask_dev, ++h->arc_serial, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_archive_arrays(rg_t *h, rg_archive_arrays_t *out) {
+    if (archive_on(h, "rg_archive_arrays")) return 1;
+    if (!out) { h->err = "rg_archive_arrays: out is NULL"; return 1; }
+    const RgArchive &A = h->arc;
+    *out = rg_archive_arrays_t{A.key, A.score, A.steps, A.seen, A.chosen, A.when, A.records, A.slot, A.stored, A.score_in, A.steps_in};
+    return 0;
+}
+int rg_archive_restore(rg_t *h, const int32_t *slot_ids, const int32_t *env_ids, int k, int ids_on_device) {
+    if (archive_on(h, "rg_archive_restore")) return 1;
+    if (!slot_ids) { h->err = "rg_archive_restore: slot_ids is NULL"; return 1; }
+    if (!env_ids) k = h->S.n;
+    if (k < 0) { h->err = "rg_archive_restore: negative record count"; return 1; }
+    if (k == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t *sid = slot_ids;
+    if (!ids_on_device) {
+        for (int i = 0; i < k; i++)
+            if (slot_ids[i] < 0 || slot_ids[i] >= h->arc.cells) {
+                h->err = "rg_archive_restore: slot_ids[" + std::to_string(i) + "] = " + std::to_string(slot_ids[i]) + " is out of range [0, " + std::to_string(h->arc.cells) + ")";
+                return 1;
+            }
+        // (the env ids are checked before anything is launched, as the load itself will check them)
+        if (env_ids && rgh_env_ids_check(h->err, "rg_archive_restore", env_ids, k, h->S.n, true)) return 1;
+    }
+    bool grown = false;
+    if (!ids_on_device && (size_t)k > h->arc_sid_cap) {
+        size_t cap = h->arc_sid_cap ? h->arc_sid_cap : 256;
+        while (cap < (size_t)k) cap *= 2;
+        if (!dev_alloc(h, &h->arc_sid, cap)) return 1;
+        h->arc_sid_cap = cap; grown = true;
+    }
+    if ((size_t)k > h->arc_stage_cap) {
+        size_t cap = h->arc_stage_cap ? h->arc_stage_cap : 256;
+        while (cap < (size_t)k) cap *= 2;
+        if (!dev_alloc(h, &h->arc_stage, cap * (size_t)h->arc.R)) return 1;
+        h->arc_stage_cap = cap; grown = true;
+    }
+    if (grown) HIPCHK(h, hipDeviceSynchronize());  // (the allocation was zeroed on the null stream, which the handle's stream may not wait for)
+    if (!ids_on_device) {
+        HIPCHK(h, hipMemcpyAsync(h->arc_sid, slot_ids, (size_t)k * 4, hipMemcpyHostToDevice, h->stream));  // (pageable source: staged before the call returns)
+        sid = h->arc_sid;
+    }
+    rgk_archive_gather(&h->arc, sid, k, h->arc_stage, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (rg_state_load(h, h->arc_stage, (size_t)h->arc.R, env_ids, k, ids_on_device)) return 1;
+    rgk_archive_chosen(&h->arc, sid, k, h->io_ok, h->stream);  // (io_ok: per record, whether the load took it)
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int rg_archive_stats(rg_t *h, uint64_t *out) {
+    if (archive_on(h, "rg_archive_stats")) return 1;
+    if (!out) { h->err = "rg_archive_stats: out is NULL"; return 1; }
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(st, h->arc.stat, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out[0] = st[0]; out[1] = st[1]; out[2] = st[2]; out[3] = h->arc_serial;
+    return 0;
+}
+int rg_archive_clear(rg_t *h) {
+    if (archive_on(h, "rg_archive_clear")) return 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    const RgArchive &A = h->arc;
+    const size_t c = (size_t)A.cells;
+    HIPCHK(h, hipMemsetAsync(A.key, 0, c * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.bid, 0, c * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.win, 0, c * 8, h->stream));
+    for (void *p : {(void *)A.score, (void *)A.steps, (void *)A.seen, (void *)A.chosen, (void *)A.when}) HIPCHK(h, hipMemsetAsync(p, 0, c * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.records, 0, c * (size_t)A.R, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.slot, 0xff, (size_t)h->S.n * 4, h->stream));  // (the envs' slots of the last update are gone with the table)
+    HIPCHK(h, hipMemsetAsync(A.stored, 0, (size_t)h->S.n, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.stat, 0, 4 * sizeof(unsigned long long), h->stream));
+    h->arc_serial = 0;
+    return 0;
+}
+int rg_archive_offer_host(void *slots, int cells, uint64_t key, int32_t score, uint32_t steps, uint32_t serial, int32_t *slot, int32_t *stored) {
+    return rga_offer_host(g_create_err, slots, cells, key, score, steps, serial, slot, stored);
 }
 
 // ---- partial reset: the envs a caller picks (rg_kernels.hip k_reset_compact / k_build_list) ----

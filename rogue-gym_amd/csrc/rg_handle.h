@@ -10,6 +10,7 @@
 #include "rg_state.h"
 #include "rg_episode.h"
 #include "rg_novelty.h"
+#include "rg_archive.h"
 
 // (rg_api_comm.cpp spells out the few RCCL declarations it needs; the handle holds the communicator)
 extern "C" { typedef struct ncclComm *ncclComm_t; }
@@ -100,6 +101,12 @@ struct rg_handle {
     bool nov_on = false;
     RgNovelty nov = {};
     uint64_t nov_calls = 0;                            // update / cut calls since the enable or the last clear
+    // the cell archive (rg_archive_*; rg_archive.h): off until rg_archive_enable, which allocates the slot arrays and the records
+    bool arc_on = false;
+    RgArchive arc = {};
+    uint32_t arc_serial = 0;                           // update calls since the enable or the last clear: the `when` of the records the next one writes, from 1
+    uint8_t *arc_stage = nullptr; size_t arc_stage_cap = 0;   // rg_archive_restore: the gathered records (grown like ids_buf: the old buffer stays until rg_destroy)
+    int32_t *arc_sid = nullptr; size_t arc_sid_cap = 0;       // ... and its host-side slot ids, uploaded
     // the tileset of the pixel passes (rg_tileset_set; rg_pixels.h): the font, then the ink table; allocated at the first call.  Config groups read the parent's
     uint8_t *tiles = nullptr; int tile_th = 0;
 };

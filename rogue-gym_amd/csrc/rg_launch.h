@@ -9,6 +9,7 @@
 struct RgIoLayout;  // rg_state_io.h
 struct RgEpisode;   // rg_episode.h
 struct RgNovelty;   // rg_novelty.h
+struct RgArchive;   // rg_archive.h
 
 extern "C" {
 // rg_kernels.hip
@@ -67,4 +68,10 @@ void rgk_state_save(const RgState *S, const RgIoLayout *L, const uint64_t *desc,
 void rgk_state_load(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const int32_t *ids, int k, const uint8_t *recs, uint32_t rec_bytes, uint8_t *ok,
                     uint8_t *mark, hipStream_t st);
 void rgk_state_stairs(const RgState *S, const RgIoLayout *L, uint8_t *mark, hipStream_t st);
+// rg_archive.hip (librogue_gym_archive.so)
+void rgk_archive_update(const RgState *S, const RgIoLayout *L, const uint64_t *desc, const uint32_t *guard, const RgArchive *A, const uint64_t *key, const int32_t *score,
+                        const uint8_t *mask, uint32_t serial, hipStream_t st);
+void rgk_archive_gather(const RgArchive *A, const int32_t *sid, int k, uint8_t *out, hipStream_t st);
+void rgk_archive_chosen(const RgArchive *A, const int32_t *sid, int k, const uint8_t *ok, hipStream_t st);
+const char *rgk_archive_build_id(void);
 }

@@ -48,7 +48,8 @@ class HipVecRogueEnv:
                  episodes: bool = False, scout: bool = False, episode_log: int = 0, monsters=None, monster_cap: int = 4,
                  objects=None, object_kinds: str = "stairs+gold+door", object_cap: int = 8, object_secrets: bool = False,
                  pixels=None, pixel_crop=None, tileset=None,
-                 novelty=None, novelty_scope: str = "episode", novelty_crop=None, novelty_slots: int = 1024, novelty_global_slots: int = 1 << 22):
+                 novelty=None, novelty_scope: str = "episode", novelty_crop=None, novelty_slots: int = 1024, novelty_global_slots: int = 1 << 22,
+                 archive=None, archive_auto: bool = True):
         """persistent_obs (opt-in; image settings without status planes and history plane): `self.obs` is BOUND to the stepper (rg_obs_bind) -- every step
         keeps it current in place, rewriting only the envs whose screen changed; its contents are bit-identical to the unbound encode's.  The caller
         must not write to `self.obs`.
@@ -135,7 +136,17 @@ class HipVecRogueEnv:
         slots (a power of two, 1 024 .. 2^28), as it stands after the whole step; "both": both.  A visit that finds its table full counts 0 and is
         reported by novelty_stats().  step*, reset, reset_envs, load_state and clone_state keep all three current.  The bonus is one tensor op of the
         learner's: visit_count.float().rsqrt(), or visit_count == 1.  None: the three attributes are None and nothing is added to any call.  Not for
-        batches with config groups."""
+        batches with config groups.
+
+        archive (None or cells, a power of two, 1 024 .. 2^24): the cell archive on the device (rg_archive_update) -- per hashed state the best state record
+        any env has offered, Go-Explore's archive, and archive_restore() the way back into it.  An offer is (key, score, steps): a larger score beats a
+        smaller, at equal scores fewer steps of the running episode beat more, at equal both the lowest env of the call wins and a later call replaces
+        nothing.  `self.archive` carries the table as tensors, per slot `key` int64 [cells] (0 = empty), `score`, `steps`, `seen` (the offers the key
+        ever got), `chosen` (the restores from it), `when` (the update call that last wrote it, from 1) int32 [cells], `records` uint8 [cells, state_bytes],
+        and per env `slot` int32 [N] (-1: the offer was dropped, the table is full there), `stored` bool [N] (this env's record was written by the last
+        update), `score_in`, `steps_in` int32 [N].  cells x state_bytes of device memory: 192 MB at 2^14 cells of the mini config.  With archive_auto
+        (which needs novelty=) every step* offers each env's state behind the novelty pass under its novelty hash with its gold as the score; without,
+        archive_update() is the explicit call.  None: `self.archive` is None and nothing is added to any call.  Not for batches with config groups."""
         import torch
 
         if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
@@ -240,6 +251,7 @@ class HipVecRogueEnv:
             self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
         self._encode()
         self._novelty_setup()  # (behind the first encode: the mirrors are drawn)
+        self._archive_setup(archive, archive_auto)
 
     def _novelty_check(self, what, scope, crop, slots, gslots):
         """The arguments of rg_novelty_enable from the constructor's; the enable itself follows the first encode."""
@@ -301,6 +313,125 @@ class HipVecRogueEnv:
         if self._nov_args is None:
             raise ValueError("novelty_clear needs novelty")
         self._h.check(self._h.L.rg_novelty_clear(self._h.h))
+
+    # ---- the cell archive (rg_archive_*; the rule: csrc/rg_archive.h) ----
+    class Archive:
+        """The archive's tensors (HipVecRogueEnv.archive): views of the library's device arrays, rewritten in place by every update."""
+        __slots__ = ("cells", "key", "score", "steps", "seen", "chosen", "when", "records", "slot", "stored", "score_in", "steps_in")
+
+    def _archive_setup(self, cells, auto):
+        torch = self.torch
+        self.archive, self._arc_auto = None, False
+        if cells is None:
+            return
+        cells = operator.index(cells)
+        if auto and self._nov_args is None:
+            raise ValueError("archive_auto=True needs novelty= (the keys are the novelty hashes); pass archive_auto=False and call archive_update(keys=...)")
+        L, h, n = self._h.L, self._h.h, self.num_envs
+        self._h.check(L.rg_archive_enable(h, cells))
+        a = inner.RgArchiveArrays()
+        self._h.check(L.rg_archive_arrays(h, C.byref(a)))
+        A = self.Archive()
+        A.cells = cells
+        with torch.cuda.device(self.device):
+            def view(ptr, shape, typestr):
+                return torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
+            A.key = view(a.key, (cells,), "<i8")
+            for k in ("score", "steps", "seen", "chosen", "when"):
+                setattr(A, k, view(getattr(a, k), (cells,), "<i4"))
+            A.records = view(a.records, (cells, self.state_bytes), "|u1")
+            A.slot, A.stored = view(a.slot, (n,), "<i4"), view(a.stored, (n,), "|b1")
+            A.score_in, A.steps_in = view(a.score_in, (n,), "<i4"), view(a.steps_in, (n,), "<i4")
+        self.archive, self._arc_auto = A, bool(auto)
+
+    def _archive_need(self, what):
+        if self.archive is None:
+            raise ValueError("%s needs archive=" % what)
+
+    def archive_update(self, keys=None, score=None, mask=None):
+        """Offer every env's present state to the archive (rg_archive_update; asynchronous, no host trip).  keys: int64 device tensor [N], the cells -- None
+        takes `novelty_hash` (needs novelty=); a learner's own keys can be the hash xor a per-seed salt, which keeps the cells of different dungeons apart.
+        score: int32 device tensor [N], larger is better -- None takes the env's gold.  mask: bool / uint8 device tensor [N], the envs that offer -- None:
+        all.  Afterwards archive.slot / archive.stored say where each env's key lives and whose record was written."""
+        torch = self.torch
+        self._archive_need("archive_update")
+        def arg(t, name, dtypes):
+            if t is None:
+                return None, None
+            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (self.num_envs,):
+                raise ValueError("archive_update: %s must be a %s tensor [%d] on %s" % (name, " / ".join(str(d) for d in dtypes), self.num_envs, self.device))
+            t = t.contiguous()
+            return t, C.c_void_p(t.data_ptr())
+        if keys is None and self._nov_args is None:
+            raise ValueError("archive_update: keys=None takes the novelty hash, which needs novelty=")
+        keys, kp = arg(keys, "keys", (torch.int64,))
+        score, sp = arg(score, "score", (torch.int32,))
+        mask, mp = arg(mask, "mask", (torch.bool, torch.uint8))
+        self._h.check(self._h.L.rg_archive_update(self._h.h, kp, sp, mp))
+
+    def archive_sample(self, k, weights="seen", generator=None):
+        """int32 [k] on the device: k occupied slots drawn with replacement -- weights "seen": Go-Explore's 1 / sqrt(seen + 1), "uniform", or a float tensor
+        [cells] of the caller's (empty slots never drawn).  Plain torch ops (one multinomial over the table), not a kernel of the library; it is meant for the
+        few hundred draws between exploration phases, not for every step."""
+        torch = self.torch
+        self._archive_need("archive_sample")
+        A = self.archive
+        occupied = A.key != 0
+        if isinstance(weights, torch.Tensor):
+            if tuple(weights.shape) != (A.cells,) or weights.device != self.device:
+                raise ValueError("archive_sample: a weight tensor must be [%d] on %s" % (A.cells, self.device))
+            w = weights.to(torch.float32)
+        elif weights == "seen":
+            w = (A.seen.to(torch.float32) + 1.0).rsqrt()
+        elif weights == "uniform":
+            w = torch.ones((A.cells,), dtype=torch.float32, device=self.device)
+        else:
+            raise ValueError("archive_sample: weights must be 'seen', 'uniform' or a tensor, got %r" % (weights,))
+        w = torch.where(occupied, w, torch.zeros_like(w))
+        return torch.multinomial(w, operator.index(k), replacement=True, generator=generator).to(torch.int32)
+
+    def archive_restore(self, slots, env_ids=None):
+        """Restore envs env_ids (default: envs 0 .. len(slots)-1 when that is every env) from the records of archive slots `slots` (int32 device tensor, a
+        list or a numpy array; env_ids of the same kind) -- rg_archive_restore: the records go through load_state's own path, `chosen` of each slot taken
+        grows by 1, and an empty slot leaves its env unchanged and makes check_errors() raise.  Then what follows a load: the restored envs start a new
+        episode of visit counts and, with episodes=True, of the accounting (the running one ends with cause 3), and the observations are re-encoded.
+        Returns the observation batch."""
+        torch = self.torch
+        self._archive_need("archive_restore")
+        on_dev = isinstance(slots, torch.Tensor) and slots.device.type == "cuda"
+        if env_ids is not None and (isinstance(env_ids, torch.Tensor) and env_ids.device.type == "cuda") != on_dev:
+            raise ValueError("archive_restore: slots and env_ids must both be device tensors or both be host lists")
+        if on_dev:
+            st = slots.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+            sp, ks = C.c_void_p(st.data_ptr()), int(st.numel())
+        else:
+            st = np.ascontiguousarray(np.asarray(slots.numpy() if isinstance(slots, torch.Tensor) else slots, dtype=np.int64).reshape(-1).astype(np.int32))
+            sp, ks = C.c_void_p(st.ctypes.data), int(st.size)
+        ptr, k, dev_ids, _keep = self._state_ids(env_ids, unique=True)
+        if k != ks:
+            raise ValueError("archive_restore: %d slots for %d envs" % (ks, k))
+        L, h = self._h.L, self._h.h
+        if k:
+            self._h.check(L.rg_archive_restore(h, sp, ptr, k, int(on_dev)))
+            if self._episodes:
+                self._h.check(L.rg_episode_cut(h, ptr, k, dev_ids, None, 1))
+        obs = self._encode()
+        if k:
+            self._novelty_cut(ptr, k, dev_ids)
+        return obs
+
+    def archive_stats(self):
+        """dict of occupied (slots in use), dropped (offers that found the table full), written (records written) and calls (updates).  It waits for the
+        stream.  Needs archive=."""
+        self._archive_need("archive_stats")
+        out = (C.c_uint64 * 4)()
+        self._h.check(self._h.L.rg_archive_stats(self._h.h, out))
+        return dict(zip(inner.ARCHIVE_STATS, (int(v) for v in out)))
+
+    def archive_clear(self):
+        """Empty the archive: the table, the records and the counters of archive_stats().  Needs archive=."""
+        self._archive_need("archive_clear")
+        self._h.check(self._h.L.rg_archive_clear(self._h.h))
 
     _EP_NAMES = ("ep_return", "ep_length", "ep_depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen_bits")
 
@@ -719,6 +850,8 @@ class HipVecRogueEnv:
             self._h.check(self._h.L.rg_episode_update(self._h.h))
         if self._nov_args is not None:  # the visit of the state this step left, behind the observation: the mirrors are drawn
             self._h.check(self._h.L.rg_novelty_update(self._h.h))
+        if self._arc_auto:  # ... and the offer of that state to its cell, under the hash just made
+            self._h.check(self._h.L.rg_archive_update(self._h.h, None, None, None))
         return obs, self.reward, self.done
 
     def step(self, actions):

@@ -49,12 +49,19 @@ class RgNoveltyArrays(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("hash", "count", "gcount")]
 
 
+class RgArchiveArrays(C.Structure):
+    """rg_archive_arrays_t (include/rogue_gym_hip.h): device pointers."""
+    _fields_ = [(k, C.c_void_p) for k in ("key", "score", "steps", "seen", "chosen", "when", "records", "slot", "stored", "score_in", "steps_in")]
+
+
 RG_EP_STATS, RG_EP_SCOUT = 1, 2
 RG_NOV_POS, RG_NOV_SCREEN, RG_NOV_CROP = 1, 2, 3
 RG_NOV_EPISODE, RG_NOV_GLOBAL = 1, 2
 NOVELTY_WHAT = {"pos": RG_NOV_POS, "screen": RG_NOV_SCREEN, "crop": RG_NOV_CROP}
 NOVELTY_SCOPE = {"episode": RG_NOV_EPISODE, "global": RG_NOV_GLOBAL, "both": RG_NOV_EPISODE | RG_NOV_GLOBAL}
 NOVELTY_STATS = ("occupied_global", "dropped_global", "dropped_episode", "calls")   # the words of rg_novelty_stats
+ARCHIVE_STATS = ("occupied", "dropped", "written", "calls")                          # the words of rg_archive_stats
+ARCHIVE_SLOT = [("key", "<u8"), ("score", "<i4"), ("steps", "<u4"), ("seen", "<u4"), ("chosen", "<u4"), ("when", "<u4"), ("zero", "<u4")]  # a slot of rg_archive_offer_host's table
 RG_EP_DIED, RG_EP_TIME_LIMIT, RG_EP_CUT = 1, 2, 3
 RG_MON_SHOWN, RG_MON_ALL, RG_MON_MAX_CAP, RG_MON_COLS = 0, 1, 16, 8
 MONSTER_MODES = {"shown": RG_MON_SHOWN, "all": RG_MON_ALL}
@@ -79,6 +86,7 @@ _INT_FUNCS = (
     "rg_path", "rg_path_host", "rg_route", "rg_route_host",
     "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
     "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host",
+    "rg_archive_enable", "rg_archive_update", "rg_archive_arrays", "rg_archive_restore", "rg_archive_stats", "rg_archive_clear", "rg_archive_offer_host",
     "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
     "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host",
 )
@@ -154,6 +162,9 @@ def load_library():
         "rg_novelty_arrays": [vp, C.POINTER(RgNoveltyArrays)], "rg_novelty_stats": [vp, C.POINTER(C.c_uint64)], "rg_novelty_table_read": [vp, vp, vp, i32, C.POINTER(i32)],
         "rg_novelty_clear": [vp], "rg_novelty_hash_host": [i32, i32, i32, i32, vp, i32, i32, i32, i32, C.POINTER(C.c_uint64)],
         "rg_novelty_finish_host": [C.c_uint64, C.c_uint64], "rg_novelty_insert_host": [vp, i32, u32, C.c_uint64, C.POINTER(u32)],
+        "rg_archive_enable": [vp, i32], "rg_archive_update": [vp, vp, vp, vp], "rg_archive_arrays": [vp, C.POINTER(RgArchiveArrays)],
+        "rg_archive_restore": [vp, vp, vp, i32, i32], "rg_archive_stats": [vp, C.POINTER(C.c_uint64)], "rg_archive_clear": [vp],
+        "rg_archive_offer_host": [vp, i32, C.c_uint64, C.c_int32, u32, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
         "rg_monsters": [vp, u32, i32, vp, vp],
         "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
         "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
@@ -169,6 +180,7 @@ def load_library():
                 "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
                 "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
                 "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host", "rg_novelty_finish_host",
+                "rg_archive_enable", "rg_archive_update", "rg_archive_arrays", "rg_archive_restore", "rg_archive_stats", "rg_archive_clear", "rg_archive_offer_host",
                 "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
                 "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
     for name, argtypes in sig.items():

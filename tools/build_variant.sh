@@ -14,6 +14,6 @@ for u in $UNITS; do
     PIDS="$PIDS $!"; OBJS="$OBJS $obj"
 done
 for p in $PIDS; do wait $p; done   # (a failed compile ends the script: set -e)
-# (the novelty pass is the product's own library beside the variant's directory: csrc/build.sh or __graft_entry__.build() made it)
-hipcc --offload-arch=gfx950 -shared $OBJS -L.. -lrogue_gym_novelty '-Wl,-rpath,$ORIGIN/..' -o ../variants/librogue_$name.so
+# (the novelty pass and the cell archive are the product's own libraries beside the variant's directory: csrc/build.sh or __graft_entry__.build() made them)
+hipcc --offload-arch=gfx950 -shared $OBJS -L.. -lrogue_gym_novelty -lrogue_gym_archive '-Wl,-rpath,$ORIGIN/..' -o ../variants/librogue_$name.so
 echo "built variants/librogue_$name.so"
