@@ -1540,7 +1540,9 @@ __device__ __forceinline__ void bfs_rows_w32(const RgState &S, const RgConfig &c
         }
     }
     const bool up_ok = row > 0, dn_ok = row + 1 < H;
-    const uint32_t wu = ROW16 ? row_shr1(wk) : (up_ok ? wave_shr1(wk) : 0u), wd = ROW16 ? row_shl1(wk) : (dn_ok ? wave_shl1(wk) : 0u);  // (rows >= H hold no walkable cell)
+    // (the whole-wave shifts by every lane, selected afterwards: under `up_ok ? .. : 0u` the lanes of row 0 would sit the move out, and row 1 get nothing from them)
+    const uint32_t wk_up = ROW16 ? row_shr1(wk) : wave_shr1(wk), wk_dn = ROW16 ? row_shl1(wk) : wave_shl1(wk);
+    const uint32_t wu = (ROW16 || up_ok) ? wk_up : 0u, wd = (ROW16 || dn_ok) ? wk_dn : 0u;  // (rows >= H hold no walkable cell)
     uint32_t vis = 0, fr = 0;
     uint32_t inject = (row_ok && row == ty) ? 1u << tx : 0u;  // level 0: the target cell itself, walkable or not
     uint32_t p0 = 0, p1 = 0, p2 = 0, ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1679,10 +1681,14 @@ __device__ __forceinline__ bool bfs_rows_n32(const RgState &S, const RgConfig &c
         }
     }
     const bool up_ok = row > 0, dn_ok = row + 1 < H;
+    // (every shift below is taken by ALL lanes and selected afterwards: `up_ok ? wave_shr1(v) : 0u` runs the DPP move with the lanes of row 0 switched off, and a
+    // move whose SOURCE lane is off delivers nothing -- row 1 never saw row 0's frontier nor its walkable cells, row H - 2 never row H - 1's.  No generated level has
+    // a walkable cell there; a loaded state may: tests/test_gpu_turn_scenarios.py.  Floor::make_dist_map, floor.rs:395-416, knows no such rows.)
 #pragma unroll
     for (int k = 0; k < WN; k++) {
-        wu[k] = up_ok ? wave_shr1(wk[k]) : 0u;   // walkable mask of row y-1
-        wd[k] = dn_ok ? wave_shl1(wk[k]) : 0u;   // and of row y+1
+        const uint32_t from_up = wave_shr1(wk[k]), from_dn = wave_shl1(wk[k]);
+        wu[k] = up_ok ? from_up : 0u;   // walkable mask of row y-1
+        wd[k] = dn_ok ? from_dn : 0u;   // and of row y+1
         if (row_ok && row == ty && (tx >> 5) == k) inject[k] = 1u << (tx & 31);  // level 0: the target cell itself, walkable or not
     }
     uint32_t blk = 0;
@@ -1696,8 +1702,9 @@ __device__ __forceinline__ bool bfs_rows_n32(const RgState &S, const RgConfig &c
             uint32_t fu[WN], fd[WN], au[WN], ad[WN], nw[WN];
 #pragma unroll
             for (int k = 0; k < WN; k++) {
-                fu[k] = up_ok ? wave_shr1(fr[k]) : 0u;
-                fd[k] = dn_ok ? wave_shl1(fr[k]) : 0u;
+                const uint32_t from_up = wave_shr1(fr[k]), from_dn = wave_shl1(fr[k]);
+                fu[k] = up_ok ? from_up : 0u;
+                fd[k] = dn_ok ? from_dn : 0u;
                 au[k] = fu[k] & wk[k]; ad[k] = fd[k] & wk[k];  // neighbour-row frontier whose vertical step lands on a walkable cell of my row
             }
 #pragma unroll
