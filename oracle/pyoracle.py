@@ -412,6 +412,20 @@ class OracleEnv:
         return self._image(self._L.orc_symbol_image, self.symbols, flag, with_hist)
 
 
+def encode_image(kind, screen, status, symbols, flag=0, hist=None):
+    """The oracle's encoders on plain arrays (orc_gray_image / orc_symbol_image: PlayerState::gray_image / symbol_image [_with_hist]) for mirrors that do
+    not come from an OracleEnv: screen u8 [H, W], status 10 words, hist u8 [H, W] or None -> f32 [C, H, W].  kind 0 gray, 1 one-hot."""
+    scr = np.ascontiguousarray(screen, np.uint8)
+    h, w = scr.shape
+    st = np.ascontiguousarray(np.asarray(status, np.int64).astype(np.uint32))
+    hs = None if hist is None else np.ascontiguousarray(np.asarray(hist, np.uint8).reshape(h, w))
+    out = np.empty(((symbols if kind else 1) + bin(flag).count("1") + (hs is not None), h, w), np.float32)
+    L = lib()
+    if (L.orc_symbol_image if kind else L.orc_gray_image)(scr.ctypes.data, h, w, symbols, st.ctypes.data, flag, None if hs is None else hs.ctypes.data, out.ctypes.data):
+        raise RuntimeError("Error in rogue-gym: Invalid tile")
+    return out
+
+
 def kat_edges(xr, yr, direction, inclusive=True):
     """passages::edges on RectRange::from_ranges(xr, yr); direction in ("Up", "Down", "Left", "Right")."""
     xs, ys = (C.c_int * 256)(), (C.c_int * 256)()

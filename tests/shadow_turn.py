@@ -7,7 +7,12 @@ file is another reading, written from the Rust sources function by function (the
 Python model of `actions::process_action` and everything below it.  tests/test_oracle_shadow.py runs it in lock step with the C oracle -- levels come from
 the oracle (the generator is pinned by the reference's goldens), every key is then played by BOTH, and the whole state is compared after every key.
 
+The same object also restates what Python SEES of that state: `draw_screen`, `history` and `status` (RunTime::draw_screen, Floor::history_map,
+RunTime::player_status), the Redraw / StatusUpdated reactions of every key, and `Mirror`, which is PlayerState under GameStateImpl::react: a screen that is
+redrawn only on Redraw and a status that is refreshed only on StatusUpdated -- both lag the state by rule.
+
 Not modelled (out of the hot path's scope): items other than gold, traps, thrown weapons, the inventory."""
+import numpy as np
 
 M32 = 0xFFFFFFFF
 M64 = 0xFFFFFFFFFFFFFFFF
@@ -23,6 +28,8 @@ VISITED, HIDDEN, VISIBLE, DRAWN, LOCKED, DARK = 1, 2, 4, 8, 16, 32
 # EnemyAttr (character/enemies.rs:126-139)
 MEAN, RANDOM, CONFUSED = 0b1, 0b001_000_000_000, 0b010_000_000_000
 INF = 0xFFFFFFFF
+# the Reaction kinds (core/src/lib.rs) the mirrors depend on; Notify and UiTransition are not recorded
+REDRAW, STATUS = "Redraw", "StatusUpdated"
 
 # KeyMap::ai (input.rs:73-100)
 KEYMAP = {"l": ("move", RIGHT), "k": ("move", UP), "j": ("move", DOWN), "h": ("move", LEFT), "u": ("move", RIGHTUP), "y": ("move", LEFTUP),
@@ -113,6 +120,9 @@ class Shadow:
         self.weapon = weapon        # at_weild (times, max), hit_plus, dam_plus of Player::weapon, or None (fight.rs:20-33): the default pack wields a mace 2d4 +1,+1
         self.armor = armor          # Player::arm: def + def_plus of the equipped armor (player.rs:125-132); ring mail 3 + 1
         self.dist_cache = []        # DistCache (rogue/mod.rs:492-518): a VecDeque of (map, coord), lives as long as the Dungeon
+        self.past_floors = []       # Dungeon::past_floors (rogue/mod.rs:199, :476-479), of which only history_map is ever read: one visited map per floor left
+        self.reactions = []         # `out` of the last process_action: the key's REDRAW / STATUS reactions in the order they were pushed
+        self.move_res = []          # `res.0` of the last move_player
 
     # ---- state exchange with the oracle (levels are the oracle's; the turn is played here) --------------------------------------------
     def load_level(self, o):
@@ -141,6 +151,7 @@ class Shadow:
 
     def new_game(self, o):
         self.dist_cache = []
+        self.past_floors = []
         self.load_level(o)
         self.load_player(o)
 
@@ -385,7 +396,11 @@ class Shadow:
         self.food_left -= 1                              # u32: wraps below zero in a release build (App. C-9)
         if self.food_left == 0:
             return                                       # [PlayerEvent::Dead], which after_turn ignores (actions.rs:75)
-        self.heal()                                      # (notify_hungry only reports)
+        hunger = self.hunger_time // 10                  # notify_hungry (player.rs:241-244) -> PlayerEvent::Hungry -> StatusUpdated (actions.rs:76)
+        if self.food_left & M32 in (hunger, hunger * 2):
+            self.reactions.append(STATUS)
+        if self.heal():                                  # PlayerEvent::Healed -> StatusUpdated
+            self.reactions.append(STATUS)
 
     # ---- actions.rs ------------------------------------------------------------------------------------------------------------------
     def after_turn(self):                                # actions.rs:67-119 -> True when the player died
@@ -393,12 +408,16 @@ class Shadow:
         attacks = self.move_actives()
         if attacks:
             self.quiet = 0                               # player.buttle()
+        did_hit = False
         for enemy in attacks:
             hp = self.fight_enemy_attack(enemy)
             if hp is not None:
+                did_hit = True
                 self.hp = max(self.hp - hp, 0)           # Player::get_damage (player.rs:177-184)
                 if self.hp == 0:
-                    return True
+                    return True                          # (the Grave transition; no StatusUpdated is pushed behind it, actions.rs:100-104)
+        if did_hit:
+            self.reactions.append(STATUS)                # actions.rs:115-117
         return False
 
     def player_attack(self, place):                      # actions.rs:140-166
@@ -411,13 +430,16 @@ class Shadow:
             if cur <= hp:
                 self.placed.pop(place, None)
                 self.active.pop(place, None)
-                self.level_up(enemy.exp)
+                if self.level_up(enemy.exp):             # actions.rs:154-158: StatusUpdated only for a new level, Redraw for every kill
+                    self.move_res.append(STATUS)
+                self.move_res.append(REDRAW)
             else:
                 enemy.hp = hp - cur                      # (sic) damage - cur
 
-    def move_player(self, d):                            # actions.rs:168-194 -> done
+    def move_player(self, d):                            # actions.rs:168-194 -> done; its reactions in self.move_res
+        self.move_res = []
         if not self.can_move_impl(self.pos, d, False):
-            return True
+            return True                                  # (Notify(CantMove) alone)
         new_pos = (self.pos[0] + DIRS[d][0], self.pos[1] + DIRS[d][1])
         if new_pos in self.placed or new_pos in self.active:
             self.player_attack(new_pos)
@@ -425,9 +447,11 @@ class Shadow:
         self.player_out(self.pos)                        # Dungeon::move_player (rogue/mod.rs:237-258)
         self.player_in(new_pos, False)
         self.pos = new_pos
+        self.move_res.append(REDRAW)                     # actions.rs:188
         i = self.idx(*new_pos)
         if i in self.items:                              # get_item (actions.rs:206-231): gold merges into the pack's gold; Floor::remove_obj always finds the
             self.gold += self.items.pop(i)               # cell filled (the player stands on it), so the item is removed
+            self.move_res.append(STATUS)                 # actions.rs:189-192
             return True
         return False
 
@@ -454,24 +478,122 @@ class Shadow:
         assert not self.dead, "IgnoredInput: the Grave modal takes no action (core/src/lib.rs:301-315)"
         act, d = KEYMAP[key]
         ui_dead, grave = False, False     # `ui`: the LAST after_turn's result; `grave`: a Reaction::UiTransition(Grave) was pushed by ANY of them
+        out = self.reactions = []         # `out` (actions.rs:24): after_turn pushes into it; a NoOp returns it empty (:62)
         if act == "downstair":
             if self.surface[self.idx(*self.pos)] == STAIR:
+                self.past_floors.append(self.history_map())   # Dungeon::new_level_ keeps the floor that is left (rogue/mod.rs:476-479)
                 new_level()
+                out += [REDRAW, STATUS]                       # actions.rs:31
             ui_dead = grave = self.after_turn()
         elif act == "move":
             self.move_player(d)
+            out += self.move_res
             ui_dead = grave = self.after_turn()
         elif act == "run":
-            while True:
+            while True:                              # actions.rs:44-57: the first iteration's reactions, every after_turn's, and the stopping iteration's
                 done = self.move_player(d)
                 tile = self.tile_under_player()
                 if done or tile not in ".#":
+                    out += self.move_res
                     break
+                elif not out:
+                    out += self.move_res
                 ui_dead = self.after_turn()          # a run goes on after the player's death: a later turn without a hit leaves `ui` = None again,
                 grave = grave or ui_dead             # but the Grave reaction stays in the key's reaction list
         elif act == "search":
             self.search()
+            out.append(REDRAW)                       # actions.rs:197-204
             ui_dead = grave = self.after_turn()
         if ui_dead:
             self.dead = True                         # RunTime::ui = Mordal(Grave) (core/src/lib.rs:316-318)
         return grave                                 # GameStateImpl::react: is_terminal = a Grave transition among the reactions || steps >= max_steps (state_impls.rs:56-78)
+
+    # ---- what Python sees: RunTime::draw_screen, Floor::history_map, RunTime::player_status ---------------------------------------------
+    def in_same_room(self, a, b):                        # Floor::in_same_room (floor.rs:381-393)
+        rid = self.room_of(a)
+        if rid is None or self.room_of(b) != rid:
+            return False
+        room = self.rooms[rid]
+        if room["kind"] == 2:                            # Room::range (rooms.rs:84-90): Normal and Maze have one, an Empty room has none -> unwrap_or(true)
+            return True
+        x0, y0, x1, y1 = room["range"]
+        return (x0 <= a[0] < x1 and y0 <= a[1] < y1) == (x0 <= b[0] < x1 and y0 <= b[1] < y1)
+
+    def draw_enemy(self, enemy):                         # rogue/mod.rs:398-404; Coord::is_adjacent (coord.rs:92-94): euc_dist_squared <= 2
+        dx, dy = self.pos[0] - enemy[0], self.pos[1] - enemy[1]
+        return dx * dx + dy * dy <= 2 or self.in_same_room(self.pos, enemy)
+
+    def obj_visible(self, attr):                         # Cell::is_obj_visible (field.rs:38-40)
+        return bool(attr & (VISIBLE | DRAWN))
+
+    def draw_rows(self):                                 # Field::size_ytrimed (field.rs:145-147) and draw_ranges' 1..height - 1 (rogue/mod.rs:291-300)
+        return range(1, self.H - 1)
+
+    def object_at(self, p):
+        """The tile RunTime::draw_screen's closure draws for one path of draw_ranges (core/src/lib.rs:270-284), or None: the player, else the item, else the
+        enemy -- a cell with an item never shows its enemy, drawn or not."""
+        if p == self.pos:
+            return "@"
+        if self.idx(*p) in self.items:
+            return "*"                                   # Item::tile of gold (item/mod.rs:60)
+        m = self.placed.get(p) or self.active.get(p)     # EnemyHandler::get_enemy (enemies.rs:330-335)
+        if m is not None and self.draw_enemy(p):
+            return m.glyph
+        return None
+
+    def draw_screen(self):
+        """RunTime::draw_screen (core/src/lib.rs:264-285) into PlayerState::new's map of blanks (python/src/lib.rs:41-51) -> u8 [H * W].  Dungeon::draw
+        (rogue/mod.rs:278-290) writes Cell::tile (field.rs:91-98) of rows 1 .. H - 2, so rows 0 and H - 1 stay blank for ever; then the objects of draw_ranges.
+        The objects are few: instead of filtering every cell of draw_ranges, each object's own cell is tested for being in it."""
+        W = self.W
+        out = np.full(W * self.H, 32, np.uint8)
+        rows = self.draw_rows()
+        tiles = np.frombuffer(TILES.encode(), np.uint8)[np.asarray(self.surface)]
+        vis = (np.asarray(self.attr) & VISIBLE) != 0
+        lo, hi = rows[0] * W, (rows[-1] + 1) * W
+        out[lo:hi] = np.where(vis[lo:hi], tiles[lo:hi], 32)
+        for p in [self.pos] + [(i % W, i // W) for i in self.items] + list(self.placed) + list(self.active):
+            if p[1] in rows and self.obj_visible(self.attr[self.idx(*p)]):
+                t = self.object_at(p)
+                if t is not None:
+                    out[self.idx(*p)] = ord(t)
+        return out
+
+    def history_map(self):                               # Floor::history_map (floor.rs:372-379): IS_VISITED of every cell, rows 0 and H - 1 included
+        return ((np.asarray(self.attr) & VISITED) != 0).astype(np.uint8)
+
+    def history(self, level):                            # Dungeon::get_history (rogue/mod.rs:329-338) for the level a Status names
+        if level == self.level:
+            return self.history_map()
+        if 1 <= level <= len(self.past_floors):
+            return self.past_floors[level - 1]
+        return None
+
+    def status(self):
+        """RunTime::player_status (core/src/lib.rs:345-356) + Player::fill_status (player.rs:107-118) in the mirror's word order: dungeon_level, gold, hp, hp max,
+        strength, strength max, defense (never filled: 0), player_level, exp, hunger_level (Normal 0, Hungry 1, Weak 2)."""
+        hunger = self.hunger_time // 10
+        food = self.food_left & M32
+        return [self.level, self.gold, self.hp, self.hp_max, PLAYER_STRENGTH, PLAYER_STRENGTH, 0, self.plevel, self.exp, 2 if food <= hunger else (1 if food <= hunger * 2 else 0)]
+
+
+class Mirror:
+    """PlayerState (python/src/lib.rs:30-68) as GameStateImpl keeps it (python/src/state_impls.rs:51-79): screen and history change only on a Redraw, the status
+    only on a StatusUpdated, in the order the key's reactions come.  The history is that of the level the MIRROR's status names (draw_map, lib.rs:59-60): after a
+    descent, whose reactions are Redraw then StatusUpdated, it is the floor that was left, until the next Redraw."""
+
+    def __init__(self, sh, status=None):                 # PlayerState::reset (lib.rs:52-58): the status, then draw_map
+        self.status = sh.status() if status is None else [int(v) for v in status]
+        self.redraw(sh)
+
+    def redraw(self, sh):
+        self.hist = sh.history(self.status[0])
+        assert self.hist is not None, "runtime.history(..).unwrap()"
+        self.screen = sh.draw_screen()
+
+    def react(self, sh, reactions=None):
+        for r in sh.reactions if reactions is None else reactions:
+            if r == REDRAW:
+                self.redraw(sh)
+            elif r == STATUS:
+                self.status = sh.status()

@@ -152,6 +152,7 @@ class State:
         s.rng_dungeon, s.rng_enemy, s.rng_item_words = st.Rng(self.rng[0:4]), st.Rng(self.rng[8:12]), list(self.rng[4:8])
         s.hp, s.hp_max, s.exp, s.plevel, s.food_left, s.quiet, s.gold, s.dead = self.hp, self.hp_max, self.exp, self.plevel, self.food, self.quiet, self.pack_gold, False
         s.dist_cache = []
+        s.mirror = st.Mirror(s, self.status())   # what fill_record puts into the record: these status words and a pending Redraw, drawn here
         return s
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle.pyoracle import OracleEnv
-from shadow_turn import KEYMAP, Shadow
+from shadow_turn import KEYMAP, Mirror, Shadow
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_KEYS = "hjklyubnhjklyubnHJKLYUBN.s>"
@@ -62,6 +62,7 @@ def run_differential(cfg, seeds, steps, max_steps, policy, rng, weapon=(2, 4, 1,
         o = OracleEnv(cfg, max_steps=max_steps, seed=seed)
         sh = Shadow(o.w, o.h, cfg.get("player", {}).get("hunger_time", 1300), d.get("passage_unlock_rate_inv", 3), d.get("door_unlock_rate_inv", 5), weapon, armor)
         sh.new_game(o)
+        mirror = Mirror(sh)
         episode, n_steps, stuck = [], 0, [0]
         for t in range(steps):
             key = policy(o, rng, stuck)
@@ -74,7 +75,7 @@ def run_differential(cfg, seeds, steps, max_steps, policy, rng, weapon=(2, 4, 1,
                 sh.load_level(twin)
                 if stats is not None:
                     stats["descents"] = stats.get("descents", 0) + 1
-            lvl0, plv0 = sh.plevel, sh.level
+            lvl0, plv0, floors0 = sh.plevel, sh.level, len(sh.past_floors)
             died = sh.process_action(key, new_level)
             o.react(key)
             episode.append(key)
@@ -97,10 +98,22 @@ def run_differential(cfg, seeds, steps, max_steps, policy, rng, weapon=(2, 4, 1,
                 assert sh.surface == [int(v) for v in surf.reshape(-1)], where + ": surface"
                 assert sh.attr == [int(v) for v in attr.reshape(-1)], where + ": attr"
                 assert sh.items == {i: int(v) for i, v in enumerate(gold.reshape(-1)) if v >= 0}, where + ": items"
+            # what Python sees: the Shadow's draw, history and status under its own reaction list against the oracle's mirrors (stale by rule, both)
+            mirror.react(sh)
+            assert np.array_equal(mirror.screen, o.screen().reshape(-1)), "%s: screen (reactions %s)\nShadow:\n%s\noracle:\n%s" % (
+                where, sh.reactions, "\n".join(bytes(r).decode() for r in mirror.screen.reshape(o.h, o.w)), "\n".join(o.dungeon()))
+            assert np.array_equal(mirror.hist, o.hist().reshape(-1)), "%s: history (reactions %s)" % (where, sh.reactions)
+            assert [v & M32 for v in mirror.status] == [int(v) for v in o.status_arr()], "%s: status %s, the oracle's %s (reactions %s)" % (where, mirror.status, o.status_arr(), sh.reactions)
+            if stats is not None:
+                stats["stale_screens"] = stats.get("stale_screens", 0) + int(not np.array_equal(mirror.screen, sh.draw_screen()))
+                stats["stale_status"] = stats.get("stale_status", 0) + int(mirror.status != sh.status())
+                if len(sh.past_floors) > floors0:   # a descent's Redraw comes before its StatusUpdated: the history drawn is the floor's that was left
+                    stats["past_hist"] = stats.get("past_hist", 0) + int(np.array_equal(mirror.hist, sh.past_floors[-1]) and not np.array_equal(mirror.hist, sh.history_map()))
             assert o.flags()["is_terminal"] == (died or n_steps >= max_steps), where
             if o.flags()["is_terminal"]:
                 o.reset()
                 sh.new_game(o)
+                mirror = Mirror(sh)
                 episode, n_steps = [], 0
     return played
 
@@ -133,6 +146,9 @@ def test_turn_matches_the_second_restatement(cfgs):
     n += run_differential(default, range(300, 306), 400, 400, mixed_policy, rng, grid_every=4, stats=stats)
     assert n >= 37000
     assert stats["descents"] >= 30 and stats["level_ups"] >= 10 and stats["deaths"] >= 20, stats
+    # the mirrors were compared while they lagged the state: a screen older than the state, a status older than the player, a history of the floor that was left
+    print(stats)
+    assert stats["stale_screens"] >= 100 and stats["stale_status"] >= 100 and stats["past_hist"] >= 30, stats
 
 
 @pytest.mark.parametrize("k", [34, 36, 37, 38, 39, 40, 43, 46, 48, 50, 51, 56, 58, 62, 63, 64, 65])
