@@ -149,30 +149,12 @@ class HipVecRogueEnv:
         archive_update() is the explicit call.  None: `self.archive` is None and nothing is added to any call.  Not for batches with config groups."""
         import torch
 
-        if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError("obs_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (obs_dtype,))
-        typed16 = obs_dtype in (torch.float16, torch.bfloat16)
-        if symbol_ids:
-            if image_setting.dungeon != DungeonType.SYMBOL or image_setting.status.value != 0 or obs_dtype is not None:
-                raise ValueError("symbol_ids=True needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype=None (the ids are uint8), got %s, status %r, obs_dtype %r"
-                                 % (image_setting.dungeon, image_setting.status, obs_dtype))
-        if (typed16 or symbol_ids) and (crop is not None or persistent_obs):
-            raise ValueError("%s cannot be combined with %s: the crop and the bound observation tensor are float32 only"
-                             % ("symbol_ids=True" if symbol_ids else "obs_dtype=%s" % (obs_dtype,), "crop" if crop is not None else "persistent_obs=True"))
-
-        if guide is not None and (not isinstance(guide, str) or (guide not in inner.PATH_GOALS and guide != "explore")):
-            raise ValueError("guide must be None or one of %s, 'explore', got %r" % (", ".join(repr(g) for g in inner.PATH_GOALS), guide))
-        if guide_secrets and guide is None:
-            raise ValueError("guide_secrets=True needs a guide")
-
-        if crop is not None:
-            if persistent_obs:
-                raise ValueError("crop and persistent_obs cannot be combined: the bound observation tensor is the whole screen")
-            crop = self._crop_radii(crop)
-        self.crop = crop
-        self._views = []
-
         self.torch = torch
+        self._views = []       # the crop views (add_crop): what _refresh_views encodes first, in this order
+        self._refresh = []     # ... and then calls: the refresh call of each optional feature, registered by its _setup_* in the order they run below
+        self._after_step = []  # what _step_keys calls behind the step's observation: the episode, novelty and archive updates, registered the same way
+        self._scratch = {}
+        self._draw = 0  # sample_keys: the draw counter of calls that give none
         cfgs = [d if isinstance(d, str) else json.dumps(d) for d in config_dicts]
         self._h = inner._Handle(cfgs, max_steps, auto_reset=True, device=device)
         self.device = torch.device("cuda", self._h.device)
@@ -180,83 +162,161 @@ class HipVecRogueEnv:
         self.image_setting = image_setting
         self.symbols = self._h.symbols
         self.height, self.width = self._h.height, self._h.width
-        L, h = self._h.L, self._h.h
+        L, h, n = self._h.L, self._h.h, self.num_envs
         with torch.cuda.device(self.device):
             self._h.check(L.rg_set_stream(h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
             self._action_keys = torch.tensor([ord(a) for a in self.ACTIONS], dtype=torch.uint8, device=self.device)
-            self._sym = image_setting.dungeon == DungeonType.SYMBOL
-            self.channels = L.rg_obs_channels(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist))
-            # (kind, RG_OBS_* dtype) of rg_obs_typed, or None: the f32 calls
-            self._typed = (2, 3) if symbol_ids else (int(self._sym), 1 if obs_dtype == torch.float16 else 2) if typed16 else None
-            if symbol_ids:
-                self.channels = 1 + int(image_setting.includes_hist)
-            oh, ow = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
-            self.obs = torch.empty((self.num_envs, self.channels, oh, ow), dtype=torch.uint8 if symbol_ids else obs_dtype if typed16 else torch.float32,
-                                   device=self.device)
-            self.crop_center = None if crop is None else torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
-            p = C.c_void_p()
-            self._h.check(L.rg_reward(h, C.byref(p)))
-            self.reward = torch.as_tensor(_DevArray(p.value, (self.num_envs,), "<f4"), device=self.device)
-            self._h.check(L.rg_done(h, C.byref(p)))
-            self.done = torch.as_tensor(_DevArray(p.value, (self.num_envs,), "|b1"), device=self.device)
-            self._h.check(L.rg_flags(h, C.byref(p)))
-            self.flags = torch.as_tensor(_DevArray(p.value, (self.num_envs,), "<i4"), device=self.device)
-            self._h.check(L.rg_status(h, C.byref(p)))
-            self.status = torch.as_tensor(_DevArray(p.value, (self.num_envs, 10), "<i4"), device=self.device)
-            self._screen = None
-            if crop is None:  # (with a crop the batch may mix screen sizes: no screen tensor then, `screen` raises)
-                self._screen_view()
-        self._scratch = {}
-        self._draw = 0  # sample_keys: the draw counter of calls that give none
-        self._mask_u8 = torch.zeros((self.num_envs, len(self.ACTIONS)), dtype=torch.uint8, device=self.device) if action_mask else None
-        self.action_mask = None if self._mask_u8 is None else self._mask_u8.view(torch.bool)
-        self.guide = guide
-        self._guide_goals = 0 if guide is None or guide == "explore" or guide_secrets else inner.PATH_GOALS[guide]  # rg_path's goals, 0 = rg_path is not called
-        # (goals, fallback_goals, mode) of rg_route, None = rg_route is not called
-        self._guide_route = inner._route_args(*inner.EXPLORE) if guide == "explore" else inner._route_args(guide, None, True, False) if guide_secrets else None
-        self.guide_secrets = bool(guide_secrets)
-        self.guide_tier = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device) if guide == "explore" else None
-        self.guide_keys = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
-        self.guide_dist = None if guide is None else torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
-        self._mon_args = None if monsters is None else inner._monster_args(monsters, monster_cap)  # (mode, cap) of rg_monsters, None = it is not called
+        self._setup_obs(crop, obs_dtype, symbol_ids, persistent_obs)
+        p = C.c_void_p()
+        for name, get, shape, typestr in (("reward", L.rg_reward, (n,), "<f4"), ("done", L.rg_done, (n,), "|b1"), ("flags", L.rg_flags, (n,), "<i4"), ("status", L.rg_status, (n, 10), "<i4")):
+            self._h.check(get(h, C.byref(p)))
+            setattr(self, name, self._dev_view(p.value, shape, typestr))
+        self._screen = None
+        if self.crop is None:  # (with a crop the batch may mix screen sizes: no screen tensor then, `screen` raises)
+            self._screen_view()
+        self._setup_pixels(pixels, pixel_crop, tileset)
+        self._setup_action_mask(action_mask)
+        self._setup_guide(guide, guide_secrets)
+        self._setup_monsters(monsters, monster_cap)
+        self._setup_objects(objects, object_kinds, object_secrets, object_cap)
+        self._setup_episodes(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
+        if self.persistent_obs:
+            self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
+        self._encode()
+        self._setup_novelty(novelty, novelty_scope, novelty_crop, novelty_slots, novelty_global_slots)  # (behind the first encode: the mirrors are drawn)
+        self._setup_archive(archive, archive_auto)
+
+    # ---- what the argument checks share ----
+    def _dev_view(self, ptr, shape, typestr):
+        """A tensor over a device array that the library owns (zero-copy); None for a null pointer: the handle has no such array."""
+        if not ptr:
+            return None
+        with self.torch.cuda.device(self.device):
+            return self.torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
+
+    def _dev_arg(self, call, name, t, dtypes, shape, contiguous=False):
+        """The argument `name` of `call`, checked: a tensor of one of `dtypes` and of `shape` on this env's device.  contiguous=True (a tensor to write into)
+        demands a contiguous one; otherwise the contiguous form of `t` is returned."""
+        torch = self.torch
+        if (not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != tuple(shape)
+                or (contiguous and not t.is_contiguous())):
+            raise ValueError("%s: %s must be a %s%s tensor %s on %s, got %s" % (
+                call, name, "contiguous " if contiguous else "", " / ".join(str(d).replace("torch.", "") for d in dtypes), list(shape), self.device,
+                "%s %s on %s" % (list(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+        return t if contiguous else t.contiguous()
+
+    def _obs_call(self, st, obs_dtype, symbol_ids):
+        """((kind, RG_OBS_* dtype) of the typed observation calls -- dtype 0 is f32 --, channels, torch dtype) of an image of setting `st` with the obs_dtype and
+        symbol_ids of the constructor or of add_crop."""
+        torch = self.torch
+        if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("obs_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (obs_dtype,))
+        sym = st.dungeon == DungeonType.SYMBOL
+        if symbol_ids:
+            if not sym or st.status.value != 0 or obs_dtype is not None:
+                raise ValueError("symbol_ids=True needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype=None (the ids are uint8), got %s, status %r, obs_dtype %r"
+                                 % (st.dungeon, st.status, obs_dtype))
+            return (2, 3), 1 + int(st.includes_hist), torch.uint8
+        call = (int(sym), 1 if obs_dtype == torch.float16 else 2 if obs_dtype == torch.bfloat16 else 0)
+        channels = self._h.L.rg_obs_channels(self._h.h, int(sym), st.status.value, int(st.includes_hist))
+        return call, channels, torch.float32 if obs_dtype is None else obs_dtype
+
+    # ---- the optional features: each checks its arguments, makes its tensors and registers its refresh call in one place ----
+    def _setup_obs(self, crop, obs_dtype, symbol_ids, persistent_obs):
+        """`obs` and `crop_center`; _encode_obs and _step_keys keep them current."""
+        torch, st = self.torch, self.image_setting
+        self._sym = st.dungeon == DungeonType.SYMBOL
+        call, self.channels, dtype = self._obs_call(st, obs_dtype, symbol_ids)
+        if call[1] and (crop is not None or persistent_obs):
+            raise ValueError("%s cannot be combined with %s: the crop and the bound observation tensor are float32 only"
+                             % ("symbol_ids=True" if symbol_ids else "obs_dtype=%s" % (obs_dtype,), "crop" if crop is not None else "persistent_obs=True"))
+        if crop is not None and persistent_obs:
+            raise ValueError("crop and persistent_obs cannot be combined: the bound observation tensor is the whole screen")
+        self.crop = None if crop is None else self._crop_radii(crop)
+        self.persistent_obs = bool(persistent_obs)
+        self._typed = call if call[1] else None  # (kind, RG_OBS_* dtype) of rg_obs_typed, or None: the f32 calls
+        oh, ow = (self.height, self.width) if self.crop is None else (2 * self.crop[0] + 1, 2 * self.crop[1] + 1)
         with torch.cuda.device(self.device):
-            self.monsters = None if monsters is None else torch.zeros((self.num_envs, self._mon_args[1], len(self.MONSTER_COLS)), dtype=torch.int16, device=self.device)
-            self.threat = None if monsters is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
-        if objects is not None and (not isinstance(objects, str) or objects not in ("known", "all")):
-            raise ValueError("objects must be None, 'known' or 'all', got %r" % (objects,))
-        # (kinds, mode, cap) of rg_objects, None = it is not called
-        self._obj_args = None if objects is None else inner._object_args(object_kinds, objects == "known", bool(object_secrets), object_cap)
-        with torch.cuda.device(self.device):
-            self.objects = None if objects is None else torch.zeros((self.num_envs, self._obj_args[2], len(self.OBJECT_COLS)), dtype=torch.int16, device=self.device)
-            self.object_count = None if objects is None else torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+            self.obs = torch.empty((self.num_envs, self.channels, oh, ow), dtype=dtype, device=self.device)
+            self.crop_center = None if self.crop is None else torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
+
+    def _setup_pixels(self, pixels, pixel_crop, tileset):
+        torch = self.torch
         if pixels not in (None, "gray", "rgb"):
             raise ValueError("pixels must be None, 'gray' or 'rgb', got %r" % (pixels,))
         if pixels is None and pixel_crop is not None:
             raise ValueError("pixel_crop needs pixels='gray' or 'rgb'")
-        self._px_crop = None if pixel_crop is None else self._crop_radii(pixel_crop)
-        self._px_channels = 0 if pixels is None else 3 if pixels == "rgb" else 1
         self.tileset = None
         self.pixels = self.pixel_center = None
         if tileset is not None or pixels is not None:
             self.set_tileset(tileset)
-        if pixels is not None:
-            self.pixels = self._pixel_tensor(self.num_envs, self._px_channels, self._px_crop)
-            if self._px_crop is not None:
-                with torch.cuda.device(self.device):
-                    self.pixel_center = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
-        self._episode_setup(bool(episodes) or bool(scout) or int(episode_log) > 0, bool(scout), int(episode_log))
-        self._novelty_check(novelty, novelty_scope, novelty_crop, novelty_slots, novelty_global_slots)
-        self.persistent_obs = bool(persistent_obs)
-        if self.persistent_obs:
-            self._h.check(L.rg_obs_bind(h, int(self._sym), image_setting.status.value, int(image_setting.includes_hist), C.c_void_p(self.obs.data_ptr())))
-        self._encode()
-        self._novelty_setup()  # (behind the first encode: the mirrors are drawn)
-        self._archive_setup(archive, archive_auto)
+        if pixels is None:
+            return
+        crop = None if pixel_crop is None else self._crop_radii(pixel_crop)
+        channels = 3 if pixels == "rgb" else 1
+        self.pixels = self._pixel_tensor(self.num_envs, channels, crop)
+        if crop is not None:
+            with torch.cuda.device(self.device):
+                self.pixel_center = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
+        self._refresh.append(lambda: self._pixel_call(channels, crop, self.pixels, self.pixel_center))
 
-    def _novelty_check(self, what, scope, crop, slots, gslots):
-        """The arguments of rg_novelty_enable from the constructor's; the enable itself follows the first encode."""
+    def _setup_action_mask(self, on):
+        torch, hd = self.torch, self._h
+        self._mask_u8 = torch.zeros((self.num_envs, len(self.ACTIONS)), dtype=torch.uint8, device=self.device) if on else None  # (sample_keys writes it too)
+        self.action_mask = None if self._mask_u8 is None else self._mask_u8.view(torch.bool)
+        if on:
+            self._refresh.append(lambda: hd.check(hd.L.rg_action_mask(hd.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0)))
+
+    def _setup_guide(self, guide, secrets):
+        torch, hd = self.torch, self._h
+        if guide is not None and (not isinstance(guide, str) or (guide not in inner.PATH_GOALS and guide != "explore")):
+            raise ValueError("guide must be None or one of %s, 'explore', got %r" % (", ".join(repr(g) for g in inner.PATH_GOALS), guide))
+        if secrets and guide is None:
+            raise ValueError("guide_secrets=True needs a guide")
+        self.guide, self.guide_secrets = guide, bool(secrets)
+        self.guide_keys = self.guide_dist = self.guide_tier = None
+        if guide is None:
+            return
+        self.guide_keys = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
+        self.guide_dist = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+        if guide == "explore" or secrets:  # rg_route in place of rg_path
+            goals, fb, mode = inner._route_args(*inner.EXPLORE) if guide == "explore" else inner._route_args(guide, None, True, False)
+            if guide == "explore":
+                self.guide_tier = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
+            self._refresh.append(lambda: hd.check(hd.L.rg_route(hd.h, goals, fb, mode, None, C.c_void_p(self.guide_dist.data_ptr()), C.c_void_p(self.guide_keys.data_ptr()),
+                                                                None if self.guide_tier is None else C.c_void_p(self.guide_tier.data_ptr()))))
+        else:
+            goals = inner.PATH_GOALS[guide]
+            self._refresh.append(lambda: hd.check(hd.L.rg_path(hd.h, goals, None, None, C.c_void_p(self.guide_dist.data_ptr()), C.c_void_p(self.guide_keys.data_ptr()))))
+
+    def _setup_monsters(self, monsters, cap):
+        torch, hd = self.torch, self._h
+        self.monsters = self.threat = None
+        if monsters is None:
+            return
+        mode, cap = inner._monster_args(monsters, cap)
+        with torch.cuda.device(self.device):
+            self.monsters = torch.zeros((self.num_envs, cap, len(self.MONSTER_COLS)), dtype=torch.int16, device=self.device)
+            self.threat = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        self._refresh.append(lambda: hd.check(hd.L.rg_monsters(hd.h, mode, cap, C.c_void_p(self.monsters.data_ptr()), C.c_void_p(self.threat.data_ptr()))))
+
+    def _setup_objects(self, objects, kinds, secrets, cap):
+        torch, hd = self.torch, self._h
+        self.objects = self.object_count = None
+        if objects is None:
+            return
+        if not isinstance(objects, str) or objects not in ("known", "all"):
+            raise ValueError("objects must be None, 'known' or 'all', got %r" % (objects,))
+        kw, mode, cap = inner._object_args(kinds, objects == "known", bool(secrets), cap)
+        with torch.cuda.device(self.device):
+            self.objects = torch.zeros((self.num_envs, cap, len(self.OBJECT_COLS)), dtype=torch.int16, device=self.device)
+            self.object_count = torch.zeros((self.num_envs, 4), dtype=torch.int32, device=self.device)
+        self._refresh.append(lambda: hd.check(hd.L.rg_objects(hd.h, kw, mode, cap, C.c_void_p(self.objects.data_ptr()), C.c_void_p(self.object_count.data_ptr()))))
+
+    def _setup_novelty(self, what, scope, crop, slots, gslots):
+        hd, n = self._h, self.num_envs
         self.novelty, self.novelty_hash, self.visit_count, self.visit_count_global = what, None, None, None
-        self._nov_args = None
+        self._nov_args = None  # the arguments of rg_novelty_enable, None = no novelty
         if what is None:
             if crop is not None:
                 raise ValueError("novelty_crop needs novelty='crop'")
@@ -268,20 +328,13 @@ class HipVecRogueEnv:
         if (what == "crop") != (crop is not None):
             raise ValueError("novelty_crop goes with novelty='crop' and only with it, got novelty=%r, novelty_crop=%r" % (what, crop))
         ry, rx = (0, 0) if crop is None else self._crop_radii(crop)
-        self._nov_args = (inner.NOVELTY_WHAT[what], inner.NOVELTY_SCOPE[scope], ry, rx, operator.index(slots), operator.index(gslots))
-
-    def _novelty_setup(self):
-        if self._nov_args is None:
-            return
-        torch = self.torch
-        L, h, n = self._h.L, self._h.h, self.num_envs
-        self._h.check(L.rg_novelty_enable(h, *self._nov_args))
+        args = (inner.NOVELTY_WHAT[what], inner.NOVELTY_SCOPE[scope], ry, rx, operator.index(slots), operator.index(gslots))
+        hd.check(hd.L.rg_novelty_enable(hd.h, *args))
+        self._nov_args = args
         a = inner.RgNoveltyArrays()
-        self._h.check(L.rg_novelty_arrays(h, C.byref(a)))
-        with torch.cuda.device(self.device):
-            def view(ptr, typestr):
-                return None if not ptr else torch.as_tensor(_DevArray(ptr, (n,), typestr), device=self.device)
-            self.novelty_hash, self.visit_count, self.visit_count_global = view(a.hash, "<i8"), view(a.count, "<i4"), view(a.gcount, "<i4")
+        hd.check(hd.L.rg_novelty_arrays(hd.h, C.byref(a)))
+        self.novelty_hash, self.visit_count, self.visit_count_global = (self._dev_view(ptr, (n,), t) for ptr, t in ((a.hash, "<i8"), (a.count, "<i4"), (a.gcount, "<i4")))
+        self._after_step.append(lambda: hd.check(hd.L.rg_novelty_update(hd.h)))  # the visit of the state a step left, behind its observation: the mirrors are drawn
 
     def _novelty_cut(self, ptr=None, k=0, on_dev=0, mask=None):
         """The envs a reset or a load replaced (a list, a mask, or every env) start a new episode and count the state they show now."""
@@ -319,30 +372,28 @@ class HipVecRogueEnv:
         """The archive's tensors (HipVecRogueEnv.archive): views of the library's device arrays, rewritten in place by every update."""
         __slots__ = ("cells", "key", "score", "steps", "seen", "chosen", "when", "records", "slot", "stored", "score_in", "steps_in")
 
-    def _archive_setup(self, cells, auto):
-        torch = self.torch
-        self.archive, self._arc_auto = None, False
+    def _setup_archive(self, cells, auto):
+        hd, n, view = self._h, self.num_envs, self._dev_view
+        self.archive = None
         if cells is None:
             return
         cells = operator.index(cells)
         if auto and self._nov_args is None:
             raise ValueError("archive_auto=True needs novelty= (the keys are the novelty hashes); pass archive_auto=False and call archive_update(keys=...)")
-        L, h, n = self._h.L, self._h.h, self.num_envs
-        self._h.check(L.rg_archive_enable(h, cells))
+        hd.check(hd.L.rg_archive_enable(hd.h, cells))
         a = inner.RgArchiveArrays()
-        self._h.check(L.rg_archive_arrays(h, C.byref(a)))
+        hd.check(hd.L.rg_archive_arrays(hd.h, C.byref(a)))
         A = self.Archive()
         A.cells = cells
-        with torch.cuda.device(self.device):
-            def view(ptr, shape, typestr):
-                return torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
-            A.key = view(a.key, (cells,), "<i8")
-            for k in ("score", "steps", "seen", "chosen", "when"):
-                setattr(A, k, view(getattr(a, k), (cells,), "<i4"))
-            A.records = view(a.records, (cells, self.state_bytes), "|u1")
-            A.slot, A.stored = view(a.slot, (n,), "<i4"), view(a.stored, (n,), "|b1")
-            A.score_in, A.steps_in = view(a.score_in, (n,), "<i4"), view(a.steps_in, (n,), "<i4")
-        self.archive, self._arc_auto = A, bool(auto)
+        A.key = view(a.key, (cells,), "<i8")
+        for k in ("score", "steps", "seen", "chosen", "when"):
+            setattr(A, k, view(getattr(a, k), (cells,), "<i4"))
+        A.records = view(a.records, (cells, self.state_bytes), "|u1")
+        A.slot, A.stored = view(a.slot, (n,), "<i4"), view(a.stored, (n,), "|b1")
+        A.score_in, A.steps_in = view(a.score_in, (n,), "<i4"), view(a.steps_in, (n,), "<i4")
+        self.archive = A
+        if auto:  # every step offers the state it left to its cell, under the hash the novelty update just made
+            self._after_step.append(lambda: hd.check(hd.L.rg_archive_update(hd.h, None, None, None)))
 
     def _archive_need(self, what):
         if self.archive is None:
@@ -355,19 +406,11 @@ class HipVecRogueEnv:
         all.  Afterwards archive.slot / archive.stored say where each env's key lives and whose record was written."""
         torch = self.torch
         self._archive_need("archive_update")
-        def arg(t, name, dtypes):
-            if t is None:
-                return None, None
-            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (self.num_envs,):
-                raise ValueError("archive_update: %s must be a %s tensor [%d] on %s" % (name, " / ".join(str(d) for d in dtypes), self.num_envs, self.device))
-            t = t.contiguous()
-            return t, C.c_void_p(t.data_ptr())
         if keys is None and self._nov_args is None:
             raise ValueError("archive_update: keys=None takes the novelty hash, which needs novelty=")
-        keys, kp = arg(keys, "keys", (torch.int64,))
-        score, sp = arg(score, "score", (torch.int32,))
-        mask, mp = arg(mask, "mask", (torch.bool, torch.uint8))
-        self._h.check(self._h.L.rg_archive_update(self._h.h, kp, sp, mp))
+        args = [None if t is None else self._dev_arg("archive_update", name, t, dtypes, (self.num_envs,))
+                for t, name, dtypes in ((keys, "keys", (torch.int64,)), (score, "score", (torch.int32,)), (mask, "mask", (torch.bool, torch.uint8)))]
+        self._h.check(self._h.L.rg_archive_update(self._h.h, *(None if t is None else C.c_void_p(t.data_ptr()) for t in args)))
 
     def archive_sample(self, k, weights="seen", generator=None):
         """int32 [k] on the device: k occupied slots drawn with replacement -- weights "seen": Go-Explore's 1 / sqrt(seen + 1), "uniform", or a float tensor
@@ -435,8 +478,8 @@ class HipVecRogueEnv:
 
     _EP_NAMES = ("ep_return", "ep_length", "ep_depth", "died", "time_limit", "last_return", "last_length", "last_depth", "last_cause", "scout", "seen_bits")
 
-    def _episode_setup(self, on, scout, log_cap):
-        torch = self.torch
+    def _setup_episodes(self, on, scout, log_cap):
+        hd, n, view = self._h, self.num_envs, self._dev_view
         self._episodes, self._ep_log_cap = on, log_cap
         for k in self._EP_NAMES:
             setattr(self, k, None)
@@ -444,42 +487,27 @@ class HipVecRogueEnv:
             return
         if log_cap < 0:
             raise ValueError("episode_log must be >= 0, got %d" % log_cap)
-        L, h, n = self._h.L, self._h.h, self.num_envs
-        self._h.check(L.rg_episode_enable(h, inner.RG_EP_STATS | (inner.RG_EP_SCOUT if scout else 0), log_cap))
+        hd.check(hd.L.rg_episode_enable(hd.h, inner.RG_EP_STATS | (inner.RG_EP_SCOUT if scout else 0), log_cap))
         a = inner.RgEpisodeArrays()
-        self._h.check(L.rg_episode_arrays(h, C.byref(a)))
-        with torch.cuda.device(self.device):
-            def view(ptr, shape, typestr):
-                return None if not ptr else torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.device)
-            self.ep_return, self.ep_length, self.ep_depth = view(a.ret, (n,), "<f4"), view(a.len, (n,), "<i4"), view(a.depth, (n,), "<i4")
-            self.died, self.time_limit = view(a.died, (n,), "|b1"), view(a.time_limit, (n,), "|b1")
-            self.last_return, self.last_length, self.last_depth = view(a.last_return, (n,), "<f4"), view(a.last_length, (n,), "<i4"), view(a.last_depth, (n,), "<i4")
-            self.last_cause = view(a.last_cause, (n,), "|u1")
-            self.scout, self.seen_bits = view(a.scout, (n,), "<f4"), view(a.seen, (n, a.seen_bytes), "|u1")
+        hd.check(hd.L.rg_episode_arrays(hd.h, C.byref(a)))
+        self.ep_return, self.ep_length, self.ep_depth = view(a.ret, (n,), "<f4"), view(a.len, (n,), "<i4"), view(a.depth, (n,), "<i4")
+        self.died, self.time_limit = view(a.died, (n,), "|b1"), view(a.time_limit, (n,), "|b1")
+        self.last_return, self.last_length, self.last_depth = view(a.last_return, (n,), "<f4"), view(a.last_length, (n,), "<i4"), view(a.last_depth, (n,), "<i4")
+        self.last_cause = view(a.last_cause, (n,), "|u1")
+        self.scout, self.seen_bits = view(a.scout, (n,), "<f4"), view(a.seen, (n, a.seen_bytes), "|u1")
+        self._after_step.append(lambda: hd.check(hd.L.rg_episode_update(hd.h)))  # the accounting of a step, on the mirrors and cells as it left them
 
     def cut_episodes(self, env_ids=None, mask=None, record=False):
         """Tell the episode accounting that the caller overwrote envs (load_state / clone_state, which leave it alone): the lanes of env_ids (a list, a numpy
         array or a device tensor, without duplicates), of mask (a bool / uint8 device tensor [num_envs]) or -- both None -- of every env start anew from the
         game that stands in them now, `ep_length` from that game's own step counter.  record=True first finishes the running episode of each (if it has
         played a step) with cause 3, as reset() and reset_envs() do.  Needs episodes=True."""
-        torch = self.torch
         if not self._episodes:
             raise ValueError("cut_episodes needs episodes=True")
-        if env_ids is not None and mask is not None:
-            raise ValueError("cut_episodes takes env_ids or mask, not both")
-        L, h = self._h.L, self._h.h
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,):
-                raise ValueError("cut_episodes: mask must be a bool / uint8 tensor [%d] on %s" % (self.num_envs, self.device))
-            mask = mask.contiguous()
-            self._h.check(L.rg_episode_cut(h, None, 0, 0, C.c_void_p(mask.data_ptr()), int(bool(record))))
-            return
-        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
-        if on_dev and torch.unique(_keep).numel() != k:
-            raise ValueError("cut_episodes: duplicate env_ids")
+        ptr, k, on_dev, mask, _keep = self._ids_or_mask("cut_episodes", env_ids, mask, one=False)
         if env_ids is not None and k == 0:
             return
-        self._h.check(L.rg_episode_cut(h, ptr, k, on_dev, None, int(bool(record))))
+        self._h.check(self._h.L.rg_episode_cut(self._h.h, ptr, k, on_dev, None if mask is None else C.c_void_p(mask.data_ptr()), int(bool(record))))
 
     def pop_episodes(self):
         """The episodes finished since the last call, as a dict of numpy arrays in (serial, env) order -- serial (the ordinal of the step, reset or cut since
@@ -522,7 +550,6 @@ class HipVecRogueEnv:
         """uint8 [N, C, hp, wp] on the device, C = 3 (rgb) or 1 (gray): every env's screen -- or with crop (r or (ry, rx)) its player-centred window -- drawn
         through the env's tileset (rg_obs_pixels / rg_obs_pixels_crop).  tileset (optional): a Tileset that replaces the env's from this call on
         (set_tileset).  out (optional): a contiguous uint8 tensor of that shape on this env's device to write into.  No host trip."""
-        torch = self.torch
         if tileset is not None or self.tileset is None:
             self.set_tileset(tileset)
         crop = None if crop is None else self._crop_radii(crop)
@@ -531,9 +558,7 @@ class HipVecRogueEnv:
             out = self._pixel_tensor(self.num_envs, channels, crop)
         else:
             hc, wc = (self.height, self.width) if crop is None else (2 * crop[0] + 1, 2 * crop[1] + 1)
-            shape = (self.num_envs, channels, hc * self.tileset.th, wc * 8)
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != shape or not out.is_contiguous():
-                raise ValueError("render_pixels: out must be a contiguous uint8 tensor %s on %s" % (list(shape), self.device))
+            self._dev_arg("render_pixels", "out", out, (self.torch.uint8,), (self.num_envs, channels, hc * self.tileset.th, wc * 8), contiguous=True)
         self._pixel_call(channels, crop, out, None)
         return out
 
@@ -582,18 +607,7 @@ class HipVecRogueEnv:
         st = self.image_setting if image_setting is None else image_setting
         if not isinstance(st, ImageSetting):
             raise ValueError("image_setting must be an ImageSetting or None, got %r" % (image_setting,))
-        if obs_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError("obs_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r" % (obs_dtype,))
-        sym = st.dungeon == DungeonType.SYMBOL
-        if symbol_ids:
-            if not sym or st.status.value != 0 or obs_dtype is not None:
-                raise ValueError("symbol_ids=True needs DungeonType.SYMBOL, StatusFlag.EMPTY and obs_dtype=None (the ids are uint8), got %s, status %r, obs_dtype %r"
-                                 % (st.dungeon, st.status, obs_dtype))
-            call, channels, dtype = (2, 3), 1 + int(st.includes_hist), torch.uint8
-        else:
-            call = (int(sym), 1 if obs_dtype == torch.float16 else 2 if obs_dtype == torch.bfloat16 else 0)
-            channels = self._h.L.rg_obs_channels(self._h.h, int(sym), st.status.value, int(st.includes_hist))
-            dtype = torch.float32 if obs_dtype is None else obs_dtype
+        call, channels, dtype = self._obs_call(st, obs_dtype, symbol_ids)
         with torch.cuda.device(self.device):
             view = CropView((ry, rx), st, call, torch.empty((self.num_envs, channels, 2 * ry + 1, 2 * rx + 1), dtype=dtype, device=self.device),
                             torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device))
@@ -615,20 +629,8 @@ class HipVecRogueEnv:
         """After `obs` was refreshed: nothing is pending then, so the crop passes only read the mirrors (and a bound `obs` stays valid)."""
         for v in self._views:
             self._encode_view(v)
-        if self.pixels is not None:
-            self._pixel_call(self._px_channels, self._px_crop, self.pixels, self.pixel_center)
-        if self._mask_u8 is not None:
-            self._h.check(self._h.L.rg_action_mask(self._h.h, None, 0, C.c_void_p(self._mask_u8.data_ptr()), None, 0, 0))
-        if self._guide_goals:
-            self._h.check(self._h.L.rg_path(self._h.h, self._guide_goals, None, None, C.c_void_p(self.guide_dist.data_ptr()), C.c_void_p(self.guide_keys.data_ptr())))
-        if self._guide_route is not None:
-            self._h.check(self._h.L.rg_route(self._h.h, self._guide_route[0], self._guide_route[1], self._guide_route[2], None, C.c_void_p(self.guide_dist.data_ptr()),
-                                             C.c_void_p(self.guide_keys.data_ptr()), None if self.guide_tier is None else C.c_void_p(self.guide_tier.data_ptr())))
-        if self._mon_args is not None:
-            self._h.check(self._h.L.rg_monsters(self._h.h, self._mon_args[0], self._mon_args[1], C.c_void_p(self.monsters.data_ptr()), C.c_void_p(self.threat.data_ptr())))
-        if self._obj_args is not None:
-            self._h.check(self._h.L.rg_objects(self._h.h, self._obj_args[0], self._obj_args[1], self._obj_args[2], C.c_void_p(self.objects.data_ptr()),
-                                               C.c_void_p(self.object_count.data_ptr())))
+        for call in self._refresh:  # pixels, action mask, guide, monsters, objects: those the env was built with
+            call()
 
     def object_table(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
         """(table, count) on the device (rg_objects): table int16 [N, cap, 8], the first `cap` (1 .. 32) objects of every env as rows of OBJECT_COLS in
@@ -667,9 +669,7 @@ class HipVecRogueEnv:
         torch = self.torch
         goals, fb, mode = inner._route_args(goal, fallback, secrets, known, cells is not None)
         if cells is not None:
-            if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or cells.device != self.device or tuple(cells.shape) != (self.num_envs, 2):
-                raise ValueError("route: cells must be an int32 tensor [%d, 2] on %s" % (self.num_envs, self.device))
-            cells = cells.contiguous()
+            cells = self._dev_arg("route", "cells", cells, (torch.int32,), (self.num_envs, 2))
         with torch.cuda.device(self.device):
             keys = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
             dist = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
@@ -687,9 +687,7 @@ class HipVecRogueEnv:
         torch = self.torch
         goals = inner._path_goals(goal, cells is not None)
         if cells is not None:
-            if not isinstance(cells, torch.Tensor) or cells.dtype != torch.int32 or cells.device != self.device or tuple(cells.shape) != (self.num_envs, 2):
-                raise ValueError("path: cells must be an int32 tensor [%d, 2] on %s" % (self.num_envs, self.device))
-            cells = cells.contiguous()
+            cells = self._dev_arg("path", "cells", cells, (torch.int32,), (self.num_envs, 2))
         with torch.cuda.device(self.device):
             keys = torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device)
             dist = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
@@ -712,9 +710,8 @@ class HipVecRogueEnv:
         if out is None:
             with torch.cuda.device(self.device):
                 out = torch.empty((self.num_envs, nk), dtype=torch.uint8, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype not in (torch.uint8, torch.bool) or out.device != self.device or tuple(out.shape) != (self.num_envs, nk)
-              or not out.is_contiguous()):
-            raise ValueError("legal_mask: out must be a contiguous uint8 / bool tensor [%d, %d] on %s" % (self.num_envs, nk, self.device))
+        else:
+            self._dev_arg("legal_mask", "out", out, (torch.uint8, torch.bool), (self.num_envs, nk), contiguous=True)
         self._mask_call(keys, out, None, 0, 0)
         return out if out.dtype == torch.bool else out.view(torch.bool)
 
@@ -741,7 +738,7 @@ class HipVecRogueEnv:
         p = C.c_void_p()
         self._h.check(self._h.L.rg_screen(self._h.h, C.byref(p)))
         if self._screen is None:
-            self._screen = self.torch.as_tensor(_DevArray(p.value, (self.num_envs, self.height, self.width), "|u1"), device=self.device)
+            self._screen = self._dev_view(p.value, (self.num_envs, self.height, self.width), "|u1")
         return self._screen
 
     def _encode(self):
@@ -777,26 +774,17 @@ class HipVecRogueEnv:
         other env keeps its state.  Exactly one of env_ids (a list, a numpy array or a device tensor of env indices, without duplicates) and mask (a
         bool / uint8 device tensor [num_envs], True = rebuild; it never reaches the host) is given.  seeds (optional, with host env_ids only): one
         int of up to 128 bits per id, given to those envs first (rg_seed_envs) -- they restart on it now and at every later reset."""
-        torch = self.torch
-        if (env_ids is None) == (mask is None):
-            raise ValueError("reset_envs needs exactly one of env_ids and mask")
+        ptr, k, on_dev, mask, _keep = self._ids_or_mask("reset_envs", env_ids, mask, one=True)
         L, h = self._h.L, self._h.h
         if mask is not None:
             if seeds is not None:
                 raise ValueError("reset_envs: seeds go with host env_ids, not with a mask")
-            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self.device or tuple(mask.shape) != (self.num_envs,):
-                raise ValueError("reset_envs: mask must be a bool / uint8 tensor [%d] on %s, got %s" % (
-                    self.num_envs, self.device, "%s %s on %s" % (tuple(mask.shape), mask.dtype, mask.device) if isinstance(mask, torch.Tensor) else type(mask).__name__))
-            mask = mask.contiguous()
             self._h.check(L.rg_reset_mask(h, C.c_void_p(mask.data_ptr())))  # (a bool tensor is one byte per element, 0 / 1)
             if self._episodes:
                 self._h.check(L.rg_episode_cut(h, None, 0, 0, C.c_void_p(mask.data_ptr()), 1))
             obs = self._encode()
             self._novelty_cut(mask=mask)
             return obs
-        ptr, k, on_dev, _keep = self._state_ids(env_ids, unique=False)
-        if on_dev and torch.unique(_keep).numel() != k:
-            raise ValueError("reset_envs: duplicate env_ids")
         if seeds is not None:
             if on_dev:
                 raise ValueError("reset_envs: seeds go with host env_ids, not with a device tensor")
@@ -846,12 +834,8 @@ class HipVecRogueEnv:
             self._h.check(self._h.L.rg_step_obs_gray(self._h.h, C.c_void_p(keys.data_ptr()), 1, self.image_setting.status.value, int(self.image_setting.includes_hist),
                                                       C.c_void_p(self.obs.data_ptr())))
             obs = self.obs
-        if self._episodes:  # the accounting of this step, on the mirrors and cells as it left them
-            self._h.check(self._h.L.rg_episode_update(self._h.h))
-        if self._nov_args is not None:  # the visit of the state this step left, behind the observation: the mirrors are drawn
-            self._h.check(self._h.L.rg_novelty_update(self._h.h))
-        if self._arc_auto:  # ... and the offer of that state to its cell, under the hash just made
-            self._h.check(self._h.L.rg_archive_update(self._h.h, None, None, None))
+        for call in self._after_step:  # the episode, novelty and archive updates: those the env was built with
+            call()
         return obs, self.reward, self.done
 
     def step(self, actions):
@@ -866,11 +850,15 @@ class HipVecRogueEnv:
         """u8 [num_envs, record]: the compact observation record of every env of this rank (rg_pack_compact)."""
         L, h = self._h.L, self._h.h
         rec = L.rg_compact_record_bytes(h, int(with_hist))
-        key = ("packed", bool(with_hist))
+        buf = self._scratch_tensor(("packed", bool(with_hist)), (self.num_envs, rec))
+        self._h.check(L.rg_pack_compact(h, int(with_hist), C.c_void_p(buf.data_ptr())))
+        return buf
+
+    def _scratch_tensor(self, key, shape):
+        """The uint8 device tensor kept under `key` from one call to the next (made by the first)."""
         buf = self._scratch.get(key)
         if buf is None:
-            buf = self._scratch[key] = self.torch.empty((self.num_envs, rec), dtype=self.torch.uint8, device=self.device)
-        self._h.check(L.rg_pack_compact(h, int(with_hist), C.c_void_p(buf.data_ptr())))
+            buf = self._scratch[key] = self.torch.empty(shape, dtype=self.torch.uint8, device=self.device)
         return buf
 
     def expand_records(self, packed, image_setting: Optional[ImageSetting] = None, packed_has_hist: bool = False, out=None):
@@ -925,10 +913,7 @@ class HipVecRogueEnv:
         rank, world = self._comm
         L, h = self._h.L, self._h.h
         rec = L.rg_compact_record_bytes(h, int(with_hist))
-        key = ("gathered", bool(with_hist))
-        buf = self._scratch.get(key)
-        if buf is None:
-            buf = self._scratch[key] = self.torch.empty((world * self.num_envs, rec), dtype=self.torch.uint8, device=self.device)
+        buf = self._scratch_tensor(("gathered", bool(with_hist)), (world * self.num_envs, rec))
         self._h.check(L.rg_allgather_compact(h, int(with_hist), C.c_void_p(buf.data_ptr())))
         return buf
 
@@ -1025,6 +1010,18 @@ class HipVecRogueEnv:
             raise ValueError("load_state: duplicate env ids")
         a = a.astype(np.int32)
         return C.c_void_p(a.ctypes.data), int(a.size), 0, a
+
+    def _ids_or_mask(self, call, env_ids, mask, one):
+        """(pointer, count, on_device, mask, keep-alive) of the envs that `call` names by env_ids (_state_ids' forms, duplicates among device ids refused here) or
+        by mask (a bool / uint8 device tensor [num_envs]: pointer None, count 0).  one: exactly one of the two must be given; else both None = every env."""
+        if (env_ids is not None and mask is not None) or (one and env_ids is None and mask is None):
+            raise ValueError("%s takes %s env_ids and mask" % (call, "exactly one of" if one else "at most one of"))
+        if mask is not None:
+            return None, 0, 0, self._dev_arg(call, "mask", mask, (self.torch.bool, self.torch.uint8), (self.num_envs,)), None
+        ptr, k, on_dev, keep = self._state_ids(env_ids, unique=False)
+        if on_dev and self.torch.unique(keep).numel() != k:
+            raise ValueError("%s: duplicate env_ids" % call)
+        return ptr, k, on_dev, None, keep
 
     def save_state(self, env_ids=None):
         """u8 [k, state_bytes] on this env's device: the state records of env_ids (default: every env, in order), asynchronously on the stream.

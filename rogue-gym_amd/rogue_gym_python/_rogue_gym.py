@@ -7,6 +7,7 @@ MI355X; this file only marshals.  There is no CPU fallback: importing works anyw
 constructing a GameState without the built library or without a HIP device raises.
 """
 import ctypes as C
+import functools
 import operator
 import weakref
 import json
@@ -75,21 +76,89 @@ EPISODE_REC = [("serial", "<u4"), ("env", "<i4"), ("ret", "<f4"), ("length", "<i
 
 _lib = None
 
-_INT_FUNCS = (
-    "rg_create", "rg_dims", "rg_env_dims", "rg_env_symbols", "rg_set_stream", "rg_seed", "rg_reset", "rg_step", "rg_step_prefix", "rg_step_obs_gray", "rg_step_fetch", "rg_sync", "rg_screen", "rg_hist", "rg_status", "rg_flags",
-    "rg_reward", "rg_done", "rg_set_stair_reward", "rg_obs_bind", "rg_obs_gray", "rg_obs_symbol", "rg_obs_channels", "rg_fetch_states", "rg_encode_host", "rg_encode_host_batch", "rg_obs_host",
-    "rg_host_alloc", "rg_dev_alloc", "rg_snapshot_take", "rg_dev_read", "rg_dev_read_rows", "rg_compact_record_bytes", "rg_pack_compact", "rg_expand_compact", "rg_comm_unique_id", "rg_comm_init", "rg_comm_destroy", "rg_comm_count", "rg_allgather_compact", "rg_status_vec", "rg_history_enable", "rg_history_keys",
-    "rg_dump_history", "rg_counters", "rg_counters_ex", "rg_probe_sclk", "rg_dump_config", "rg_config_canonical", "rg_config_resolved", "rg_config_schema", "rg_debug_fetch", "rg_debug_descend", "rg_timing_enable", "rg_timing_read", "rg_timing_read_all", "rg_timing_read_samples",
-    "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed", "rg_step_obs_typed",
-    "rg_obs_crop_typed", "rg_step_obs_crop_typed",
-    "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-    "rg_path", "rg_path_host", "rg_route", "rg_route_host",
-    "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
-    "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host",
-    "rg_archive_enable", "rg_archive_update", "rg_archive_arrays", "rg_archive_restore", "rg_archive_stats", "rg_archive_clear", "rg_archive_offer_host",
-    "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
-    "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host",
-)
+vp, i32, u32, u64, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t
+_P = C.POINTER
+
+# The C-ABI (include/rogue_gym_hip.h), every entry point once: name -> (argtypes, restype, may be absent).  In the two tables below a plain list is the
+# argtypes of an entry point that returns int; a pair is (argtypes, restype) of one that does not.  tests/test_cabi_load.py holds them against the header.
+_ABI = {}
+
+
+def _abi(may_be_absent, table):
+    for name, spec in table.items():
+        argtypes, restype = spec if isinstance(spec, tuple) else (spec, C.c_int)
+        _ABI[name] = (argtypes, restype, may_be_absent)
+
+
+_abi(False, {
+    "rg_create": [_P(C.c_char_p), i32, u64, i32, i32, _P(vp)],
+    "rg_destroy": ([vp], None),
+    "rg_last_error": ([vp], C.c_char_p),
+    "rg_build_id": ([], C.c_char_p),
+    "rg_dims": [vp] + [_P(i32)] * 4,
+    "rg_env_symbols": [vp, vp], "rg_env_dims": [vp, vp, vp],
+    "rg_set_stream": [vp, vp],
+    "rg_seed": [vp, _P(u64), _P(u64), i32],
+    "rg_reset": [vp],
+    "rg_step": [vp, vp, i32],
+    "rg_step_prefix": [vp, vp, i32, i32],
+    "rg_step_obs_gray": [vp, vp, i32, u32, i32, vp],
+    "rg_step_fetch": [vp, vp, i32, vp, vp, vp, vp],
+    "rg_sync": [vp],
+    "rg_screen": [vp, _P(vp)], "rg_hist": [vp, _P(vp)], "rg_status": [vp, _P(vp)], "rg_flags": [vp, _P(vp)],
+    "rg_reward": [vp, _P(vp)], "rg_done": [vp, _P(vp)], "rg_set_stair_reward": [vp, C.c_float],
+    "rg_obs_gray": [vp, u32, i32, vp], "rg_obs_symbol": [vp, u32, i32, vp], "rg_obs_channels": [vp, i32, u32, i32],
+    "rg_fetch_states": [vp, vp, vp, vp, vp],
+    "rg_encode_host": [i32, vp, vp, vp, i32, i32, i32, u32, i32, i32, vp],
+    "rg_encode_host_batch": [i32, i32, vp, vp, vp, i32, i32, i32, u32, i32, i32, vp],
+    "rg_obs_host": [vp, i32, u32, i32, vp],
+    "rg_host_alloc": [sz, _P(vp)], "rg_host_free": ([vp], None),
+    "rg_dev_alloc": [i32, sz, _P(vp)], "rg_dev_free": ([i32, vp], None), "rg_snapshot_take": [vp, vp], "rg_dev_read": [vp, vp, vp, sz], "rg_dev_read_rows": [vp, vp, sz, vp, sz, i32],
+    "rg_compact_record_bytes": [vp, i32], "rg_pack_compact": [vp, i32, vp], "rg_expand_compact": [vp, vp, i32, i32, i32, u32, i32, vp],
+    "rg_comm_unique_id": [vp], "rg_comm_init": [vp, vp, i32, i32], "rg_comm_destroy": [vp], "rg_comm_count": [vp, vp, vp], "rg_allgather_compact": [vp, i32, vp],
+    "rg_status_vec": [vp, u32, vp],
+    "rg_history_enable": [vp, i32], "rg_history_keys": [vp, i32, i32, vp, sz, _P(u32)],
+    "rg_dump_history": [vp, i32, i32, C.c_char_p, sz, _P(sz)],
+    "rg_counters": [vp, _P(u64), i32], "rg_counters_ex": [vp, _P(u64), i32, i32], "rg_probe_sclk": [vp, _P(C.c_double)],
+    "rg_timing_enable": [vp, i32], "rg_timing_read": [vp, _P(C.c_double), _P(u64)],
+    "rg_timing_read_all": [vp, i32, _P(C.c_double), _P(u64), _P(u64)],
+    "rg_dump_config": [vp, i32, C.c_char_p, sz], "rg_config_canonical": [C.c_char_p, C.c_char_p, sz],
+    "rg_config_resolved": [C.c_char_p, C.c_char_p, sz], "rg_config_schema": [C.c_char_p, sz, _P(sz)],
+    "rg_debug_fetch": [vp, i32, _P(RgDebugState), vp], "rg_debug_descend": [vp],
+})
+# Entry points that a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack; the product library exports every symbol of the header.
+_abi(True, {
+    "rg_timing_read_samples": [vp, i32, _P(C.c_float), i32, _P(i32)],
+    "rg_obs_bind": [vp, i32, u32, i32, vp],
+    "rg_state_record_bytes": [vp], "rg_state_save": [vp, vp, i32, i32, vp], "rg_state_load": [vp, vp, sz, vp, i32, i32],
+    "rg_obs_crop": [vp, i32, i32, i32, u32, i32, vp, vp],
+    "rg_obs_dtype_bytes": [i32], "rg_obs_typed": [vp, i32, i32, u32, i32, vp], "rg_step_obs_typed": [vp, vp, i32, i32, i32, u32, i32, vp],
+    "rg_obs_crop_typed": [vp, i32, i32, i32, i32, u32, i32, vp, vp], "rg_step_obs_crop_typed": [vp, vp, i32, i32, i32, i32, i32, u32, i32, vp, vp],
+    "rg_reset_envs": [vp, vp, i32, i32], "rg_reset_mask": [vp, vp], "rg_seed_envs": [vp, vp, _P(u64), _P(u64), i32],
+    "rg_tail_encode": [vp, i32],
+    "rg_action_mask": [vp, vp, i32, vp, vp, u64, u64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
+    "rg_sample_index": ([u64, u32, u64, u32], u32),
+    "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
+    "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
+    "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, _P(RgEpisodeArrays)],
+    "rg_episode_log_read": [vp, vp, i32, _P(i32), _P(u64)], "rg_scout_host": [vp, i32, i32, vp, _P(i32)],
+    "rg_novelty_enable": [vp, i32, u32, i32, i32, i32, i32], "rg_novelty_update": [vp], "rg_novelty_cut": [vp, vp, i32, i32, vp],
+    "rg_novelty_arrays": [vp, _P(RgNoveltyArrays)], "rg_novelty_stats": [vp, _P(u64)], "rg_novelty_table_read": [vp, vp, vp, i32, _P(i32)],
+    "rg_novelty_clear": [vp], "rg_novelty_hash_host": [i32, i32, i32, i32, vp, i32, i32, i32, i32, _P(u64)],
+    "rg_novelty_finish_host": ([u64, u64], u64), "rg_novelty_insert_host": [vp, i32, u32, u64, _P(u32)],
+    "rg_archive_enable": [vp, i32], "rg_archive_update": [vp, vp, vp, vp], "rg_archive_arrays": [vp, _P(RgArchiveArrays)],
+    "rg_archive_restore": [vp, vp, vp, i32, i32], "rg_archive_stats": [vp, _P(u64)], "rg_archive_clear": [vp],
+    "rg_archive_offer_host": [vp, i32, u64, C.c_int32, u32, u32, _P(C.c_int32), _P(C.c_int32)],
+    "rg_monsters": [vp, u32, i32, vp, vp],
+    "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
+    "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
+    "rg_tileset_default": [_P(i32), vp, vp], "rg_tileset_set": [vp, i32, vp, vp],
+    "rg_obs_pixels": [vp, i32, vp], "rg_obs_pixels_crop": [vp, i32, i32, i32, vp, vp],
+    "rg_step_obs_pixels": [vp, vp, i32, i32, vp], "rg_step_obs_pixels_crop": [vp, vp, i32, i32, i32, i32, vp, vp],
+    "rg_pixels_host": [i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp],
+})
+
+_INT_FUNCS = tuple(name for name, (_, restype, _absent) in _ABI.items() if restype is C.c_int)
 
 
 def load_library():
@@ -110,97 +179,12 @@ def load_library():
     except ImportError:
         pass
     L = C.CDLL(_SO)
-    vp, i32, u32, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_size_t
-    sig = {
-        "rg_create": [C.POINTER(C.c_char_p), i32, C.c_uint64, i32, i32, C.POINTER(vp)],
-        "rg_destroy": [vp],
-        "rg_last_error": [vp],
-        "rg_dims": [vp] + [C.POINTER(i32)] * 4,
-        "rg_env_symbols": [vp, vp], "rg_env_dims": [vp, vp, vp],
-        "rg_set_stream": [vp, vp],
-        "rg_seed": [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i32],
-        "rg_reset": [vp],
-        "rg_step": [vp, vp, i32],
-        "rg_step_prefix": [vp, vp, i32, i32],
-        "rg_step_obs_gray": [vp, vp, i32, u32, i32, vp],
-        "rg_step_fetch": [vp, vp, i32, vp, vp, vp, vp],
-        "rg_sync": [vp],
-        "rg_screen": [vp, C.POINTER(vp)], "rg_hist": [vp, C.POINTER(vp)], "rg_status": [vp, C.POINTER(vp)], "rg_flags": [vp, C.POINTER(vp)],
-        "rg_reward": [vp, C.POINTER(vp)], "rg_done": [vp, C.POINTER(vp)], "rg_set_stair_reward": [vp, C.c_float],
-        "rg_obs_bind": [vp, i32, u32, i32, vp], "rg_obs_gray": [vp, u32, i32, vp], "rg_obs_symbol": [vp, u32, i32, vp], "rg_obs_channels": [vp, i32, u32, i32],
-        "rg_fetch_states": [vp, vp, vp, vp, vp],
-        "rg_encode_host": [i32, vp, vp, vp, i32, i32, i32, u32, i32, i32, vp],
-        "rg_encode_host_batch": [i32, i32, vp, vp, vp, i32, i32, i32, u32, i32, i32, vp],
-        "rg_obs_host": [vp, i32, u32, i32, vp],
-        "rg_host_alloc": [sz, C.POINTER(vp)], "rg_host_free": [vp],
-        "rg_dev_alloc": [i32, sz, C.POINTER(vp)], "rg_dev_free": [i32, vp], "rg_snapshot_take": [vp, vp], "rg_dev_read": [vp, vp, vp, sz], "rg_dev_read_rows": [vp, vp, sz, vp, sz, i32],
-        "rg_compact_record_bytes": [vp, i32], "rg_pack_compact": [vp, i32, vp], "rg_expand_compact": [vp, vp, i32, i32, i32, u32, i32, vp],
-        "rg_comm_unique_id": [vp], "rg_comm_init": [vp, vp, i32, i32], "rg_comm_destroy": [vp], "rg_comm_count": [vp, vp, vp], "rg_allgather_compact": [vp, i32, vp],
-        "rg_status_vec": [vp, u32, vp],
-        "rg_history_enable": [vp, i32], "rg_history_keys": [vp, i32, i32, vp, sz, C.POINTER(u32)],
-        "rg_dump_history": [vp, i32, i32, C.c_char_p, sz, C.POINTER(sz)],
-        "rg_counters": [vp, C.POINTER(C.c_uint64), i32], "rg_counters_ex": [vp, C.POINTER(C.c_uint64), i32, i32], "rg_probe_sclk": [vp, C.POINTER(C.c_double)],
-        "rg_timing_enable": [vp, i32], "rg_timing_read": [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)],
-        "rg_timing_read_all": [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
-        "rg_timing_read_samples": [vp, i32, C.POINTER(C.c_float), i32, C.POINTER(i32)],
-        "rg_dump_config": [vp, i32, C.c_char_p, sz], "rg_config_canonical": [C.c_char_p, C.c_char_p, sz],
-        "rg_config_resolved": [C.c_char_p, C.c_char_p, sz], "rg_config_schema": [C.c_char_p, sz, C.POINTER(sz)],
-        "rg_debug_fetch": [vp, i32, C.POINTER(RgDebugState), vp], "rg_debug_descend": [vp],
-        "rg_state_record_bytes": [vp], "rg_state_save": [vp, vp, i32, i32, vp], "rg_state_load": [vp, vp, sz, vp, i32, i32],
-        "rg_obs_crop": [vp, i32, i32, i32, u32, i32, vp, vp],
-        "rg_obs_dtype_bytes": [i32], "rg_obs_typed": [vp, i32, i32, u32, i32, vp], "rg_step_obs_typed": [vp, vp, i32, i32, i32, u32, i32, vp],
-        "rg_obs_crop_typed": [vp, i32, i32, i32, i32, u32, i32, vp, vp], "rg_step_obs_crop_typed": [vp, vp, i32, i32, i32, i32, i32, u32, i32, vp, vp],
-        "rg_reset_envs": [vp, vp, i32, i32], "rg_reset_mask": [vp, vp], "rg_seed_envs": [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i32],
-        "rg_tail_encode": [vp, i32],
-        "rg_action_mask": [vp, vp, i32, vp, vp, C.c_uint64, C.c_uint64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
-        "rg_sample_index": [C.c_uint64, u32, C.c_uint64, u32],
-        "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
-        "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
-        "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, C.POINTER(RgEpisodeArrays)],
-        "rg_episode_log_read": [vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)], "rg_scout_host": [vp, i32, i32, vp, C.POINTER(i32)],
-        "rg_novelty_enable": [vp, i32, u32, i32, i32, i32, i32], "rg_novelty_update": [vp], "rg_novelty_cut": [vp, vp, i32, i32, vp],
-        "rg_novelty_arrays": [vp, C.POINTER(RgNoveltyArrays)], "rg_novelty_stats": [vp, C.POINTER(C.c_uint64)], "rg_novelty_table_read": [vp, vp, vp, i32, C.POINTER(i32)],
-        "rg_novelty_clear": [vp], "rg_novelty_hash_host": [i32, i32, i32, i32, vp, i32, i32, i32, i32, C.POINTER(C.c_uint64)],
-        "rg_novelty_finish_host": [C.c_uint64, C.c_uint64], "rg_novelty_insert_host": [vp, i32, u32, C.c_uint64, C.POINTER(u32)],
-        "rg_archive_enable": [vp, i32], "rg_archive_update": [vp, vp, vp, vp], "rg_archive_arrays": [vp, C.POINTER(RgArchiveArrays)],
-        "rg_archive_restore": [vp, vp, vp, i32, i32], "rg_archive_stats": [vp, C.POINTER(C.c_uint64)], "rg_archive_clear": [vp],
-        "rg_archive_offer_host": [vp, i32, C.c_uint64, C.c_int32, u32, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
-        "rg_monsters": [vp, u32, i32, vp, vp],
-        "rg_monsters_host": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, i32, vp, vp],
-        "rg_objects": [vp, u32, u32, i32, vp, vp], "rg_objects_host": [vp, i32, i32, i32, i32, i32, u32, u32, i32, vp, vp],
-        "rg_tileset_default": [C.POINTER(i32), vp, vp], "rg_tileset_set": [vp, i32, vp, vp],
-        "rg_obs_pixels": [vp, i32, vp], "rg_obs_pixels_crop": [vp, i32, i32, i32, vp, vp],
-        "rg_step_obs_pixels": [vp, vp, i32, i32, vp], "rg_step_obs_pixels_crop": [vp, vp, i32, i32, i32, i32, vp, vp],
-        "rg_pixels_host": [i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp],
-    }
-    # (entry points added in round 6: a library named by ROGUE_GYM_HIP_LIB -- an older build in a same-box A/B run -- may lack them; the product library
-    # exports every symbol of the header, tests/test_cabi_load.py)
-    optional = {"rg_timing_read_samples", "rg_obs_bind", "rg_state_record_bytes", "rg_state_save", "rg_state_load", "rg_obs_crop", "rg_obs_dtype_bytes", "rg_obs_typed",
-                "rg_step_obs_typed", "rg_obs_crop_typed", "rg_step_obs_crop_typed", "rg_reset_envs", "rg_reset_mask", "rg_seed_envs", "rg_tail_encode", "rg_action_mask", "rg_action_mask_host",
-                "rg_sample_index", "rg_path", "rg_path_host", "rg_route", "rg_route_host",
-                "rg_episode_enable", "rg_episode_update", "rg_episode_cut", "rg_episode_arrays", "rg_episode_log_read", "rg_scout_host",
-                "rg_novelty_enable", "rg_novelty_update", "rg_novelty_cut", "rg_novelty_arrays", "rg_novelty_stats", "rg_novelty_table_read", "rg_novelty_clear", "rg_novelty_hash_host", "rg_novelty_insert_host", "rg_novelty_finish_host",
-                "rg_archive_enable", "rg_archive_update", "rg_archive_arrays", "rg_archive_restore", "rg_archive_stats", "rg_archive_clear", "rg_archive_offer_host",
-                "rg_monsters", "rg_monsters_host", "rg_objects", "rg_objects_host",
-                "rg_tileset_default", "rg_tileset_set", "rg_obs_pixels", "rg_obs_pixels_crop", "rg_step_obs_pixels", "rg_step_obs_pixels_crop", "rg_pixels_host"} if os.environ.get("ROGUE_GYM_HIP_LIB") else set()
-    for name, argtypes in sig.items():
-        if name in optional and not hasattr(L, name):
+    other_build = bool(os.environ.get("ROGUE_GYM_HIP_LIB"))
+    for name, (argtypes, restype, may_be_absent) in _ABI.items():
+        if may_be_absent and other_build and not hasattr(L, name):
             continue
-        getattr(L, name).argtypes = argtypes
-    L.rg_destroy.restype = None
-    L.rg_host_free.restype = None
-    L.rg_dev_free.restype = None
-    L.rg_last_error.restype = C.c_char_p
-    L.rg_build_id.restype = C.c_char_p
-    L.rg_build_id.argtypes = []
-    if hasattr(L, "rg_sample_index"):
-        L.rg_sample_index.restype = C.c_uint32
-    if hasattr(L, "rg_novelty_finish_host"):
-        L.rg_novelty_finish_host.restype = C.c_uint64
-    for name in _INT_FUNCS:
-        if name in optional and not hasattr(L, name):
-            continue
-        getattr(L, name).restype = C.c_int
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L
 
@@ -287,25 +271,27 @@ def _default_device():
     return int(os.environ.get("ROGUE_GYM_HIP_DEVICE", os.environ.get("LOCAL_RANK", "0")))
 
 
-class _PinnedPool:
-    """Page-locked host buffers for the per-step D2H copies of the value-object API.  A StateBatch borrows its buffers and hands them back
-    when it is collected, so a stepping loop settles on two or three buffer sets and the copies run at full PCIe rate."""
+class _Pool:
+    """Buffers of one kind on loan, kept by size: take(nbytes) gives an address, give(address, nbytes) takes it back.  alloc(nbytes, byref) and free(pointer)
+    are the library's pair for the kind.  The handle keeps two.  `pool`: page-locked host buffers for the per-step D2H copies of the value-object API -- a
+    StateBatch borrows its buffers and hands them back when it is collected, so a stepping loop settles on two or three buffer sets and the copies run at full
+    PCIe rate.  `dev_pool`: device buffers for the StateBatch snapshots."""
 
-    def __init__(self, L):
-        self.L, self.free, self.closed = L, {}, False
+    def __init__(self, L, alloc, free):
+        self.L, self.alloc, self.release, self.free, self.closed = L, alloc, free, {}, False
 
     def take(self, nbytes):
         lst = self.free.get(nbytes)
         if lst:
             return lst.pop()
         p = C.c_void_p()
-        if self.L.rg_host_alloc(nbytes, C.byref(p)):
+        if self.alloc(nbytes, C.byref(p)):
             raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
         return p.value
 
     def give(self, ptr, nbytes):
         if self.closed:
-            self.L.rg_host_free(C.c_void_p(ptr))
+            self.release(C.c_void_p(ptr))
         else:
             self.free.setdefault(nbytes, []).append(ptr)
 
@@ -313,43 +299,15 @@ class _PinnedPool:
         self.closed = True
         for lst in self.free.values():
             for ptr in lst:
-                self.L.rg_host_free(C.c_void_p(ptr))
-        self.free = {}
-
-
-class _DevPool:
-    """Device buffers for the StateBatch snapshots (same take / give protocol as _PinnedPool)."""
-
-    def __init__(self, L, device):
-        self.L, self.device, self.free, self.closed = L, device, {}, False
-
-    def take(self, nbytes):
-        lst = self.free.get(nbytes)
-        if lst:
-            return lst.pop()
-        p = C.c_void_p()
-        if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-            raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-        return p.value
-
-    def give(self, ptr, nbytes):
-        if self.closed:
-            self.L.rg_dev_free(self.device, C.c_void_p(ptr))
-        else:
-            self.free.setdefault(nbytes, []).append(ptr)
-
-    def close(self):
-        self.closed = True
-        for lst in self.free.values():
-            for ptr in lst:
-                self.L.rg_dev_free(self.device, C.c_void_p(ptr))
+                self.release(C.c_void_p(ptr))
         self.free = {}
 
 
 class _Lease:
-    """One pooled pinned buffer on loan.  It goes back to the pool when the LAST array that views it is collected -- not when the StateBatch
+    """One pooled buffer on loan.  A pinned one goes back to the pool when the LAST array that views it is collected -- not when the StateBatch
     that asked for it is: `obs = env.images()` kept in a rollout buffer stays valid (and unchanged) for as long as the caller holds it, like the
-    independent arrays the reference returns (python/src/lib.rs:78,95)."""
+    independent arrays the reference returns (python/src/lib.rs:78,95).  A device one is on loan to one StateBatch (its snapshot of the screen / history
+    mirrors)."""
     __slots__ = ("pool", "ptr", "nbytes")
 
     def __init__(self, pool, nbytes):
@@ -358,22 +316,7 @@ class _Lease:
 
     def __del__(self):
         try:
-            self.pool.give(self.ptr, self.nbytes)  # a closed pool frees it instead (hipHostFree)
-        except Exception:
-            pass
-
-
-class _DevLease:
-    """A pooled device buffer on loan to one StateBatch (its snapshot of the screen / history mirrors)."""
-    __slots__ = ("pool", "ptr", "nbytes")
-
-    def __init__(self, pool, nbytes):
-        self.pool, self.nbytes = pool, nbytes
-        self.ptr = pool.take(nbytes)
-
-    def __del__(self):
-        try:
-            self.pool.give(self.ptr, self.nbytes)
+            self.pool.give(self.ptr, self.nbytes)  # a closed pool frees it instead
         except Exception:
             pass
 
@@ -514,12 +457,12 @@ class _Handle:
         self.env_heights, self.env_widths = np.empty(self.n, np.int32), np.empty(self.n, np.int32)  # ... and in size (python/src/lib.rs:270-294)
         L.rg_env_dims(h, self.env_heights.ctypes.data, self.env_widths.ctypes.data)
         self.mixed_sizes = bool((self.env_heights != self.height).any() or (self.env_widths != self.width).any())
-        self.pool = _PinnedPool(L)
-        self.dev_pool = _DevPool(L, self.device)
+        self.pool = _Pool(L, L.rg_host_alloc, L.rg_host_free)
+        self.dev_pool = _Pool(L, functools.partial(L.rg_dev_alloc, self.device), functools.partial(L.rg_dev_free, self.device))
         self.lazy = {}  # id -> weakref of the StateBatches whose screens still live only in their device snapshot (materialised before the handle goes)
         self.epoch = 0  # bumped by every call that changes the device-side states (a StateBatch remembers the epoch it was taken at)
         self.fast_step = True  # rg_step_fetch applies (cleared by the first refusal: a handle with config groups)
-        self._mask_dev = None  # action_mask: its device scratch (address, bytes), kept between calls
+        self._scratch = (None, -1)  # the device scratch buffer of the host readers below (address, bytes; -1: none yet): kept between calls, grow-only, freed in close()
 
     def check(self, rc):
         if rc:
@@ -531,9 +474,9 @@ class _Handle:
                 b = ref()
                 if b is not None:
                     b._materialise()
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
+            if self._scratch[0]:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._scratch[0]))
+                self._scratch = (None, -1)
             self.L.rg_destroy(self.h)
             self.h = None
             self.pool.close()
@@ -574,101 +517,69 @@ class _Handle:
         self.check(self.L.rg_debug_fetch(self.h, env, C.byref(out), cells.ctypes.data))
         return out, cells
 
+    def _scratch_grow(self, nbytes):
+        """The address of the device scratch buffer, which holds at least nbytes afterwards (a larger one replaces it; it never shrinks)."""
+        if self._scratch[1] < nbytes:
+            if self._scratch[0]:
+                self.L.rg_dev_free(self.device, C.c_void_p(self._scratch[0]))
+                self._scratch = (None, -1)
+            p = C.c_void_p()
+            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+            self._scratch = (p.value, nbytes)
+        return self._scratch[0]
+
+    def _scratch_read(self, nbytes):
+        """The first nbytes of the device scratch buffer as a numpy uint8 array of its own (one rg_dev_read)."""
+        out = np.empty(nbytes, np.uint8)
+        self.check(self.L.rg_dev_read(self.h, C.c_void_p(self._scratch[0]), out.ctypes.data, nbytes))
+        return out
+
     def action_mask(self, keys=None):
         """bool [n, n_keys]: which of `keys` (bytes / str; None = RG_ACTION_KEYS, RogueEnv.ACTIONS in index order) would do anything for each env now
         (rg_action_mask into a device scratch buffer the handle keeps, one rg_dev_read)."""
         kb, nk = _mask_keys(keys)
-        nbytes = self.n * nk
-        if self._mask_dev is None or self._mask_dev[1] < nbytes:
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
-            p = C.c_void_p()
-            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-            self._mask_dev = (p.value, nbytes)
-        self.check(self.L.rg_action_mask(self.h, kb, nk, C.c_void_p(self._mask_dev[0]), None, 0, 0))
-        out = np.empty((self.n, nk), np.uint8)
-        self.check(self.L.rg_dev_read(self.h, C.c_void_p(self._mask_dev[0]), out.ctypes.data, nbytes))
-        return out.view(np.bool_)
+        base = self._scratch_grow(self.n * nk)
+        self.check(self.L.rg_action_mask(self.h, kb, nk, C.c_void_p(base), None, 0, 0))
+        return self._scratch_read(self.n * nk).reshape(self.n, nk).view(np.bool_)
 
     def path_keys(self, goal="stairs"):
         """(keys u8 [n], dist i32 [n]) towards `goal` ("stairs", "gold", "stairs+gold"): rg_path into the device scratch buffer the handle keeps, one
         rg_dev_read.  dist -1 = unreachable."""
-        goals = _path_goals(goal)
-        nbytes = self.n * 5
-        if self._mask_dev is None or self._mask_dev[1] < nbytes:
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
-            p = C.c_void_p()
-            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-            self._mask_dev = (p.value, nbytes)
-        base = self._mask_dev[0]  # dist i32 [n], then keys u8 [n]
-        self.check(self.L.rg_path(self.h, goals, None, None, C.c_void_p(base), C.c_void_p(base + 4 * self.n)))
-        out = np.empty(nbytes, np.uint8)
-        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
-        return out[4 * self.n:].copy(), out[:4 * self.n].view(np.int32).copy()
+        goals, n = _path_goals(goal), self.n
+        base = self._scratch_grow(5 * n)  # dist i32 [n], then keys u8 [n]
+        self.check(self.L.rg_path(self.h, goals, None, None, C.c_void_p(base), C.c_void_p(base + 4 * n)))
+        out = self._scratch_read(5 * n)
+        return out[4 * n:].copy(), out[:4 * n].view(np.int32).copy()
+
+    def _tables(self, cap, cols, launch):
+        """(table i16 [n, cap, cols], words i32 [n, 4]) of a table pass: launch(table address, words address) into the device scratch buffer, one rg_dev_read."""
+        tb = self.n * cap * cols * 2
+        base = self._scratch_grow(tb + self.n * 16)  # table i16 [n][cap][8], then the words i32 [n][4]: both on multiples of 16 bytes
+        self.check(launch(C.c_void_p(base), C.c_void_p(base + tb)))
+        out = self._scratch_read(tb + self.n * 16)
+        return out[:tb].view(np.int16).reshape(self.n, cap, cols).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
 
     def monster_tables(self, mode="shown", cap=4):
         """(table i16 [n, cap, 8], threat i32 [n, 4]) of rg_monsters (_monster_args names the arguments): into the device scratch buffer the handle keeps,
         one rg_dev_read."""
         m, cap = _monster_args(mode, cap)
-        tb = self.n * cap * 16
-        nbytes = tb + self.n * 16
-        if self._mask_dev is None or self._mask_dev[1] < nbytes:
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
-            p = C.c_void_p()
-            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-            self._mask_dev = (p.value, nbytes)
-        base = self._mask_dev[0]  # table i16 [n][cap][8], then threat i32 [n][4]: both on multiples of 16 bytes
-        self.check(self.L.rg_monsters(self.h, m, cap, C.c_void_p(base), C.c_void_p(base + tb)))
-        out = np.empty(nbytes, np.uint8)
-        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
-        return out[:tb].view(np.int16).reshape(self.n, cap, RG_MON_COLS).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
+        return self._tables(cap, RG_MON_COLS, lambda table, threat: self.L.rg_monsters(self.h, m, cap, table, threat))
 
     def object_tables(self, kinds="stairs+gold+door", known=False, secrets=False, cap=8):
         """(table i16 [n, cap, 8], count i32 [n, 4]) of rg_objects (_object_args names the arguments): into the device scratch buffer the handle keeps,
         one rg_dev_read."""
         kw, mode, cap = _object_args(kinds, known, secrets, cap)
-        tb = self.n * cap * 16
-        nbytes = tb + self.n * 16
-        if self._mask_dev is None or self._mask_dev[1] < nbytes:
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
-            p = C.c_void_p()
-            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-            self._mask_dev = (p.value, nbytes)
-        base = self._mask_dev[0]  # table i16 [n][cap][8], then count i32 [n][4]: both on multiples of 16 bytes
-        self.check(self.L.rg_objects(self.h, kw, mode, cap, C.c_void_p(base), C.c_void_p(base + tb)))
-        out = np.empty(nbytes, np.uint8)
-        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
-        return out[:tb].view(np.int16).reshape(self.n, cap, RG_OBJ_COLS).copy(), out[tb:].view(np.int32).reshape(self.n, 4).copy()
+        return self._tables(cap, RG_OBJ_COLS, lambda table, count: self.L.rg_objects(self.h, kw, mode, cap, table, count))
 
     def route_keys(self, goal="stairs", fallback=None, secrets=False, known=False):
         """(keys u8 [n], dist i32 [n], tier u8 [n]) of rg_route (_route_args names the arguments): into the device scratch buffer the handle keeps, one
         rg_dev_read.  dist -1 = unreachable, tier 255 = neither tier reached the player."""
-        goals, fb, mode = _route_args(goal, fallback, secrets, known)
-        nbytes = self.n * 6
-        if self._mask_dev is None or self._mask_dev[1] < nbytes:
-            if self._mask_dev is not None:
-                self.L.rg_dev_free(self.device, C.c_void_p(self._mask_dev[0]))
-                self._mask_dev = None
-            p = C.c_void_p()
-            if self.L.rg_dev_alloc(self.device, nbytes, C.byref(p)):
-                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
-            self._mask_dev = (p.value, nbytes)
-        base = self._mask_dev[0]  # dist i32 [n], then keys u8 [n], then tier u8 [n]
-        self.check(self.L.rg_route(self.h, goals, fb, mode, None, C.c_void_p(base), C.c_void_p(base + 4 * self.n), C.c_void_p(base + 5 * self.n)))
-        out = np.empty(nbytes, np.uint8)
-        self.check(self.L.rg_dev_read(self.h, C.c_void_p(base), out.ctypes.data, nbytes))
-        return out[4 * self.n:5 * self.n].copy(), out[:4 * self.n].view(np.int32).copy(), out[5 * self.n:].copy()
+        (goals, fb, mode), n = _route_args(goal, fallback, secrets, known), self.n
+        base = self._scratch_grow(6 * n)  # dist i32 [n], then keys u8 [n], then tier u8 [n]
+        self.check(self.L.rg_route(self.h, goals, fb, mode, None, C.c_void_p(base), C.c_void_p(base + 4 * n), C.c_void_p(base + 5 * n)))
+        out = self._scratch_read(6 * n)
+        return out[4 * n:5 * n].copy(), out[:4 * n].view(np.int32).copy(), out[5 * n:].copy()
 
     def history_keys(self, env, previous=False):
         n = C.c_uint32()
@@ -757,7 +668,7 @@ class StateBatch:
                 scr, hst = self._screen.ctypes.data, self._hist.ctypes.data
             else:
                 self._screen = self._hist = None
-                self._snap = _DevLease(handle.dev_pool, 2 * n * h * w)
+                self._snap = _Lease(handle.dev_pool, 2 * n * h * w)
                 scr, hst = self._snap.ptr, self._snap.ptr + n * h * w
             rc = L.rg_step_fetch(handle.h, keys.ctypes.data, int(keys.shape[0]), C.c_void_p(scr), C.c_void_p(hst), self.status.ctypes.data, self.flags.ctypes.data)
             if rc and b"config groups" in L.rg_last_error(handle.h):  # (refused before anything was stepped: the general path from now on)
@@ -786,7 +697,7 @@ class StateBatch:
             # The RL loop reads gold and is_terminal of every state and nothing else (parallel.py:59-64): status + flags (44 B per env) come to the host
             # now, the screens (1 KB per env) are snapshotted device-to-device (~30 us for 65 536 envs) and cross PCIe only when somebody looks at them
             self._screen = self._hist = None
-            self._snap = _DevLease(handle.dev_pool, 2 * n * h * w)
+            self._snap = _Lease(handle.dev_pool, 2 * n * h * w)
             handle.check(handle.L.rg_snapshot_take(handle.h, C.c_void_p(self._snap.ptr)))
             handle.check(handle.L.rg_fetch_states(handle.h, None, None, self.status.ctypes.data, self.flags.ctypes.data))  # (synchronises the stream)
             self._register_lazy()

@@ -26,6 +26,26 @@ def test_header_symbols_exported(lib):
         assert hasattr(lib, n), "missing export %s" % n
 
 
+def test_ctypes_table_matches_the_header():
+    """Every prototype of include/rogue_gym_hip.h has one entry in the bindings' table and every entry a prototype; the argument counts agree and the restype
+    follows the declared return type.  It reads the module-level table: no library is loaded."""
+    from rogue_gym_python import _rogue_gym as inner
+    hdr = open(os.path.join(ROOT, "include", "rogue_gym_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    restypes = {"int": C.c_int, "void": None, "const char *": C.c_char_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+    protos = re.findall(r"(?<!\w)(int|void|const char \*|uint32_t|uint64_t)\s*\b(rg_[a-z0-9_]+)\s*\(([^()]*)\)\s*(?=;)", hdr)
+    assert len(protos) >= 116 and len({name for _, name, _ in protos}) == len(protos)
+    assert {name for _, name, _ in protos} == set(re.findall(r"\b(rg_[a-z0-9_]+)\s*\(", hdr)), "a prototype of the header was not understood"
+    assert {name for _, name, _ in protos} == set(inner._ABI), {name for _, name, _ in protos} ^ set(inner._ABI)
+    for ret, name, args in protos:
+        argtypes, restype, _ = inner._ABI[name]
+        n_args = 0 if args.strip() in ("", "void") else args.count(",") + 1
+        assert len(argtypes) == n_args, "%s: %d argtypes, the header declares %d arguments" % (name, len(argtypes), n_args)
+        assert restype is restypes[ret], "%s: restype %r, the header declares %s" % (name, restype, ret)
+    assert set(inner._INT_FUNCS) == {name for ret, name, _ in protos if ret == "int"}
+
+
 def test_loaded_library_is_built_from_the_checked_out_sources(lib):
     """The .so is git-ignored and ships prebuilt to the GPU box: its compiled-in build id must be the hash of the sources in the tree."""
     import __graft_entry__ as g

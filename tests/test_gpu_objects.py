@@ -280,7 +280,7 @@ def test_twin_handles_no_side_effects(goldens):
     cfg, seeds = _mini(goldens), [9000 + i for i in range(135)]
     a = HipVecRogueEnv(seeded(cfg, seeds), max_steps=60)
     b = HipVecRogueEnv(seeded(cfg, seeds), max_steps=60, objects="known", object_kinds="stairs+gold+door+frontier", object_cap=32, object_secrets=True)
-    assert a.objects is None and a.object_count is None and a._obj_args is None and b.objects.shape == (135, 32, 8) and b.object_count.shape == (135, 4)
+    assert a.objects is None and a.object_count is None and a._refresh == [] and b.objects.shape == (135, 32, 8) and b.object_count.shape == (135, 4)
     keys = torch.as_tensor(mu.key_table(1, 60, 135), device=a.device)
     for t in range(60):
         a.step_keys(keys[t])
@@ -304,6 +304,7 @@ def test_python_surface_on_every_refresh_path(goldens, lib):
     HipVecFirstFloor; the kept tensors are what the host entry gives on rg_debug_fetch's grids."""
     import torch
     from rogue_gym.envs import OBJECT_COLS, HipVecFirstFloor, HipVecRogueEnv
+    from rogue_gym_python import _rogue_gym as inner
     cfg, seeds = _mini(goldens), [9000 + i for i in range(40)]
     table = mu.key_table(1, 30, 40)
 
@@ -313,7 +314,7 @@ def test_python_surface_on_every_refresh_path(goldens, lib):
         assert torch.equal(env.objects, tb) and torch.equal(env.object_count, cnt), where
         if deep:
             grids, players, dead = fetch(env._h)
-            kw, mode, _ = env._obj_args
+            kw, mode, _ = inner._object_args(kinds, known, secrets, cap)
             t, c = env.objects.cpu().numpy(), env.object_count.cpu().numpy()
             for i in range(40):
                 hb, hc = ou.host(lib, grids[i], players[i][0], players[i][1], int(dead[i]), kw, mode, cap)

@@ -351,7 +351,7 @@ def _check_env(env, font, pal, where):
     if env.pixel_center is None:
         want = pu.full_images(font, pal, screen, ch)
     else:
-        want = pu.crop_images(font, pal, screen, ch, env.pixel_center.cpu().numpy(), *env._px_crop)
+        want = pu.crop_images(font, pal, screen, ch, env.pixel_center.cpu().numpy(), (env.pixels.shape[2] // env.tileset.th - 1) // 2, (env.pixels.shape[3] // 8 - 1) // 2)
     assert_same(env.pixels.cpu().numpy(), want, where)
 
 

@@ -49,10 +49,10 @@ def case(name, cfg, n, what, a):
     L, h = env._h.L, env._h.h
     gen = torch.Generator(device=dev).manual_seed(0)
     table = env._action_keys[torch.randint(0, len(env.ACTIONS), (512, n), generator=gen, device=dev)].contiguous()
-    t = [0]
+    t, after = [0], list(env._after_step)  # (the novelty update, then the archive's: the last registered)
 
     def step(on):
-        env._arc_auto = on  # (off: _step_keys makes exactly the calls of a handle without the archive)
+        env._after_step[:] = after if on else after[:-1]  # (off: _step_keys makes exactly the calls of a handle without the archive)
         env._step_keys(table[t[0] % 512])
         t[0] += 1
 

@@ -66,10 +66,10 @@ def case(name, cfg, n, kind, a):
         dev = env.device
         gen = torch.Generator(device=dev).manual_seed(0)
         table = env._action_keys[torch.randint(0, len(env.ACTIONS), (512, n), generator=gen, device=dev)].contiguous()
-        t = [0]
+        t, update = [0], list(env._after_step)  # (the episode update is all this env registered behind its steps)
 
         def step(on):
-            env._episodes = on  # (off: _step_keys makes exactly the calls of a handle without the accounting)
+            env._after_step[:] = update if on else []  # (off: _step_keys makes exactly the calls of a handle without the accounting)
             env._step_keys(table[t[0] % 512])
             t[0] += 1
 
@@ -86,7 +86,7 @@ def case(name, cfg, n, kind, a):
                     step(m == "on")
                 torch.cuda.synchronize()
                 rates[m].append(n * a.steps / (time.perf_counter() - t0) / 1e6)
-        env._episodes = True
+        env._after_step[:] = update
         if kind == "symbol":
             env._h.L.rg_sync(env._h.h)  # (drains the tile-error word: 'Z' is a monster of these configs and not a symbol, as in the reference)
         else:

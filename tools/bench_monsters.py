@@ -44,9 +44,15 @@ def case(name, cfg, n, a):
     tables = {v: torch.zeros((n, v[1], 8), dtype=torch.int16, device=dev) for v in VARIANTS}
     t = [0]
 
+    def refresh(variant):
+        mode, cap = inner._monster_args(*variant)
+        return lambda: env._h.check(env._h.L.rg_monsters(env._h.h, mode, cap, C.c_void_p(tables[variant].data_ptr()), C.c_void_p(env.threat.data_ptr())))
+
+    calls = {v: refresh(v) for v in VARIANTS}
+
     def step(variant):
-        """variant None: _refresh_views makes exactly the calls of a handle without the pass."""
-        env._mon_args = None if variant is None else inner._monster_args(*variant)
+        """variant None: _refresh_views makes exactly the calls of a handle without the pass (the monster pass is all this env registered)."""
+        env._refresh[:] = [] if variant is None else [calls[variant]]
         if variant is not None:
             env.monsters = tables[variant]
         env.step_keys(table[t[0] % 512])

@@ -44,11 +44,10 @@ def case(name, cfg, n, what, crop, scope, a):
     dev = env.device
     gen = torch.Generator(device=dev).manual_seed(0)
     table = env._action_keys[torch.randint(0, len(env.ACTIONS), (512, n), generator=gen, device=dev)].contiguous()
-    t = [0]
-    args = env._nov_args
+    t, update = [0], list(env._after_step)  # (the novelty update is all this env registered behind its steps)
 
     def step(on):
-        env._nov_args = args if on else None  # (off: _step_keys makes exactly the calls of a handle without novelty)
+        env._after_step[:] = update if on else []  # (off: _step_keys makes exactly the calls of a handle without novelty)
         env._step_keys(table[t[0] % 512])
         t[0] += 1
 
@@ -65,7 +64,7 @@ def case(name, cfg, n, what, crop, scope, a):
                 step(m == "on")
             torch.cuda.synchronize()
             rates[m].append(n * a.steps / (time.perf_counter() - t0) / 1e6)
-    env._nov_args = args
+    env._after_step[:] = update
     env.check_errors()
     out = {m: dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2)) for m, v in rates.items()}
     cost = round(100.0 * (statistics.median(rates["off"]) / statistics.median(rates["on"]) - 1.0), 1)

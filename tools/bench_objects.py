@@ -51,11 +51,17 @@ def case(name, cfg, n, a):
     table = env._action_keys[torch.randint(0, len(env.ACTIONS), (512, n), generator=gen, device=dev)].contiguous()
     tables = {v: torch.zeros((n, v[2], 8), dtype=torch.int16, device=dev) for v in VARIANTS}
     args = {v: inner._object_args(v[1], v[0] == "known", False, v[2]) for v in VARIANTS}
-    t = [0]
+    t, others = [0], env._refresh[:-1]  # (the object pass is the last an env registers; a guide's comes before it)
+
+    def refresh(variant):
+        kw, mode, cap = args[variant]
+        return lambda: env._h.check(env._h.L.rg_objects(env._h.h, kw, mode, cap, C.c_void_p(tables[variant].data_ptr()), C.c_void_p(env.object_count.data_ptr())))
+
+    calls = {v: refresh(v) for v in VARIANTS}
 
     def step(variant):
         """variant None: _refresh_views makes exactly the calls of a handle without the pass."""
-        env._obj_args = None if variant is None else args[variant]
+        env._refresh[:] = others if variant is None else others + [calls[variant]]
         if variant is not None:
             env.objects = tables[variant]
         env.step_keys(table[t[0] % 512] if a.guide is None else env.guide_keys)

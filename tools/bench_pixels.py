@@ -61,12 +61,13 @@ def case(name, workload, cfg, n, pixels, crop, a):
     dev = env.device
     gen = torch.Generator(device=dev).manual_seed(0)
     table = env._action_keys[torch.randint(0, len(env.ACTIONS), (512, n), generator=gen, device=dev)].contiguous()
-    px, channels, radii = env.pixels, env._px_channels, env._px_crop
+    px, channels, radii = env.pixels, 3 if pixels == "rgb" else 1, None if crop is None else env._crop_radii(crop)
+    refresh = list(env._refresh)  # (the pixel pass is all this env registered)
     t = [0]
 
     def step(on):
         """off: _refresh_views makes exactly the calls of a handle without the pass."""
-        env.pixels = px if on else None
+        env._refresh[:] = refresh if on else []
         env.step_keys(table[t[0] % 512])
         t[0] += 1
 
@@ -83,7 +84,7 @@ def case(name, workload, cfg, n, pixels, crop, a):
                 step(m == "on")
             torch.cuda.synchronize()
             rates[m].append(n * a.steps / (time.perf_counter() - t0) / 1e6)
-    env.pixels = px
+    env._refresh[:] = refresh
     out = {m: dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2)) for m, v in rates.items()}
     print(json.dumps(dict(row="rates", case=name, n_env=n, obs="gray f32", steps=a.steps, repeats=a.repeats, unit="M env-steps/s", yardstick="off", **out)), flush=True)
     env.check_errors()
