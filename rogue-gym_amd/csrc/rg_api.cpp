@@ -439,7 +439,7 @@ int rg_reset(rg_t *h) {
 int rg_step(rg_t *h, const uint8_t *keys, int keys_on_device) { return rg_step_prefix(h, keys, h->S.n, keys_on_device); }
 int rg_step_obs_gray(rg_t *h, const uint8_t *keys, int keys_on_device, uint32_t status_flag, int with_hist, float *out_dev) {
     // The pre-streamed encode: the plain f32 gray image of an ordinary handle without a bound tensor, where rgk_obs would stream it (k_obs_stream) and the step is
-    // the capped W <= 32 kernel's -- this launch's helper blocks stream every env's image beside the turns, k_obs_resid fixes up the lines the turns touched and
+    // the capped W <= 32 kernel's -- this launch's helper blocks stream every env's image beside the turns, k_obs_fix fixes up the lines the turns touched and
     // draws the Redraws.  Armed for this launch only: rg_step alone, and every observation call on its own, are what they were.
     const bool enc = h->tail_enc && !h->tail_enc_off && h->sub.empty() && (status_flag & 0x1ffu) == 0 && !with_hist && !h->bound_out && out_dev && rgk_obs_tail_capable(&h->S, &h->cfg);
     if (enc) {
@@ -452,8 +452,11 @@ int rg_step_obs_gray(rg_t *h, const uint8_t *keys, int keys_on_device, uint32_t 
     if (rc) return 1;
     if (!enc) return obs_common(h, status_flag, with_hist, 0, out_dev);
     {
+        // the group-wise pass k_obs_fix (rg_obs_fix.hip).  Development builds: a set RG_OBS_RESID_BLOCKS launches k_obs_resid instead, on that grid
+        // (rg_obs.hip rgk_obs_resid_blocks; tests/test_gpu_resid_grid.py) -- the product has no such switch.
         TimedLaunch t(h, 2, true);
-        rgk_obs_resid(&h->S, &h->cfg, out_dev, h->stream, t.start_ev(), t.stop_ev());
+        if (RG_DEV_ENV("RG_OBS_RESID_BLOCKS")) rgk_obs_resid(&h->S, &h->cfg, out_dev, h->stream, t.start_ev(), t.stop_ev());
+        else rgk_obs_fix(&h->S, &h->cfg, out_dev, h->stream, t.start_ev(), t.stop_ev());
     }
     HIPCHK(h, hipGetLastError());
     h->render_pending = false;

@@ -74,4 +74,8 @@ void rgk_archive_update(const RgState *S, const RgIoLayout *L, const uint64_t *d
 void rgk_archive_gather(const RgArchive *A, const int32_t *sid, int k, uint8_t *out, hipStream_t st);
 void rgk_archive_chosen(const RgArchive *A, const int32_t *sid, int k, const uint8_t *ok, hipStream_t st);
 const char *rgk_archive_build_id(void);
+// rg_obs_fix.hip (librogue_gym_obsfix.so)
+int rgk_obs_fix_blocks(int n);
+void rgk_obs_fix(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+const char *rgk_obs_fix_build_id(void);
 }

@@ -139,7 +139,7 @@ struct RgState {
     const float *gray_lut;  // [128] glyph -> gray value as the observation pass encodes it (rg_obs_bind fills it on the host: symbol id / symbols, one IEEE division)
     // The pre-streamed encode (rg_step_obs_gray on an eligible handle; rg_kernels.hip enc_helper): enc_helpers one-wave blocks at the back of the step launch
     // stream the f32 gray image of EVERY env into enc_out from the screen mirror as they find it, beside the turns; a turn that writes mirror bytes itself
-    // (mirror_update) leaves the set of image lines it touched in enc_rows, and the pass behind the launch (rg_obs.hip k_obs_resid) re-encodes exactly those
+    // (mirror_update) leaves the set of image lines it touched in enc_rows, and the pass behind the launch (rg_obs_fix.hip k_obs_fix) re-encodes exactly those
     // lines from the final mirror and draws the envs that keep a Redraw flag.  enc_out == NULL: the launch encodes nothing.
     float *enc_out;      // this step's observation tensor [n][1][H][W], H * W = 512
     uint16_t *enc_rows;  // [n] bit b: this launch's turn wrote a mirror byte of cells 32 b .. 32 b + 31 (one 128-byte line of the image); written by every valid lane

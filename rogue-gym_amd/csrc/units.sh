@@ -11,6 +11,8 @@ UNITS="rg_kernels.hip:-O3 rg_regen_lanes.hip:-O3 rg_obs.hip:-Os rg_crop_typed.hi
 NOVELTY_UNITS="rg_novelty.hip:-O3"
 # The cell archive likewise, librogue_gym_archive.so: its record writers are rg_state_save's bodies (rg_state_io_dev.h) under kernel names of their own.
 ARCHIVE_UNITS="rg_archive.hip:-O3"
+# The group-wise fix-up pass likewise, librogue_gym_obsfix.so: k_obs_fix shares its Redraw service with rg_obs.hip through rg_obs_dev.h (-Os, as that unit).
+OBSFIX_UNITS="rg_obs_fix.hip:-Os"
 # The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
 # Of the host units only the core reads the environment (tests/test_novelty_resources.py).
 KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"
