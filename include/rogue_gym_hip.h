@@ -137,7 +137,10 @@ int rg_done(rg_t *h, uint8_t **dev);
 /* StairRewardParallel (python/rogue_gym/envs/wrappers.py:45-64) fused into the step kernel: from the next rg_step on, `bonus` is added to
  * reward[e] whenever the dungeon level env e reports after the key is above the level it reported one step earlier (the comparison level
  * follows the reported one, so it is back at 1 after an auto-reset: a descent that ends the episode pays nothing, exactly as the wrapper).
- * The bonus is part of the reward mirror and of the compact record (rg_pack_compact / rg_allgather_compact).  0 (the default) = off. */
+ * The bonus is part of the reward mirror and of the compact record (rg_pack_compact / rg_allgather_compact).  0 (the default) = off.
+ * A call that puts an env on another level without a key -- rg_reset, rg_reset_envs / rg_reset_mask, rg_state_load, rg_archive_restore, rg_debug_descend --
+ * pays nothing and moves the comparison level with it: the first rg_step behind it compares with the level the env reported after that call, so a
+ * level-3 record loaded over a level-1 game earns no bonus, and its next descent earns one. */
 int rg_set_stair_reward(rg_t *h, float bonus);
 
 /* rg_step_obs_gray on the plain f32 gray image of a 512-cell grid stepped by the capped W <= 32 kernel (no status planes, no history plane, no config
