@@ -140,6 +140,7 @@ static int create_homog(const RgParsed &parsed, const EnvSeed *seeds, int n_env,
             const char *hv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_HELPERS"), *dv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_DELAY"), *cv = RG_DEV_ENV("ROGUE_GYM_HIP_ENC_CUT");
             h->enc_helpers = rgk_step_enc_helpers((int)n, hv ? atoi(hv) : 0);
             if (cv && atoi(cv) == 0) h->enc_helpers = 0;
+            h->step_generic = RG_DEV_ENV("ROGUE_GYM_HIP_STEP_GENERIC") != nullptr;  // (development: the generic k_step_w32<false, true>, not k_step_enc -- the A/B and the twin test)
             S.enc_delay = dv ? (uint32_t)atoi(dv) : RG_ENC_DELAY_TICKS;
         }
     }
@@ -509,7 +510,7 @@ int rg_step_prefix(rg_t *h, const uint8_t *keys, int n_keys, int keys_on_device)
         TimedLaunch t(h, 0, true);
         h->S.stair_gen = h->stair_gen++;  // reads the stair set its predecessor produced, produces the next one
         h->S.obs_par = (int32_t)(h->step_count & 1); h->bound_steps++;  // (rg_obs_bind: this launch's half of the work list)
-        (void)rgk_step(&h->S, h->d_SP, &h->cfg, dk, h->spares ? 1 : 0, no_stair_waves ? -1 : 0, h->stream, t.start_ev(), t.stop_ev());
+        (void)rgk_step(&h->S, h->d_SP, &h->cfg, dk, h->spares ? 1 : 0, no_stair_waves ? -1 : 0, h->step_generic ? 1 : 0, h->stream, t.start_ev(), t.stop_ev());
     }
     HIPCHK(h, hipGetLastError());
     if (regen) {

@@ -10,6 +10,12 @@
 
 #define WAVE 64
 #define DIST_INF 0xFFFFu
+// the grid's width and height as device code reads them from its RgConfig `c`: the config's fields.  rg_step_enc.hip, which compiles the turn code for one grid
+// alone, defines both as that grid's constants before it includes anything; everywhere else the preprocessed text is `c.width` and `c.height`.
+#ifndef RG_GRID_W
+#define RG_GRID_W(c) c.width
+#define RG_GRID_H(c) c.height
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // static tables
@@ -56,7 +62,7 @@ __device__ __forceinline__ bool can_walk(uint32_t c) {
     uint32_t s = c & C_SURF_MASK;
     return !(s == S_WALLX || s == S_WALLY || s == S_NONE);
 }
-__device__ __forceinline__ bool in_bounds(const RgConfig &c, int x, int y) { return x >= 0 && y >= 0 && x < c.width && y < c.height; }
+__device__ __forceinline__ bool in_bounds(const RgConfig &c, int x, int y) { return x >= 0 && y >= 0 && x < RG_GRID_W(c) && y < RG_GRID_H(c); }
 
 // Room::assigned_area of room id i (rooms.rs:192-209), half-open
 __device__ __forceinline__ void assigned_area(const RgConfig &c, int i, int &x0, int &y0, int &x1, int &y1) {
@@ -65,7 +71,7 @@ __device__ __forceinline__ void assigned_area(const RgConfig &c, int i, int &x0,
     x0 = cx * rsx; x1 = x0 + rsx;
     y0 = cy == 0 ? 1 : cy * rsy;
     y1 = (cy + 1) * rsy;
-    if (y1 == c.height) y1 -= 1;
+    if (y1 == RG_GRID_H(c)) y1 -= 1;
 }
 // Floor::cd_to_room_id (floor.rs:194-200): areas are disjoint, so arithmetic replaces the scan
 __device__ __forceinline__ int room_id_of(const RgConfig &c, int x, int y) {
@@ -73,7 +79,7 @@ __device__ __forceinline__ int room_id_of(const RgConfig &c, int x, int y) {
     if (y < 1 || x < 0) return -1;
     int cx = small_div_inv(x, c.inv_rsx), cy = small_div_inv(y, c.inv_rsy);
     if (cx >= c.room_num_x || cy >= c.room_num_y) return -1;
-    if ((cy + 1) * rsy == c.height && y == c.height - 1) return -1;
+    if ((cy + 1) * rsy == RG_GRID_H(c) && y == RG_GRID_H(c) - 1) return -1;
     return cy * c.room_num_x + cx;
 }
 __device__ __forceinline__ void unpack_rect(uint32_t r, int &x0, int &y0, int &x1, int &y1) {

@@ -49,6 +49,7 @@ struct rg_handle {
     // rg_tail_encode(h, 0) keeps the two full passes; armed per call.
     bool tail_enc = false, tail_enc_off = false;
     int enc_helpers = 0;   // helper blocks per launch (rgk_step_enc_helpers); 0: none, the pass encodes every env
+    bool step_generic = false;  // development library only: the pre-streaming launch stays on k_step_w32<false, true> (rgk_step generic_enc)
     int bound_steps = 0;   // k_step launches since the bound tensor was last written: its in-place pass works from the list of exactly ONE
     int stair_gen = 0;           // producers of the stair set launched so far (k_build, k_step, the debug descent; rg_state.h)
     float *obs_scratch = nullptr;  // rg_obs_host: device-side observation buffer, kept between calls

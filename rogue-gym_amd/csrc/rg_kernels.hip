@@ -131,7 +131,7 @@ __device__ __forceinline__ void activate_room(const RgState &S, const RgConfig &
 template <int GM>
 __device__ __forceinline__ void player_in_init(const RgState &S, const RgConfig &c, Env &E, int x, int y) {
     lds_u16 *cell = E.lc;
-    int W = c.width;
+    int W = RG_GRID_W(c);
     int rid = room_id_of(c, x, y);
     if (rid >= 0) {
         uint32_t meta = gen_meta<GM>(S, E, rid);
@@ -173,7 +173,7 @@ __device__ __forceinline__ uint64_t rect_ballot(const RgConfig &c, const Env &E,
     bool in = false;
     if (t < area) {
         const int yy = small_div(t, rw), xx = t - yy * rw;
-        in = (E.lc[(y0 + yy) * c.width + x0 + xx] & bits) && POS(x0 + xx, y0 + yy) != excl;
+        in = (E.lc[(y0 + yy) * RG_GRID_W(c) + x0 + xx] & bits) && POS(x0 + xx, y0 + yy) != excl;
     }
     return __ballot(in);
 }
@@ -412,7 +412,7 @@ __device__ __forceinline__ void connect_rooms(const RgState &S, const RgConfig &
 // The cells of one corridor are distinct, so the lanes fetch them all up front (cell i in lane i), the gen_attr draws run in
 // registration order on the scalar unit, and the lanes write their cells back together (register_cell's update rule).
 __device__ __forceinline__ void paint_corridor(const RgConfig &c, Env &E, uint32_t a, uint32_t b, uint32_t level) {
-    const int W = c.width, lane = threadIdx.x;
+    const int W = RG_GRID_W(c), lane = threadIdx.x;
     const int sx = POS_X(a), sy = POS_Y(a), ex = POS_X(a >> 16), ey = POS_Y(a >> 16);
     const int bend = b & 0xff;
     const bool down = (b >> 8) & 1;
@@ -515,7 +515,7 @@ __device__ __forceinline__ void dig_maze(const RgState &S, const RgConfig &c, En
     uint16_t *gs = S.maze_stack + (size_t)E.e * S.maze_cap;
     const bool in_lds = E.stk_lds && mw * mh <= GEN_STACK_LDS;
     const bool bitmap = mw * mh <= 64;  // dug nodes as a 64-bit scalar mask: the neighbour tests never touch memory
-    const int W = c.width;
+    const int W = RG_GRID_W(c);
     const uint16_t dug = (uint16_t)(S_NONE | C_MAZE);  // the room's area is untouched (fresh Field) until its maze is painted
     E.lc[y0 * W + x0] = dug;
     uint64_t seen = 1ull;
@@ -568,7 +568,7 @@ __device__ __forceinline__ void dig_maze(const RgState &S, const RgConfig &c, En
 template <int GM>
 __device__ __forceinline__ typename RoomSet<GM>::type gen_structure(const RgState &S, const RgConfig &c, Env &E, Prof &pf) {
     typedef typename RoomSet<GM>::type rmask_t;
-    const int W = c.width, HW = W * c.height, n = E.n, e = E.e;
+    const int W = RG_GRID_W(c), HW = W * RG_GRID_H(c), n = E.n, e = E.e;
     const int rnx = c.room_num_x, nrooms = rnx * c.room_num_y;
     lds_u16 *cell = E.lc;
     const uint32_t level = ++E.dlevel;
@@ -745,7 +745,7 @@ __device__ __forceinline__ typename RoomSet<GM>::type gen_structure(const RgStat
 }
 template <int GM>
 __device__ __forceinline__ void gen_populate(const RgState &S, const RgConfig &c, Env &E, Prof &pf) {
-    const int W = c.width, H = c.height, n = E.n, e = E.e;
+    const int W = RG_GRID_W(c), H = RG_GRID_H(c), n = E.n, e = E.e;
     const int nrooms = c.room_num_x * c.room_num_y;
     lds_u16 *cell = E.lc;
     const uint32_t level = E.dlevel;
@@ -799,7 +799,7 @@ __device__ __forceinline__ void place_player(const RgState &S, const RgConfig &c
     uint32_t pos = 0;
     floor_select<GM>(S, c, E, non_empty, 1, pos);
     E.px = POS_X(pos); E.py = POS_Y(pos);
-    E.on_stairs = (uni(E.lc[E.py * c.width + E.px]) & C_SURF_MASK) == S_STAIR;  // (select_cell only avoids characters: the stairs are a legal spot)
+    E.on_stairs = (uni(E.lc[E.py * RG_GRID_W(c) + E.px]) & C_SURF_MASK) == S_STAIR;  // (select_cell only avoids characters: the stairs are a legal spot)
     player_in_init<GM>(S, c, E, E.px, E.py);
 }
 
@@ -885,7 +885,7 @@ static_assert(sizeof(Rng) == 16, "Rng is 4 words");
 // load_structure: the generator's state as gen_structure would have left it (grid, room / gold tables, streams, level, non-empty set).
 template <int GM>
 __device__ __forceinline__ typename RoomSet<GM>::type load_structure(const RgState &S, const RgConfig &c, Env &U, int real_e, int real_n, const GenTabs *T) {
-    const int HW = c.width * c.height, nrooms = c.room_num_x * c.room_num_y, lane = threadIdx.x;
+    const int HW = RG_GRID_W(c) * RG_GRID_H(c), nrooms = c.room_num_x * c.room_num_y, lane = threadIdx.x;
     const RgNext *NX = S.nx;  // (each pointer fetched where it is used: the copy of the struct held eight of them in SGPRs through the whole load)
     const uint16_t *src = NX->cell + (size_t)real_e * HW;
     if ((HW & 7) == 0) {
@@ -919,7 +919,7 @@ __device__ __forceinline__ typename RoomSet<GM>::type load_structure(const RgSta
 template <int GM, bool WT = false>
 __device__ __forceinline__ void gen_service(const RgState &S, const RgConfig &c, Env &E, int lane, int e, bool need, bool is_build_in,
                                             uint16_t *lds_grid, Prof &pf, const uint64_t from_nx = 0, const uint64_t struct_only = 0) {
-    const int HW = c.width * c.height, nrooms = c.room_num_x * c.room_num_y;
+    const int HW = RG_GRID_W(c) * RG_GRID_H(c), nrooms = c.room_num_x * c.room_num_y;
     uint8_t *slot = reinterpret_cast<uint8_t *>(lds_grid);
     const GenTabs TT = gen_tabs(slot, HW, nrooms), *T = &TT;
     uint64_t m = __ballot(need);
@@ -1118,6 +1118,7 @@ extern __shared__ __align__(16) uint8_t g_smem[];
 // BUILD_EPB envs per wave: a wave generates its levels one after the other, so fewer envs per wave = more waves per SIMD to overlap the
 // generator's latencies (create / rg_reset only; not on the step path)
 #define BUILD_EPB 16
+#ifndef RG_STEP_ENC_UNIT  // (rg_step_enc.hip includes this file for the device functions and defines one kernel of its own: no kernel or launcher of this unit in that library)
 template <int GM>  // (one kernel per generator instance: two in one kernel cost the capped k_regen 20 bytes of scratch)
 __global__ void __launch_bounds__(WAVE) k_build(RgState S, RgConfig c) {
     const int lane = threadIdx.x;
@@ -1145,6 +1146,7 @@ __global__ void __launch_bounds__(WAVE) k_build(RgState S, RgConfig c) {
     S.done[e] = 0;
     klog_new_episode(S, e);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Partial reset (rg_reset_envs / rg_reset_mask): rebuild the envs of a device-resident list
@@ -1152,6 +1154,7 @@ __global__ void __launch_bounds__(WAVE) k_build(RgState S, RgConfig c) {
 // k_reset_compact: mask -> list.  One coalesced byte per lane, a ballot, one atomic per wave that has any; the order of the list is whatever the atomics
 // give (envs are independent, a reseeding env's build ticket is its own).  cnt[0] was zeroed on the stream before this launch.
 #define COMPACT_THREADS 256
+#ifndef RG_STEP_ENC_UNIT
 __global__ void __launch_bounds__(COMPACT_THREADS) k_reset_compact(const uint8_t *__restrict__ mask, int n, int32_t *__restrict__ list, uint32_t *__restrict__ cnt) {
     const int e = blockIdx.x * COMPACT_THREADS + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
     const bool on = e < n && mask[e] != 0;
@@ -1195,11 +1198,13 @@ __global__ void __launch_bounds__(WAVE) k_build_list(RgState S, RgConfig c, cons
     klog_new_episode(S, e);
     mark[e] = 1;
 }
+#endif
 
 // Parity / property-test hook (rg_debug_descend): every env takes Dungeon::new_level + actions::new_level's player placement as if it had
 // pressed '>' on the stairs, without the turn around it -- the descent path of k_step (gen_service, is_build = false) on its own, so tests
 // can look at levels 2..30 of thousands of seeds without walking there.
 __device__ __forceinline__ void snapshot_walk_service(const RgState &S, const RgConfig &c, int lane, int e, bool want);
+#ifndef RG_STEP_ENC_UNIT
 template <int GM>
 __global__ void __launch_bounds__(WAVE) k_debug_descend(RgState S, RgConfig c) {
     const int lane = threadIdx.x;
@@ -1223,6 +1228,7 @@ __global__ void __launch_bounds__(WAVE) k_debug_descend(RgState S, RgConfig c) {
     S.flags[e] = (S.flags[e] & (RG_FLAG_TERMINAL | RG_FLAG_DEAD)) | RG_FLAG_REDRAW | RG_FLAG_HIST_DIRTY | E.err;
     if (E.err) atomicOr(S.err_any, E.err);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // k_regen: background producer of the spare level-1 states (runs on a low-priority side stream)
@@ -1314,6 +1320,7 @@ __device__ __forceinline__ void regen_body(const RgState &SP, const RgConfig &c,
 // the slots of k_step's blocks (and, the host running hundreds of steps ahead of the GPU, long before the spares it is to refill are consumed), and with
 // no event on the handle's stream.  The wait is bounded by the wall clock (s_memrealtime, 100 MHz): one second -- a k_step that never starts must not
 // hang rg_sync / rg_destroy, which drain this stream; after a time-out the generator merely runs early.
+#ifndef RG_STEP_ENC_UNIT
 __global__ void __launch_bounds__(WAVE) k_regen_gate(const uint32_t *__restrict__ mark, uint32_t target, uint32_t *__restrict__ err_any) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     while ((int32_t)(__hip_atomic_load(mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
@@ -1325,6 +1332,7 @@ __global__ void __launch_bounds__(WAVE) k_regen_gate(const uint32_t *__restrict_
 template <int GM> __global__ void __launch_bounds__(WAVE) RG_REGEN_ATTR k_regen(RgState SP, RgConfig c, int epb, int max_claims, int spares) { regen_body<GM>(SP, c, epb, max_claims, spares); }
 // (the 384-room instance does not fit the 128-register cap without scratch; its configs run at one step wave per SIMD anyway)
 __global__ void __launch_bounds__(WAVE) k_regen_huge(RgState SP, RgConfig c, int epb, int max_claims, int spares) { regen_body<2>(SP, c, epb, max_claims, spares); }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // wave-cooperative bit-parallel BFS (Floor::make_dist_map, floor.rs:395-416)
@@ -1386,7 +1394,7 @@ template <int WW, bool NARROW, bool UP> __device__ __forceinline__ RowBits<WW> r
 template <int WW, bool NARROW>
 __device__ __forceinline__ void bfs_rows(const RgState &S, const RgConfig &c, uint64_t *lds_hi /* [10][WW][64] high planes */, bool active, int env, int tx, int ty,
                                          int slot, int row) {
-    const int W = c.width, H = c.height, HW = W * H, lane = threadIdx.x;
+    const int W = RG_GRID_W(c), H = RG_GRID_H(c), HW = W * H, lane = threadIdx.x;
     const uint16_t *cell = S.cell + (size_t)env * HW;
     const bool row_ok = active && row < H;
     RowBits<WW> wk, vis, fr, inject, p0, p1, p2;  // the ten high planes live in LDS (60 registers for the widest grid otherwise: the step kernel
@@ -1520,7 +1528,7 @@ __device__ __forceinline__ void bfs_rows(const RgState &S, const RgConfig &c, ui
 // ROW16: H <= 16, a group of rows is one DPP row (row_shr1 / row_shl1 above); else whole-wave shifts and a select per level.
 template <bool ROW16>
 __device__ __forceinline__ void bfs_rows_w32(const RgState &S, const RgConfig &c, bool active, int env, int tx, int ty, int slot, int row) {
-    const int W = 32, H = c.height, HW = W * H;
+    const int W = 32, H = RG_GRID_H(c), HW = W * H;
     const uint16_t *cell = S.cell + (size_t)env * HW;
     const bool row_ok = active && row < H;
     uint32_t wk = 0;
@@ -1654,7 +1662,7 @@ __device__ __forceinline__ void row_walk_mask(const uint16_t *rowp, int W, uint3
 template <int WN>
 __device__ __forceinline__ bool bfs_rows_n32(const RgState &S, const RgConfig &c, bool active, int env, int tx, int ty, int slot, int row, uint64_t grp_lanes,
                                              const lds_u32 *mcol, bool own) {
-    const int W = c.width, H = c.height, HW = W * H;
+    const int W = RG_GRID_W(c), H = RG_GRID_H(c), HW = W * H;
     const uint16_t *cell = S.cell + (size_t)env * HW;
     const bool row_ok = active && row < H;
     uint32_t wk[WN], wu[WN], wd[WN], vis[WN], fr[WN], inject[WN], p0[WN], p1[WN], p2[WN], ph[9][WN], want[WN];
@@ -1793,7 +1801,7 @@ __device__ __forceinline__ bool bfs_rows_n32(const RgState &S, const RgConfig &c
 template <int BW>
 __device__ __forceinline__ bool bfs_service(const RgState &S, const RgConfig &c, uint64_t *lds, uint64_t need, int e, int px, int py, int map_slot, int lane, const lds_u32 *mcbase,
                                             uint64_t own_req) {
-    const int H = c.height;
+    const int H = RG_GRID_H(c);
     const int rows_pow2 = H <= 16 ? 16 : (H <= 32 ? 32 : 64);
     const int G = WAVE / rows_pow2;
     const int grp = lane / rows_pow2, row = lane - grp * rows_pow2;
@@ -1832,7 +1840,7 @@ __device__ __forceinline__ bool dist_map_sufficient(const RgState &S, const RgCo
     for (int q0 = 0; q0 < nrooms; q0 += 2) {  // two monsters per round: their probes are in flight together (one load -> test per monster was a round trip each)
         const bool has1 = q0 + 1 < nrooms;
         const uint32_t wa = E.mc[q0 * WAVE], wb = E.mc[(has1 ? q0 + 1 : q0) * WAVE];
-        const uint32_t da = dist[POS_Y(wa) * c.width + POS_X(wa)], db = dist[POS_Y(wb) * c.width + POS_X(wb)];
+        const uint32_t da = dist[POS_Y(wa) * RG_GRID_W(c) + POS_X(wa)], db = dist[POS_Y(wb) * RG_GRID_W(c) + POS_X(wb)];
         if (((wa >> 24) & (MF_PENDING | MF_RANDOM)) == MF_PENDING && da == DIST_INF) ok = false;
         if (has1 && ((wb >> 24) & (MF_PENDING | MF_RANDOM)) == MF_PENDING && db == DIST_INF) ok = false;
     }
@@ -1847,7 +1855,7 @@ __device__ __forceinline__ void snapshot_walk_service(const RgState &S, const Rg
     if (want) todo = (uint32_t)S.dc_part[e] & ~(uint32_t)S.dc_own[e];
     uint64_t m = __ballot(todo != 0);
     if (!m) return;
-    const int W = c.width, H = c.height, wpr = RG_WALK_WORDS(W);  // = the WN of the step class that reads it back (bfs_rows_n32)
+    const int W = RG_GRID_W(c), H = RG_GRID_H(c), wpr = RG_WALK_WORDS(W);  // = the WN of the step class that reads it back (bfs_rows_n32)
     while (m) {
         const int src = __ffsll((long long)m) - 1;
         m &= m - 1;
@@ -1982,7 +1990,7 @@ __device__ __forceinline__ void win_load(const RgConfig &c, const uint16_t *cell
         for (int i = -2; i <= 2; i++) {
             const int x = ox + i, y = oy + j;
             const bool in = in_bounds(c, x, y);
-            const uint32_t val = cell[in ? y * c.width + x : oy * c.width + ox];  // unconditional load: all 25 are in flight together
+            const uint32_t val = cell[in ? y * RG_GRID_W(c) + x : oy * RG_GRID_W(c) + ox];  // unconditional load: all 25 are in flight together
             t[WIN_K(i, j)] = in ? val : 0u;
             if (in) w.inb |= 1u << WIN_K(i, j);
             if (i >= -RG_NX_NEAR && i <= RG_NX_NEAR && j >= -RG_NX_NEAR && j <= RG_NX_NEAR) st = st || (in && (val & C_SURF_MASK) == S_STAIR);
@@ -1997,7 +2005,7 @@ __device__ __forceinline__ void win_flush(const RgConfig &c, uint16_t *cell, Win
     for (int j = -2; j <= 2; j++)
 #pragma unroll
         for (int i = -2; i <= 2; i++)
-            if ((w.dirty >> WIN_K(i, j)) & 1u) cell[(w.oy + j) * c.width + w.ox + i] = (uint16_t)WV(w, WIN_K(i, j));
+            if ((w.dirty >> WIN_K(i, j)) & 1u) cell[(w.oy + j) * RG_GRID_W(c) + w.ox + i] = (uint16_t)WV(w, WIN_K(i, j));
     w.dirty = 0;
 }
 // LDS of a step wave: every per-lane column FIRST, at compile-time offsets -- window, parked overlay words + glyph bytes, monster cache (its length is the
@@ -2162,7 +2170,7 @@ __device__ __forceinline__ void fill_service(const RgState &S, const RgConfig &c
             const int rw = x1 - x0, area = rw * (y1 - y0);
             for (int t = lane; t < area; t += WAVE) {
                 const int yy = small_div(t, rw), xx = t - yy * rw;
-                uint16_t *p = cell + (y0 + yy) * c.width + x0 + xx;
+                uint16_t *p = cell + (y0 + yy) * RG_GRID_W(c) + x0 + xx;
                 *p = kind ? (uint16_t)(*p | C_DRAWN | C_VISIBLE) : (uint16_t)(*p & ~C_VISIBLE);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the owner lane's window write-back (and a following fill) must land after these stores
@@ -2272,7 +2280,7 @@ __device__ __forceinline__ bool dist_cache_lookup(const RgState &S, const Env &E
 // EnemyHandler::move_actives moves + actions::move_active_enemies attacks
 // (enemies.rs:366-424, rogue/mod.rs:339-397, actions.rs:82-119, fight.rs:41-72)
 __device__ __forceinline__ bool monsters_move(const RgState &S, const RgConfig &c, Env &E, int map_slot, uint32_t &react) {
-    const int nrooms = c.room_num_x * c.room_num_y, W = c.width, e = E.e;
+    const int nrooms = c.room_num_x * c.room_num_y, W = RG_GRID_W(c), e = E.e;
     const uint16_t *dist = S.dc_map + ((size_t)e * RG_DIST_SLOTS + (map_slot < 0 ? 0 : map_slot)) * S.hw;
     const uint32_t ppos = POS(E.px, E.py);
     int n_att = 0;
@@ -2385,7 +2393,7 @@ __device__ __forceinline__ bool monsters_move(const RgState &S, const RgConfig &
 
 // What a cell shows without overlays (rg_obs.hip's decode, core/src/lib.rs:264-285 + rogue/mod.rs:278-300): the glyph, bit 7 = an object on it is drawn
 __device__ __forceinline__ uint32_t base_glyph(const RgConfig &c, uint32_t v, int y) {
-    const bool inner = y >= 1 && y < c.height - 1;
+    const bool inner = y >= 1 && y < RG_GRID_H(c) - 1;
     uint32_t gl = ' ';
     if (inner && (v & C_VISIBLE)) gl = glyph_of(v);
     if (inner && (v & (C_VISIBLE | C_DRAWN))) gl = ((v & C_GOLD) ? (uint32_t)'*' : gl) | 0x80u;
@@ -2403,7 +2411,7 @@ __device__ __forceinline__ uint32_t base_glyph(const RgConfig &c, uint32_t v, in
 // ENC: the launch pre-streams the gray images (enc_helper) -- every put() adds the image line of its cell, idx >> 5 (32 cells = one 128-byte line), to `rows`
 template <bool BND, bool ENC = false>  // BND: the handle has a bound observation tensor (rg_obs_bind) -- a step-kernel instance of its own, so that the ordinary one carries none of it
 __device__ __forceinline__ bool mirror_update(const RgState &S, const RgConfig &c, const Env &E, const Win &w, uint32_t react, int rid0, uint32_t &rows) {
-    const int W = c.width, nrooms = c.room_num_x * c.room_num_y, n = E.n;
+    const int W = RG_GRID_W(c), nrooms = c.room_num_x * c.room_num_y, n = E.n;
     // (the env index through an opaque move: the addresses below are then computed HERE -- left alone, the compiler computes `S.ovl + ... + e`, `S.hist + e * hw`
     // at the top of the kernel, spills them, and reloads them here one by one, each reload waiting for every store the turn has issued: 5 us per wave)
     int e = E.e;
@@ -3160,6 +3168,7 @@ __device__ __forceinline__ void step_wave(const RgState &S, const RgState *__res
         if (lane == 0) t = atomicAdd(next, 1u); \
         i0 = STAIR_BLOCKS + (int)uni(t); \
     }
+#ifndef RG_STEP_ENC_UNIT  // (to the end of the file: rg_step_enc.hip spells its one kernel with the body above and brings a launcher of its own)
 template <int BW, bool BND = false>
 __global__ void __launch_bounds__(WAVE) k_step(RgState S, const RgState *__restrict__ SPd, RgConfig c, const uint8_t *__restrict__ keys, int use_spares, int stage_off, int epw,
                                                int parity) {
@@ -3279,7 +3288,7 @@ int rgk_step_enc_helpers(int n, int want) {
     if (want > 0) h = want > 2048 ? 2048 : want;
     return h < nruns ? h : nruns;
 }
-int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, int generic_enc, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const bool bnd = S->obs_list != nullptr && rgk_step_bound_capable(c);
     int hw = c->width * c->height;
     const bool n32 = c->width <= 96 && hw <= 4096;
@@ -3302,7 +3311,12 @@ int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const u
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_step_huge), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess && dev >= 0 && dev < 64) raised[dev] = smem;
         }
         launch(k_step_huge);
-    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) launch(k_step_w32<true>); else if (S->enc_out) launch(k_step_w32<false, true>); else launch(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
+    } else if (c->width <= 32 && gen_mode_of(c) == 0) { if (bnd) launch(k_step_w32<true>);
+        // (the pre-streaming launch of the headline class -- 32 x 16 cells, rgk_step_enc_capable -- is k_step_enc's, the instance compiled for that class alone in
+        // librogue_gym_stepenc.so: the same grid, LDS, arguments and events.  generic_enc: the development library's switch back to the generic instance)
+        // (rgk_step_enc_takes: what the kernel takes for granted about the handle -- spares and next-level structures, no action history, no wave profile)
+        else if (!generic_enc && rgk_step_enc_capable(c) && rgk_step_enc_takes(S, use_spares, parity)) rgk_step_enc(S, SP_dev, c, keys, use_spares, stage_off, epw, parity, (int)grid.x, smem, st, ev0, ev1);
+        else if (S->enc_out) launch(k_step_w32<false, true>); else launch(k_step_w32<false>); }   // (its generator instance holds 32-bit room sets)
     else if (n32 && c->width <= 64) launch(k_step<1>);                        // ... a 32-column grid with 33..64 rooms (e.g. 32x48 with 8x5) steps here
     else if (n32) { if (bnd) launch(k_step<2, true>); else launch(k_step<2>); }
     else if (c->width <= 128) launch(k_step<3>);
@@ -3347,3 +3361,4 @@ void rgk_regen(const RgState *SP, const RgConfig *c, int bulk, int spares, const
     }
 }
 }
+#endif  // RG_STEP_ENC_UNIT

@@ -21,7 +21,8 @@ size_t rgk_step_lds_per_cu(const RgConfig *c);
 int rgk_step_bound_capable(const RgConfig *c);
 int rgk_step_tail_capable(const RgConfig *c);
 int rgk_step_enc_helpers(int n, int want);
-int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+int rgk_step(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int parity, int generic_enc, hipStream_t st, hipEvent_t ev0,
+             hipEvent_t ev1);
 void rgk_debug_descend(const RgState *S, const RgConfig *c, hipStream_t st);
 void rgk_regen_gate(const uint32_t *mark, uint32_t target, uint32_t *err_any, hipStream_t st);
 void rgk_regen(const RgState *SP, const RgConfig *c, int bulk, int spares, const uint32_t *mark, uint32_t target, uint32_t *err_any, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
@@ -78,4 +79,10 @@ const char *rgk_archive_build_id(void);
 int rgk_obs_fix_blocks(int n);
 void rgk_obs_fix(const RgState *S, const RgConfig *c, float *out, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 const char *rgk_obs_fix_build_id(void);
+// rg_step_enc.hip (librogue_gym_stepenc.so)
+int rgk_step_enc_capable(const RgConfig *c);
+int rgk_step_enc_takes(const RgState *S, int use_spares, int parity);
+void rgk_step_enc(const RgState *S, const RgState *SP_dev, const RgConfig *c, const uint8_t *keys, int use_spares, int stage_off, int epw, int parity, int blocks, size_t smem,
+                  hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+const char *rgk_step_enc_build_id(void);
 }

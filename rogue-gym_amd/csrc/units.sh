@@ -13,6 +13,9 @@ NOVELTY_UNITS="rg_novelty.hip:-O3"
 ARCHIVE_UNITS="rg_archive.hip:-O3"
 # The group-wise fix-up pass likewise, librogue_gym_obsfix.so: k_obs_fix shares its Redraw service with rg_obs.hip through rg_obs_dev.h (-Os, as that unit).
 OBSFIX_UNITS="rg_obs_fix.hip:-Os"
+# The step kernel of the headline class likewise, librogue_gym_stepenc.so: k_step_enc is rg_kernels.hip's turn code (which the unit includes) compiled for the
+# 32 x 16 grid alone (-O3, as that unit); k_step_w32<false, true> keeps its place and its registers in librogue_gym_hip.so.
+STEPENC_UNITS="rg_step_enc.hip:-O3"
 # The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
 # Of the host units only the core reads the environment (tests/test_novelty_resources.py).
 KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"

@@ -19,8 +19,15 @@ for u in $OBSFIX_UNITS; do   # the group-wise fix-up pass takes the variant's fl
     hipcc $F ${u##*:} -c $src -o $obj &
     PIDS="$PIDS $!"; FOBJS="$FOBJS $obj"
 done
+EOBJS=
+for u in $STEPENC_UNITS; do  # ... and so does the step kernel of the headline class (k_step_enc)
+    src=${u%%:*}; obj=$B/${src%.*}.o
+    hipcc $F ${u##*:} -c $src -o $obj &
+    PIDS="$PIDS $!"; EOBJS="$EOBJS $obj"
+done
 for p in $PIDS; do wait $p; done   # (a failed compile ends the script: set -e)
 hipcc --offload-arch=gfx950 -shared $FOBJS -o ../variants/librogue_gym_obsfix_$name.so
+hipcc --offload-arch=gfx950 -shared $EOBJS -o ../variants/librogue_gym_stepenc_$name.so
 # (the novelty pass and the cell archive are the product's own libraries beside the variant's directory: csrc/build.sh or __graft_entry__.build() made them)
-hipcc --offload-arch=gfx950 -shared $OBJS -L.. -L../variants -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_obsfix_$name '-Wl,-rpath,$ORIGIN/..:$ORIGIN' -o ../variants/librogue_$name.so
+hipcc --offload-arch=gfx950 -shared $OBJS -L.. -L../variants -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_obsfix_$name -lrogue_gym_stepenc_$name '-Wl,-rpath,$ORIGIN/..:$ORIGIN' -o ../variants/librogue_$name.so
 echo "built variants/librogue_$name.so"
