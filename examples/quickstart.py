@@ -133,6 +133,21 @@ for kw in (dict(guide="stairs", guide_secrets=True), dict(guide="explore")):
           % (", ".join("%s=%r" % kv for kv in kw.items()), venv.status[:, 0].float().mean().item(), 100 * (venv.guide_dist < 0).float().mean().item()))
     venv.close()
 
+# 3h'. a policy network in the loop: a random linear "network" reads the gray image and step_logits() turns its [N, 11] logits into keys in one launch -- the
+#      softmax over the keys that are legal now, a draw, the behaviour log-probability and the entropy for the rollout buffer (no autograd: the learner's update
+#      recomputes log pi from action_mask).  Then the DAgger form: with probability beta the explorer's key is played, logp stays the policy's own ----------
+venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, action_mask=True, guide="explore")
+net = torch.nn.Linear(venv.obs[0].numel(), len(venv.ACTIONS), device=venv.device)
+with torch.no_grad():
+    for beta in (0.0, 0.5):
+        logp_sum = ent_sum = taught = 0.0
+        for t in range(100):
+            obs, reward, done, res = venv.step_logits(net(venv.obs.flatten(1)), temperature=1.0, epsilon=0.05, teacher=venv.guide_keys, beta=beta, seed=3)
+            logp_sum, ent_sum, taught = logp_sum + res.logp.mean(), ent_sum + res.entropy.mean(), taught + (res.source == 2).float().mean()
+        print("HipVecRogueEnv.step_logits(beta=%.1f): keys %s %s, mean behaviour logp %.2f, entropy %.2f nats, %.0f %% of the keys were the explorer's, dungeon level %.2f"
+              % (beta, tuple(res.keys.shape), res.keys.dtype, float(logp_sum) / 100, float(ent_sum) / 100, float(taught), venv.status[:, 0].float().mean().item()))
+venv.close()
+
 # 3i. episode accounting and the scout reward on the device: what ended (died / time_limit), the finished episode's return and length, and one point per
 #     map cell seen for the first time on a level -- no host trip until pop_episodes() ---------------------------------------------------------------
 venv = HipVecRogueEnv([dict(MINI, seed=i) for i in range(4096)], max_steps=100, image_setting=ImageSetting(DungeonType.GRAY, StatusFlag.EMPTY, False), device=0, scout=True, episode_log=8192, guide="explore")

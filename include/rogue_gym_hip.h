@@ -290,6 +290,41 @@ int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, in
                         const uint8_t *keys, int n_keys, uint8_t *out);
 uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count);
 
+/* MASKED CATEGORICAL ACTIONS FROM POLICY LOGITS: for each env one key drawn from the softmax of its row of logits over the keys that are legal now (the
+ * rule of the action mask above), with the behaviour log-probability and the entropy, on the device -- what stands between a policy network and rg_step.
+ * The rule, its random word and the bit fields of that word are stated once, in rogue-gym_amd/csrc/rg_policy.h; the kernel and the host twin agree bit for
+ * bit on every output, floats included (integer operations, f32 add / multiply / fma and one division only; fixed polynomials for exp2 and ln).
+ *   Logits: [n_env][n_keys] of dtype RG_OBS_F32 / RG_OBS_F16 / RG_OBS_BF16, row e for env e of the handle, 16-bit values widened exactly, multiplied by
+ *     inv_temp.  NaN and -inf weigh 0, +inf is the largest finite value.  pi = the softmax over the LEGAL keys of the list; an illegal key has probability 0.
+ *     A weight below 2^-125 of the largest is 0.  No legal key weighs: pi is uniform over the legal keys and the source is 1.
+ *   mode RG_ACT_SAMPLE: one draw from pi -- t = u * S against the running sum of the weights in list order, the first legal key whose sum exceeds t.  With
+ *     probability beta the env plays teacher_dev[e] instead, if that key is in the list and legal now (otherwise the policy's draw stands); with probability
+ *     epsilon a uniform draw among the legal keys.  RG_ACT_GREEDY: the legal key with the largest logit, ties to the lowest index.  RG_ACT_GIVEN: no draw;
+ *     given_dev[e] is the action whose log-probability is wanted (out of range or illegal: -inf).
+ *   Outputs, each [n_env], every one but key_dev nullable: key u8, the byte rg_step takes; action i32, its index in the list; logp f32 = ln pi(action), ALWAYS
+ *     under the pure masked softmax, also when epsilon or the teacher chose (-inf where pi gives 0); entropy f32 of pi in nats; source u8 0 policy, 1 uniform,
+ *     2 teacher, 3 none.  mask_dev (nullable) = u8 [n_env][n_keys], exactly what the action-mask call writes.  An env with no legal key (the Grave modal)
+ *     answers keys[0], action 0, logp 0, entropy 0, source 3.  In RG_ACT_GIVEN key_dev may be NULL too.
+ *   The draw is a stateless function of (opts.seed, env index of the handle, opts.draw) with a stream constant of its own: equal seed and draw in the
+ *     action-mask sample and here are unrelated.  The same arguments on the same states give the same bytes.
+ *   Asynchronous on the handle's stream; reads game state only, as the action mask does; config groups and mixed sizes are served.  A handle that never calls
+ *   it allocates and launches nothing for it.
+ *   Refused, non-zero with a message naming the argument, nothing launched: n_keys or a key as for the action mask; an unknown dtype or mode; logits_dev NULL
+ *   or not 16-byte aligned, mask_dev not 16-byte aligned; opts NULL; inv_temp not finite or not > 0; epsilon or beta outside [0, 1] or epsilon + beta > 1;
+ *   beta > 0 without teacher_dev; RG_ACT_GIVEN without given_dev; key_dev NULL in a mode that draws.
+ * rg_act_host (stateless, needs no device): the same rule for ONE env given as a host grid, as the action-mask host entry takes it; `logits` = n_keys
+ *   elements of dtype; env = the env index of the draw; teacher_key = a key byte or -1; given = the action of RG_ACT_GIVEN.  Outputs nullable. */
+#define RG_ACT_SAMPLE 0u
+#define RG_ACT_GREEDY 1u
+#define RG_ACT_GIVEN  2u
+typedef struct rg_act_opts { float inv_temp, epsilon, beta; uint32_t mode; uint64_t seed, draw; } rg_act_opts;
+int rg_act(rg_t *h, const uint8_t *keys, int n_keys, const void *logits_dev, int dtype, const rg_act_opts *opts,
+           const uint8_t *teacher_dev, const int32_t *given_dev,
+           uint8_t *key_dev, int32_t *action_dev, float *logp_dev, float *entropy_dev, uint8_t *source_dev, uint8_t *mask_dev);
+int rg_act_host(const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys,
+                const void *logits, int dtype, const rg_act_opts *opts, uint32_t env, int teacher_key, int given,
+                uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source);
+
 /* SHORTEST-PATH FIELDS AND TEACHER KEYS: for each env the number of moves from every cell to the nearest goal cell, that number at the player's cell, and the
  * key that takes the player one move closer, on the device.  The moves are the engine's own: rg_action_mask's move test (Floor::can_move_impl as the player).
  * The field is PRIVILEGED: it sees stairs, gold and passages the player has not discovered.  It is a teacher (imitation, DAgger), a shaping potential

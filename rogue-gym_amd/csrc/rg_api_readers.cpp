@@ -29,6 +29,22 @@ int rg_action_mask_host(const uint16_t *cells, int height, int width, int px, in
     return rgh_action_mask(g_create_err, cells, height, width, px, py, dead, keys, n_keys, out);
 }
 uint32_t rg_sample_index(uint64_t seed, uint32_t env, uint64_t draw, uint32_t count) { return rg_sample_index_of(seed, env, draw, count); }
+int rg_act(rg_t *h, const uint8_t *keys, int n_keys, const void *logits_dev, int dtype, const rg_act_opts *opts, const uint8_t *teacher_dev, const int32_t *given_dev,
+           uint8_t *key_dev, int32_t *action_dev, float *logp_dev, float *entropy_dev, uint8_t *source_dev, uint8_t *mask_dev) {
+    uint8_t list[RG_MASK_MAX_KEYS];
+    if (mask_keys_check(h->err, "rg_act", keys, n_keys, list)) return 1;
+    if (act_opts_check(h->err, "rg_act", opts, dtype, teacher_dev != nullptr, given_dev != nullptr, key_dev != nullptr, "teacher_dev", "given_dev", "key_dev")) return 1;
+    if (!logits_dev || ((uintptr_t)logits_dev & 15)) { h->err = "rg_act: logits_dev must be a 16-byte aligned device pointer"; return 1; }
+    if ((uintptr_t)mask_dev & 15) { h->err = "rg_act: mask_dev must be a 16-byte aligned device pointer"; return 1; }
+    const rg_act_opts o = *opts;
+    return reader_launch(h, [=](rg_t *l) {
+        rgk_act(&l->S, &l->cfg, list, n_keys, logits_dev, dtype, &o, teacher_dev, given_dev, key_dev, action_dev, logp_dev, entropy_dev, source_dev, mask_dev, l->stream, nullptr, nullptr);
+    });
+}
+int rg_act_host(const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys, const void *logits, int dtype, const rg_act_opts *opts,
+                uint32_t env, int teacher_key, int given, uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source) {
+    return rgh_act(g_create_err, cells, height, width, px, py, dead, keys, n_keys, logits, dtype, opts, env, teacher_key, given, key, action, logp, entropy, source);
+}
 int rg_path(rg_t *h, uint32_t goals, const int32_t *cells_dev, uint16_t *field_dev, int32_t *dist_dev, uint8_t *key_dev) {
     if (path_goals_check(h->err, "rg_path", goals)) return 1;
     if ((goals & RG_GOAL_CELL) && !cells_dev) { h->err = "rg_path: cells_dev is NULL and goals has RG_GOAL_CELL"; return 1; }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/rogue_gym_hip.h"  // rg_act_opts
 #include "rg_state.h"
 
 struct RgIoLayout;  // rg_state_io.h
@@ -54,6 +55,10 @@ int rgk_pixels(const RgState *S, const RgConfig *c, const uint8_t *tiles, int th
 // the readers of game state: rg_action_mask.hip, rg_path.hip, rg_route.hip, rg_monsters.hip, rg_objects.hip
 void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, uint8_t *mask, uint8_t *sample, uint64_t seed, uint64_t draw, hipStream_t st,
                      hipEvent_t ev0, hipEvent_t ev1);
+// ... and rg_policy.hip (librogue_gym_policy.so)
+void rgk_act(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, const void *logits, int dtype, const rg_act_opts *opts, const uint8_t *teacher,
+             const int32_t *given, uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source, uint8_t *mask, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+const char *rgk_act_build_id(void);
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
 void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
                hipStream_t st);

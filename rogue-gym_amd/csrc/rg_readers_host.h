@@ -1,5 +1,5 @@
 // rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api_*.cpp) share with the *_host twins, and the
-// twins themselves (rgh_*; rg_action_mask_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
+// twins themselves (rgh_*; rg_action_mask_host, rg_act_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
 // rg_novelty_insert_host are one-line delegations in rg_api_readers.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
 // (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
 #pragma once
@@ -16,6 +16,7 @@
 #include "rg_monsters.h"
 #include "rg_episode.h"
 #include "rg_novelty.h"
+#include "rg_policy.h"  // (last: it switches floating-point contraction off for what follows)
 
 // ---- the argument checks: `what` is the entry's name ----
 static inline int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
@@ -163,6 +164,48 @@ static inline int rgh_action_mask(std::string &err, const uint16_t *cells, int h
     if (!cells || !out) { err = "rg_action_mask_host: cells and out must not be NULL"; return 1; }
     if (player_check(err, "rg_action_mask_host", px, py, height, width)) return 1;  // (an empty grid has no cell inside it: the same refusal)
     for (int k = 0; k < n_keys; k++) out[k] = (uint8_t)rg_key_legal(cells, height, width, px, py, dead, list[k]);
+    return 0;
+}
+// the options of an act call (rg_policy.h), shared by rg_act and rg_act_host
+static inline int act_opts_check(std::string &err, const char *what, const rg_act_opts *o, int dtype, bool have_teacher, bool have_given, bool have_key, const char *teacher_name,
+                                 const char *given_name, const char *key_name) {
+    const std::string w = std::string(what) + ": ";
+    if (dtype != RG_OBS_F32 && dtype != RG_OBS_F16 && dtype != RG_OBS_BF16) {
+        err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1) or RG_OBS_BF16 (2), got " + std::to_string(dtype);
+        return 1;
+    }
+    if (!o) { err = w + "opts must not be NULL"; return 1; }
+    if (o->mode > RG_ACT_GIVEN) { err = w + "opts.mode must be RG_ACT_SAMPLE (0), RG_ACT_GREEDY (1) or RG_ACT_GIVEN (2), got " + std::to_string(o->mode); return 1; }
+    if (!(o->inv_temp > 0.0f) || !(o->inv_temp <= 3.4028234663852886e38f)) { err = w + "opts.inv_temp must be finite and > 0, got " + std::to_string(o->inv_temp); return 1; }
+    if (!(o->epsilon >= 0.0f && o->epsilon <= 1.0f)) { err = w + "opts.epsilon must lie in [0, 1], got " + std::to_string(o->epsilon); return 1; }
+    if (!(o->beta >= 0.0f && o->beta <= 1.0f)) { err = w + "opts.beta must lie in [0, 1], got " + std::to_string(o->beta); return 1; }
+    if (o->epsilon + o->beta > 1.0f) { err = w + "opts.epsilon + opts.beta must not exceed 1, got " + std::to_string(o->epsilon) + " + " + std::to_string(o->beta); return 1; }
+    if (o->beta > 0.0f && !have_teacher) { err = w + "opts.beta > 0 needs a teacher: " + teacher_name + " is not given"; return 1; }
+    if (o->mode == RG_ACT_GIVEN && !have_given) { err = w + "RG_ACT_GIVEN needs " + given_name; return 1; }
+    if (o->mode != RG_ACT_GIVEN && !have_key) { err = w + key_name + " must not be NULL in a mode that draws"; return 1; }
+    return 0;
+}
+// teacher_key / given: < 0 = none.  Every output may be NULL except `key` in a mode that draws.
+static inline int rgh_act(std::string &err, const uint16_t *cells, int height, int width, int px, int py, int dead, const uint8_t *keys, int n_keys, const void *logits, int dtype,
+                          const rg_act_opts *opts, uint32_t env, int teacher_key, int given, uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source) {
+    uint8_t list[RG_MASK_MAX_KEYS];
+    if (mask_keys_check(err, "rg_act_host", keys, n_keys, list)) return 1;
+    if (act_opts_check(err, "rg_act_host", opts, dtype, teacher_key >= 0, opts && opts->mode == RG_ACT_GIVEN, key != nullptr, "teacher_key", "given", "key")) return 1;
+    if (!cells || !logits) { err = "rg_act_host: cells and logits must not be NULL"; return 1; }
+    if (player_check(err, "rg_act_host", px, py, height, width)) return 1;
+    const uint32_t bits = rg_legal_bits(cells, height, width, px, py, dead);
+    uint32_t row = 0;
+    int teacher = -1;
+    for (int k = n_keys - 1; k >= 0; k--) {
+        row |= ((bits >> rg_key_bit(list[k])) & 1u) << k;
+        if ((int)list[k] == teacher_key) teacher = k;  // (its first position)
+    }
+    const RgActOut r = rg_act_rule(row, n_keys, [=](int k) { return rg_pol_load(logits, k, dtype); }, *opts, env, teacher, given);
+    if (key) *key = list[r.action >= 0 && r.action < n_keys ? r.action : 0];
+    if (action) *action = r.action;
+    if (logp) *logp = r.logp;
+    if (entropy) *entropy = r.entropy;
+    if (source) *source = (uint8_t)r.source;
     return 0;
 }
 // The search runs from the goal cells over rg_path.h's pieces: rg_can_move(a -> b) taken apart into its target (expand), its start (enter) and its corners.

@@ -16,6 +16,9 @@ OBSFIX_UNITS="rg_obs_fix.hip:-Os"
 # The step kernel of the headline class likewise, librogue_gym_stepenc.so: k_step_enc is rg_kernels.hip's turn code (which the unit includes) compiled for the
 # 32 x 16 grid alone (-O3, as that unit); k_step_w32<false, true> keeps its place and its registers in librogue_gym_hip.so.
 STEPENC_UNITS="rg_step_enc.hip:-O3"
+# The masked categorical action from policy logits likewise, librogue_gym_policy.so: k_act states rg_policy.h's rule, which the host twin shares (-O3: the rule
+# is arithmetic, three short passes over a row).
+POLICY_UNITS="rg_policy.hip:-O3"
 # The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
 # Of the host units only the core reads the environment (tests/test_novelty_resources.py).
 KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"

@@ -728,6 +728,45 @@ class HipVecRogueEnv:
         self._mask_call(keys, self._mask_u8 if keys is None else None, out, seed, draw)
         return out
 
+    def act(self, logits, greedy=False, temperature=1.0, epsilon=0.0, teacher=None, beta=0.0, given=None, seed=0, draw=None, keys=None):
+        """One masked categorical action per env from policy logits, in one launch (rg_act) -> ActResult(keys, actions, logp, entropy, source) of device
+        tensors [N]: `keys` uint8 is what step_keys takes, `actions` int32 the index into `keys=` (None = ACTIONS), `logp` float32 the natural log of
+        pi(action), `entropy` float32 of pi in nats, `source` uint8 0 policy / 1 uniform / 2 teacher / 3 none (inner.ACT_SOURCES).
+        logits: [N, n_keys] float32, float16 or bfloat16 on this env's device.  pi is the softmax of logits / temperature over the keys that are LEGAL now
+        (`action_mask`'s rule); an illegal key has probability 0 whatever its logit.  greedy=True takes the legal argmax (ties: the lowest index).
+        epsilon: the probability of a uniform draw among the legal keys; teacher (uint8 [N] key bytes, e.g. `self.guide_keys`) with beta: the probability of
+        playing the teacher's key where it is listed and legal -- DAgger's mixing; epsilon + beta <= 1.  given (int32 [N] action indices): no draw, the
+        log-probability of those actions (-inf for an illegal one), `keys` their key bytes.
+        `logp` is ALWAYS under the pure masked softmax, also when epsilon or the teacher chose: it is the BEHAVIOUR log-probability for the rollout buffer
+        and carries no autograd -- the learner's update recomputes log pi from its own logits and `action_mask`.
+        The draw is a stateless function of (seed, env index, draw); draw=None uses the counter sample_keys uses, which advances by one per call.  With
+        action_mask=True and keys=None the call also rewrites `self.action_mask`.  No host trip; states, mirrors and `obs` are left as they are."""
+        torch = self.torch
+        kb, nk = inner._mask_keys(keys)
+        logits = self._dev_arg("act", "logits", logits, (torch.float32, torch.float16, torch.bfloat16), (self.num_envs, nk)).detach()
+        if teacher is not None:
+            teacher = self._dev_arg("act", "teacher", teacher, (torch.uint8,), (self.num_envs,))
+        if given is not None:
+            given = self._dev_arg("act", "given", given, (torch.int32,), (self.num_envs,))
+        if draw is None:
+            draw, self._draw = self._draw, self._draw + 1
+        opts = inner._act_opts(greedy, temperature, epsilon, beta, given is not None, seed, draw)
+        with torch.cuda.device(self.device):
+            out = inner.ActResult(torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device), torch.empty((self.num_envs,), dtype=torch.int32, device=self.device),
+                                  torch.empty((self.num_envs,), dtype=torch.float32, device=self.device), torch.empty((self.num_envs,), dtype=torch.float32, device=self.device),
+                                  torch.empty((self.num_envs,), dtype=torch.uint8, device=self.device))
+        mask = self._mask_u8 if keys is None else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self._h.check(self._h.L.rg_act(self._h.h, kb, nk, ptr(logits), inner.ACT_DTYPES[str(logits.dtype).replace("torch.", "")], C.byref(opts), ptr(teacher), ptr(given),
+                                       ptr(out.keys), ptr(out.actions), ptr(out.logp), ptr(out.entropy), ptr(out.source), ptr(mask)))
+        return out
+
+    def step_logits(self, logits, **opts):
+        """act(logits, **opts) followed by step_keys of the keys it chose -> (obs, reward, done, act_result)."""
+        res = self.act(logits, **opts)
+        obs, reward, done = self.step_keys(res.keys)
+        return obs, reward, done, res
+
     @property
     def screen(self):
         """u8 [num_envs, H, W] glyph mirror (PlayerState.map of every env).  Reading it flushes the pending render (a batch with several

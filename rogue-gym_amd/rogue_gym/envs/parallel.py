@@ -82,6 +82,11 @@ class ParallelRogueEnv:
         """bool [N, ACTION_LEN]: entry [i, a] says whether ACTIONS[a] would do anything for env i now (RogueEnv.action_mask for the whole batch)."""
         return self.game.action_masks()
 
+    def act(self, logits, **opts):
+        """ActResult(keys, actions, logp, entropy, source) of numpy arrays [N]: RogueEnv.act for the whole batch, logits [N, ACTION_LEN] float32 or float16,
+        teacher uint8 [N] key bytes, given int32 [N] action indices.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd."""
+        return self.game.act(logits, **opts)
+
     def path_keys(self, goal: str = "stairs"):
         """(keys uint8 [N], dist int32 [N]): RogueEnv.path_key for the whole batch, as key bytes and distances with -1 for unreachable."""
         return self.game.path_keys(goal)

@@ -208,6 +208,18 @@ class RogueEnv(Env):
         for diagonals, the surface under the player for '>'), which the screen does not show completely."""
         return self.game.action_mask()
 
+    def act(self, logits, **opts):
+        """ActResult(keys, actions, logp, entropy, source) of numpy arrays of length 1: one masked categorical action from a row of policy logits
+        [ACTION_LEN] (float32 or float16), by the rule HipVecRogueEnv.act runs on the device -- the softmax over the keys action_mask() calls legal, and
+        bit for bit the device call's answer on the same state.  Options as there: greedy, temperature, epsilon, teacher (a key byte), beta, given (an
+        action index), seed, draw (default 0: the caller counts), keys.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd."""
+        if opts.get("teacher") is not None:
+            t = opts["teacher"]
+            opts["teacher"] = [ord(t) if isinstance(t, (str, bytes)) else int(t)]
+        if opts.get("given") is not None:
+            opts["given"] = [int(opts["given"])]
+        return self.game.act(logits, **opts)
+
     def path_key(self, goal: str = "stairs"):
         """(key, dist): the key of ACTIONS -- a str of length 1 -- that takes the player one move closer to the nearest goal cell ("stairs", "gold" or
         "stairs+gold") and the number of moves to it, or ('s', None) when none can be reached; '>' on the stairs.  Shortest paths under the engine's

@@ -6,6 +6,7 @@ GameState, ParallelGameState, PlayerState.  All game logic runs in librogue_gym_
 MI355X; this file only marshals.  There is no CPU fallback: importing works anywhere, but
 constructing a GameState without the built library or without a HIP device raises.
 """
+import collections
 import ctypes as C
 import functools
 import operator
@@ -48,6 +49,11 @@ class RgEpisodeArrays(C.Structure):
 class RgNoveltyArrays(C.Structure):
     """rg_novelty_arrays_t (include/rogue_gym_hip.h): device pointers."""
     _fields_ = [(k, C.c_void_p) for k in ("hash", "count", "gcount")]
+
+
+class RgActOpts(C.Structure):
+    """rg_act_opts (include/rogue_gym_hip.h)."""
+    _fields_ = [("inv_temp", C.c_float), ("epsilon", C.c_float), ("beta", C.c_float), ("mode", C.c_uint32), ("seed", C.c_uint64), ("draw", C.c_uint64)]
 
 
 class RgArchiveArrays(C.Structure):
@@ -138,6 +144,8 @@ _abi(True, {
     "rg_tail_encode": [vp, i32],
     "rg_action_mask": [vp, vp, i32, vp, vp, u64, u64], "rg_action_mask_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
     "rg_sample_index": ([u64, u32, u64, u32], u32),
+    "rg_act": [vp, vp, i32, vp, i32, _P(RgActOpts), vp, vp, vp, vp, vp, vp, vp, vp],
+    "rg_act_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, _P(RgActOpts), u32, i32, i32, vp, vp, vp, vp, vp],
     "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
     "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
     "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, _P(RgEpisodeArrays)],
@@ -358,6 +366,24 @@ def _mask_keys(keys):
     return bytes(keys), len(keys)
 
 
+RG_ACT_SAMPLE, RG_ACT_GREEDY, RG_ACT_GIVEN = 0, 1, 2
+ACT_SOURCES = ("policy", "uniform", "teacher", "none")   # the values of an act result's `source`
+ActResult = collections.namedtuple("ActResult", "keys actions logp entropy source")
+ACT_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}  # RG_OBS_F32 / RG_OBS_F16 / RG_OBS_BF16 by the name of the element type
+
+
+def _act_opts(greedy=False, temperature=1.0, epsilon=0.0, beta=0.0, given=False, seed=0, draw=0):
+    """The rg_act_opts of an act call.  The library checks the values (and names the one it refuses); temperature 0 is refused here, where it would divide."""
+    temperature = float(temperature)
+    if not temperature > 0.0:
+        raise ValueError("temperature must be > 0, got %r (greedy=True takes the argmax)" % (temperature,))
+    if greedy and given:
+        raise ValueError("greedy=True and given= cannot be combined")
+    mode = RG_ACT_GIVEN if given else RG_ACT_GREEDY if greedy else RG_ACT_SAMPLE
+    inv = np.float32(1.0) / np.float32(temperature)
+    return RgActOpts(float(inv), float(epsilon), float(beta), mode, int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF)
+
+
 PATH_GOALS = {"stairs": 1, "gold": 2, "stairs+gold": 3}  # RG_GOAL_STAIRS, RG_GOAL_GOLD; RG_GOAL_CELL (4) comes with a caller's cells
 
 
@@ -513,7 +539,9 @@ class _Handle:
 
     def debug_state(self, env):
         out = RgDebugState()
-        cells = np.empty((self.height, self.width), np.uint16)
+        inside = 0 <= env < self.n  # (an env out of range is the library's to refuse)
+        # the grid of the env's OWN size: in a mixed-size batch the handle's height and width are its first group's, and a larger env would write past them
+        cells = np.empty((int(self.env_heights[env]), int(self.env_widths[env])) if inside else (self.height, self.width), np.uint16)
         self.check(self.L.rg_debug_fetch(self.h, env, C.byref(out), cells.ctypes.data))
         return out, cells
 
@@ -542,6 +570,31 @@ class _Handle:
         base = self._scratch_grow(self.n * nk)
         self.check(self.L.rg_action_mask(self.h, kb, nk, C.c_void_p(base), None, 0, 0))
         return self._scratch_read(self.n * nk).reshape(self.n, nk).view(np.bool_)
+
+    def act(self, logits, greedy=False, temperature=1.0, epsilon=0.0, teacher=None, beta=0.0, given=None, seed=0, draw=0, keys=None):
+        """The value form of rg_act: ActResult of numpy arrays [n] (keys u8, actions i32, logp f32, entropy f32, source u8) for `logits`, a numpy array
+        [n, n_keys] of float32 or float16 -- through rg_act_host, the CPU twin of the device rule, env by env on the grids rg_debug_fetch hands out (bit for
+        bit what the device call gives on the same states).  teacher: key bytes u8 [n]; given: action indices [n] (their log-probability, no draw)."""
+        kb, nk = _mask_keys(keys)
+        logits = np.ascontiguousarray(logits)
+        if logits.dtype not in (np.float32, np.float16) or logits.shape != (self.n, nk):
+            raise ValueError("act: logits must be a float32 / float16 array [%d, %d], got %s %s" % (self.n, nk, logits.shape, logits.dtype))
+        teacher = None if teacher is None else np.ascontiguousarray(teacher, dtype=np.uint8).reshape(self.n)
+        given = None if given is None else np.ascontiguousarray(given, dtype=np.int32).reshape(self.n)
+        opts = _act_opts(greedy, temperature, epsilon, beta, given is not None, seed, draw)
+        flags = np.empty(self.n, np.uint32)
+        self.check(self.L.rg_fetch_states(self.h, None, None, None, flags.ctypes.data))
+        out = ActResult(np.zeros(self.n, np.uint8), np.zeros(self.n, np.int32), np.zeros(self.n, np.float32), np.zeros(self.n, np.float32), np.zeros(self.n, np.uint8))
+        dtype = ACT_DTYPES[logits.dtype.name]
+        for e in range(self.n):
+            d, cells = self.debug_state(e)
+            h, w = int(self.env_heights[e]), int(self.env_widths[e])
+            rc = self.L.rg_act_host(cells.ctypes.data, h, w, d.px, d.py, int(flags[e] >> 1) & 1, kb, nk, logits[e].ctypes.data, dtype, C.byref(opts), e,
+                                    -1 if teacher is None else int(teacher[e]), 0 if given is None else int(given[e]),
+                                    out.keys[e:].ctypes.data, out.actions[e:].ctypes.data, out.logp[e:].ctypes.data, out.entropy[e:].ctypes.data, out.source[e:].ctypes.data)
+            if rc:
+                raise RuntimeError("Error in rogue-gym: " + self.L.rg_last_error(None).decode())
+        return out
 
     def path_keys(self, goal="stairs"):
         """(keys u8 [n], dist i32 [n]) towards `goal` ("stairs", "gold", "stairs+gold"): rg_path into the device scratch buffer the handle keeps, one
@@ -980,6 +1033,10 @@ class GameState:
         """numpy bool [n_keys]: which keys would do anything now (not part of the reference's API; rg_action_mask)."""
         return self._h.action_mask(keys)[0]
 
+    def act(self, logits, **opts):
+        """ActResult of arrays of length 1 for a row of logits [n_keys] (not part of the reference's API; rg_act_host)."""
+        return self._h.act(np.asarray(logits)[None], **opts)
+
     def path_key(self, goal="stairs"):
         """(key byte as bytes of length 1, distance or None): the key that takes the player one move closer to the nearest goal cell and the number of
         moves to it (not part of the reference's API; rg_path -- privileged: it sees what the player has not discovered)."""
@@ -1069,6 +1126,10 @@ class ParallelGameState:
     def action_masks(self, keys=None):
         """numpy bool [n, n_keys]: which keys would do anything for each env now (not part of the reference's API; rg_action_mask)."""
         return self._h.action_mask(keys)
+
+    def act(self, logits, **opts):
+        """ActResult of numpy arrays [n] for logits [n, n_keys] (not part of the reference's API; rg_act_host)."""
+        return self._h.act(logits, **opts)
 
     def path_keys(self, goal="stairs"):
         """(keys numpy u8 [n], dist numpy i32 [n], -1 = unreachable) towards `goal` (not part of the reference's API; rg_path)."""
