@@ -325,6 +325,32 @@ int rg_act_host(const uint16_t *cells, int height, int width, int px, int py, in
                 const void *logits, int dtype, const rg_act_opts *opts, uint32_t env, int teacher_key, int given,
                 uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source);
 
+/* THE LEARNER'S SIDE OF THAT RULE: the log-probability of STORED actions and the entropy under STORED masks for any number of rows of logits, and the gradient
+ * of both with respect to the logits -- what a PPO / A2C update evaluates for its T x N rows.  Stateless: no handle, a learner process may own no env.  The
+ * rule is stated once, in rogue-gym_amd/csrc/rg_policy_grad.h; kernels (k_pg_eval, k_pg_grad in librogue_gym_learn.so) and host twins agree bit for bit.
+ *   Rows: logits [n_rows][n_keys] of dtype RG_OBS_F32 / RG_OBS_F16 / RG_OBS_BF16, contiguous; mask u8 [n_rows][n_keys], a byte != 0 = the key is legal
+ *     (what the action-mask call and rg_act's mask_dev write), NULL = every key; action i32 [n_rows], an index into the row, any value.
+ *   rg_policy_eval: logp f32 [n_rows] and entropy f32 [n_rows], each nullable -- exactly what rg_act answers for that row in RG_ACT_GIVEN mode, so for the
+ *     logits, mask and action of an rg_act call they equal its logp and entropy bit for bit (no legal key: 0 and 0; action out of range or illegal: -inf).
+ *   rg_policy_grad: dlogits [n_rows][n_keys] of dtype = the gradient of sum_r g_logp[r] * logp[r] + g_entropy[r] * entropy[r]; either upstream array may be
+ *     NULL and then counts as 0.  For a legal key that weighs: inv_temp * (g_logp * ([k == a] - pi_k) - g_entropy * pi_k * (logp_k + H)); +0.0 for every
+ *     other key, for a row where no legal key weighs and a row with no legal key.  An action that is out of range, illegal or weightless (logp = -inf)
+ *     makes the g_logp term 0 for the whole row; the entropy term still flows.  A NaN is the canonical quiet NaN; 16-bit results are the f32 result
+ *     rounded to nearest even.
+ *   Asynchronous on hip_stream (NULL = the null stream), on the caller's current device; nothing is read or written past row n_rows - 1; no alignment is
+ *   asked for (a stretch of 64 rows that starts on a multiple of 16 bytes moves as 16-byte pieces, any other lane by lane).  n_rows == 0 is a valid no-op.
+ *   Refused, non-zero with a message (rg_last_error(NULL)) naming the argument, nothing launched, outputs untouched: n_keys outside 1..32; an unknown dtype;
+ *   NULL logits, actions or dlogits; inv_temp not finite or not > 0; n_rows < 0.
+ * The *_host twins: the same rule over host pointers, no stream, no device. */
+int rg_policy_eval(void *hip_stream, int64_t n_rows, int n_keys, const void *logits_dev, int dtype, const uint8_t *mask_dev,
+                   const int32_t *action_dev, float inv_temp, float *logp_dev, float *entropy_dev);
+int rg_policy_grad(void *hip_stream, int64_t n_rows, int n_keys, const void *logits_dev, int dtype, const uint8_t *mask_dev, const int32_t *action_dev, float inv_temp,
+                   const float *g_logp_dev, const float *g_entropy_dev, void *dlogits_dev);
+int rg_policy_eval_host(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp,
+                        float *logp, float *entropy);
+int rg_policy_grad_host(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp,
+                        const float *g_logp, const float *g_entropy, void *dlogits);
+
 /* SHORTEST-PATH FIELDS AND TEACHER KEYS: for each env the number of moves from every cell to the nearest goal cell, that number at the player's cell, and the
  * key that takes the player one move closer, on the device.  The moves are the engine's own: rg_action_mask's move test (Floor::can_move_impl as the player).
  * The field is PRIVILEGED: it sees stairs, gold and passages the player has not discovered.  It is a teacher (imitation, DAgger), a shaping potential

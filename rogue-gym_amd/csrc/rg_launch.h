@@ -59,6 +59,12 @@ void rgk_action_mask(const RgState *S, const RgConfig *c, const uint8_t *keys, i
 void rgk_act(const RgState *S, const RgConfig *c, const uint8_t *keys, int n_keys, const void *logits, int dtype, const rg_act_opts *opts, const uint8_t *teacher,
              const int32_t *given, uint8_t *key, int32_t *action, float *logp, float *entropy, uint8_t *source, uint8_t *mask, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 const char *rgk_act_build_id(void);
+// ... and rg_policy_grad.hip (librogue_gym_learn.so): stateless, no handle
+void rgk_pg_eval(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp, float *logp, float *entropy,
+                 hipStream_t st);
+void rgk_pg_grad(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp, const float *g_lp, const float *g_ent,
+                 void *dlogits, hipStream_t st);
+const char *rgk_learn_build_id(void);
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
 void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
                hipStream_t st);

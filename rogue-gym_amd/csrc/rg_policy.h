@@ -119,20 +119,20 @@ static __host__ __device__ inline int rg_pol_nth(uint32_t row, uint32_t idx) {
     return __builtin_ctz(row);
 }
 
-// One env.  row: bit k = keys[k] is legal (k < n_keys <= 32); fetch(k): logit k widened to f32; teacher: the position of the teacher key in the list, -1 =
-// none or not listed; given: the action of RG_ACT_GIVEN.  The options are checked by the caller (rgh_act_opts_check).
+// The row's softmax statistics, the part of the rule that the learner's side (rg_policy_grad.h) shares: row != 0.
+//   best = where the largest scaled logit among the legal keys that weigh first stands (-1 = none weighs: flat); m = that logit; S and T = the sums of w and
+//   w * d in list order; lnS = ln S (flat: ln count); inv = 1 / S, THE division (flat: unused, 0); ent = the entropy, not below 0.
+struct RgPolStats { float m, S, T, lnS, inv, ent; int best; bool flat; uint32_t count; };
 template <class Fetch>
-static __host__ __device__ inline RgActOut rg_act_rule(uint32_t row, int n_keys, Fetch fetch, const rg_act_opts &o, uint32_t env, int teacher, int given) {
-    RgActOut r = {0, 0.0f, 0.0f, 3u};
-    if (row == 0u) return r;
-    const float ninf = rg_pol_f(0xff800000u), log2e = 1.4426950216293335f;
+static __host__ __device__ inline RgPolStats rg_pol_stats(uint32_t row, int n_keys, Fetch fetch, float inv_temp) {
+    const float log2e = 1.4426950216293335f;
     const uint32_t count = (uint32_t)__builtin_popcount(row);
     // pass 1: the largest scaled logit among the legal keys that weigh, and where it first stands
     float m = 0.0f;
     int best = -1;
     for (int k = 0; k < n_keys; k++) {
         bool ok;
-        const float x = rg_pol_scaled(fetch(k), o.inv_temp, ok);
+        const float x = rg_pol_scaled(fetch(k), inv_temp, ok);
         if (((row >> k) & 1u) && ok && (best < 0 || x > m)) { m = x; best = k; }
     }
     const bool flat = best < 0;  // no legal key weighs: the uniform distribution
@@ -141,19 +141,34 @@ static __host__ __device__ inline RgActOut rg_act_rule(uint32_t row, int n_keys,
     if (!flat)
         for (int k = 0; k < n_keys; k++) {
             bool ok;
-            const float x = rg_pol_scaled(fetch(k), o.inv_temp, ok);
+            const float x = rg_pol_scaled(fetch(k), inv_temp, ok);
             if (!(((row >> k) & 1u) && ok)) continue;
             const float d = x - m, w = rg_pol_exp2(d * log2e);
             S = S + w;
             if (w != 0.0f) T = __builtin_fmaf(w, d, T);
         }
     const float lnS = flat ? rg_pol_ln((float)count) : rg_pol_ln(S);
-    float ent = lnS;
+    float ent = lnS, inv = 0.0f;
     if (!flat) {
-        const float inv = 1.0f / S;
+        inv = 1.0f / S;
         ent = lnS - T * inv;
         if (!(ent > 0.0f)) ent = 0.0f;
     }
+    return {m, S, T, lnS, inv, ent, best, flat, count};
+}
+
+// One env.  row: bit k = keys[k] is legal (k < n_keys <= 32); fetch(k): logit k widened to f32; teacher: the position of the teacher key in the list, -1 =
+// none or not listed; given: the action of RG_ACT_GIVEN.  The options are checked by the caller (rgh_act_opts_check).
+template <class Fetch>
+static __host__ __device__ inline RgActOut rg_act_rule(uint32_t row, int n_keys, Fetch fetch, const rg_act_opts &o, uint32_t env, int teacher, int given) {
+    RgActOut r = {0, 0.0f, 0.0f, 3u};
+    if (row == 0u) return r;
+    const float ninf = rg_pol_f(0xff800000u), log2e = 1.4426950216293335f;
+    const RgPolStats st = rg_pol_stats(row, n_keys, fetch, o.inv_temp);
+    const uint32_t count = st.count;
+    const float m = st.m, S = st.S, lnS = st.lnS, ent = st.ent;
+    const int best = st.best;
+    const bool flat = st.flat;
     r.entropy = ent;
     // the action
     const uint64_t z = rg_act_word(o.seed, env, o.draw);

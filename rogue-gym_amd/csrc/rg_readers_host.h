@@ -1,5 +1,5 @@
 // rg_readers_host.h -- the readers of game state on the CPU: the argument checks that the device entry points (rg_api_*.cpp) share with the *_host twins, and the
-// twins themselves (rgh_*; rg_action_mask_host, rg_act_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
+// twins themselves (rgh_*; rg_action_mask_host, rg_act_host, rg_policy_eval_host, rg_policy_grad_host, rg_path_host, rg_route_host, rg_monsters_host, rg_objects_host, rg_scout_host, rg_novelty_hash_host and
 // rg_novelty_insert_host are one-line delegations in rg_api_readers.cpp).  Host only and header only: plain C++ over a u16 grid and the rule headers' pieces -- no handle, no stream, no HIP call -- so a stand-alone program
 // (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
 #pragma once
@@ -17,6 +17,7 @@
 #include "rg_episode.h"
 #include "rg_novelty.h"
 #include "rg_policy.h"  // (last: it switches floating-point contraction off for what follows)
+#include "rg_policy_grad.h"
 
 // ---- the argument checks: `what` is the entry's name ----
 static inline int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
@@ -206,6 +207,57 @@ static inline int rgh_act(std::string &err, const uint16_t *cells, int height, i
     if (logp) *logp = r.logp;
     if (entropy) *entropy = r.entropy;
     if (source) *source = (uint8_t)r.source;
+    return 0;
+}
+// the arguments of the learner's entries (rg_policy_grad.h), shared by rg_policy_eval / rg_policy_grad and their host twins; sfx: "_dev" or ""
+static inline int pg_args_check(std::string &err, const char *what, const char *sfx, int64_t n_rows, int n_keys, const void *logits, int dtype, const int32_t *action, float inv_temp,
+                                bool wants_dlogits, const void *dlogits) {
+    const std::string w = std::string(what) + ": ";
+    if (n_rows < 0) { err = w + "n_rows must not be negative, got " + std::to_string(n_rows); return 1; }
+    if (n_rows > (int64_t)0x7fffffff * 64) { err = w + "n_rows must not exceed 2^37 - 64, got " + std::to_string(n_rows); return 1; }
+    if (n_keys < 1 || n_keys > RG_MASK_MAX_KEYS) { err = w + "n_keys must lie in 1.." + std::to_string(RG_MASK_MAX_KEYS) + ", got " + std::to_string(n_keys); return 1; }
+    if (dtype != RG_OBS_F32 && dtype != RG_OBS_F16 && dtype != RG_OBS_BF16) {
+        err = w + "dtype must be RG_OBS_F32 (0), RG_OBS_F16 (1) or RG_OBS_BF16 (2), got " + std::to_string(dtype);
+        return 1;
+    }
+    if (!(inv_temp > 0.0f) || !(inv_temp <= 3.4028234663852886e38f)) { err = w + "inv_temp must be finite and > 0, got " + std::to_string(inv_temp); return 1; }
+    if (!logits) { err = w + "logits" + sfx + " must not be NULL"; return 1; }
+    if (!action) { err = w + "action" + sfx + " must not be NULL"; return 1; }
+    if (wants_dlogits && !dlogits) { err = w + "dlogits" + sfx + " must not be NULL"; return 1; }
+    return 0;
+}
+// the legal word of row r: a mask byte counts as != 0; no mask = every key
+static inline uint32_t pg_host_row(const uint8_t *mask, int64_t r, int n_keys) {
+    if (!mask) return rg_pg_all(n_keys);
+    uint32_t row = 0;
+    for (int k = 0; k < n_keys; k++) row |= (mask[r * n_keys + k] != 0 ? 1u : 0u) << k;
+    return row;
+}
+static inline int rgh_policy_eval(std::string &err, int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp,
+                                  float *logp, float *entropy) {
+    if (pg_args_check(err, "rg_policy_eval_host", "", n_rows, n_keys, logits, dtype, action, inv_temp, false, nullptr)) return 1;
+    const size_t esz = dtype == RG_OBS_F32 ? 4 : 2;
+    for (int64_t r = 0; r < n_rows; r++) {
+        const void *x = static_cast<const uint8_t *>(logits) + (size_t)r * n_keys * esz;
+        const RgPgOut o = rg_pg_eval_rule(pg_host_row(mask, r, n_keys), n_keys, [=](int k) { return rg_pol_load(x, k, dtype); }, inv_temp, action[r]);
+        if (logp) logp[r] = o.logp;
+        if (entropy) entropy[r] = o.entropy;
+    }
+    return 0;
+}
+static inline int rgh_policy_grad(std::string &err, int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp,
+                                  const float *g_logp, const float *g_entropy, void *dlogits) {
+    if (pg_args_check(err, "rg_policy_grad_host", "", n_rows, n_keys, logits, dtype, action, inv_temp, true, dlogits)) return 1;
+    const size_t esz = dtype == RG_OBS_F32 ? 4 : 2;
+    for (int64_t r = 0; r < n_rows; r++) {
+        const void *x = static_cast<const uint8_t *>(logits) + (size_t)r * n_keys * esz;
+        void *out = static_cast<uint8_t *>(dlogits) + (size_t)r * n_keys * esz;
+        rg_pg_grad_rule(pg_host_row(mask, r, n_keys), n_keys, [=](int k) { return rg_pol_load(x, k, dtype); }, inv_temp, action[r], g_logp != nullptr, g_logp ? g_logp[r] : 0.0f,
+                        g_entropy != nullptr, g_entropy ? g_entropy[r] : 0.0f, [=](int k, float v) {
+                            if (dtype == RG_OBS_F32) static_cast<float *>(out)[k] = v;
+                            else static_cast<uint16_t *>(out)[k] = (uint16_t)rg_pol_narrow(v, dtype);
+                        });
+    }
     return 0;
 }
 // The search runs from the goal cells over rg_path.h's pieces: rg_can_move(a -> b) taken apart into its target (expand), its start (enter) and its corners.

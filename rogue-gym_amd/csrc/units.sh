@@ -4,7 +4,7 @@
 # subsystem, DESIGN.md "The host layer") take -O2.
 UNITS="rg_kernels.hip:-O3 rg_regen_lanes.hip:-O3 rg_obs.hip:-Os rg_crop_typed.hip:-Os rg_pixels.hip:-Os rg_action_mask.hip:-Os rg_path.hip:-O3 rg_route.hip:-O3
        rg_episode.hip:-O3 rg_monsters.hip:-O3 rg_objects.hip:-O3 rg_state_io.hip:-O3
-       rg_api.cpp:-O2 rg_api_obs.cpp:-O2 rg_api_readers.cpp:-O2 rg_api_episode.cpp:-O2 rg_api_state.cpp:-O2 rg_api_comm.cpp:-O2 rg_api_diag.cpp:-O2
+       rg_api.cpp:-O2 rg_api_obs.cpp:-O2 rg_api_readers.cpp:-O2 rg_api_learn.cpp:-O2 rg_api_episode.cpp:-O2 rg_api_state.cpp:-O2 rg_api_comm.cpp:-O2 rg_api_diag.cpp:-O2
        rg_config.cpp:-O2 rg_items.cpp:-O2"
 # The novelty pass is a library of its own, librogue_gym_novelty.so, which librogue_gym_hip.so links (found beside it at run time): its kernels stay out of the
 # code objects whose kernel set tests/test_pixels_resources.py pins by name.
@@ -19,6 +19,9 @@ STEPENC_UNITS="rg_step_enc.hip:-O3"
 # The masked categorical action from policy logits likewise, librogue_gym_policy.so: k_act states rg_policy.h's rule, which the host twin shares (-O3: the rule
 # is arithmetic, three short passes over a row).
 POLICY_UNITS="rg_policy.hip:-O3"
+# The learner's side of that rule likewise, librogue_gym_learn.so: k_pg_eval and k_pg_grad state rg_policy_grad.h's rule (log-probability of stored actions, entropy
+# under stored masks, their gradient), which the host twins share; librogue_gym_policy.so stays the three k_act instances (-O3, as that unit).
+LEARN_UNITS="rg_policy_grad.hip:-O3"
 # The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
 # Of the host units only the core reads the environment (tests/test_novelty_resources.py).
 KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"

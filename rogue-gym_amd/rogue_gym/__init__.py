@@ -2,5 +2,6 @@
 from .envs import (DungeonType, FirstFloorEnv, HipVecRogueEnv, HipVecStairReward, ImageSetting, ParallelRogueEnv, PlayerState, RogueEnv, StairRewardEnv, StairRewardParallel,
                    StatusFlag)
 from . import envs  # noqa: F401
+from .learn import masked_logp, masked_logp_np  # noqa: F401
 
 __version__ = "0.0.2"

@@ -738,7 +738,8 @@ class HipVecRogueEnv:
         playing the teacher's key where it is listed and legal -- DAgger's mixing; epsilon + beta <= 1.  given (int32 [N] action indices): no draw, the
         log-probability of those actions (-inf for an illegal one), `keys` their key bytes.
         `logp` is ALWAYS under the pure masked softmax, also when epsilon or the teacher chose: it is the BEHAVIOUR log-probability for the rollout buffer
-        and carries no autograd -- the learner's update recomputes log pi from its own logits and `action_mask`.
+        and carries no autograd -- the learner's update recomputes log pi from its own logits and the stored `action_mask` with `rogue_gym.masked_logp`
+        (or `self.evaluate`), which answers these very bits for unchanged logits and has a backward pass.
         The draw is a stateless function of (seed, env index, draw); draw=None uses the counter sample_keys uses, which advances by one per call.  With
         action_mask=True and keys=None the call also rewrites `self.action_mask`.  No host trip; states, mirrors and `obs` are left as they are."""
         torch = self.torch
@@ -760,6 +761,16 @@ class HipVecRogueEnv:
         self._h.check(self._h.L.rg_act(self._h.h, kb, nk, ptr(logits), inner.ACT_DTYPES[str(logits.dtype).replace("torch.", "")], C.byref(opts), ptr(teacher), ptr(given),
                                        ptr(out.keys), ptr(out.actions), ptr(out.logp), ptr(out.entropy), ptr(out.source), ptr(mask)))
         return out
+
+    def evaluate(self, logits, actions, mask=None, temperature=1.0):
+        """rogue_gym.masked_logp(logits, actions, mask, temperature) -> (logp, entropy) with autograd, `mask` defaulting to `self.action_mask` as it stands now
+        (the envs must not have stepped since the actions were chosen; a rollout buffer passes the masks it stored)."""
+        from ..learn import masked_logp
+        if mask is None:
+            if self.action_mask is None:
+                raise ValueError("evaluate: no mask given and the env was made without action_mask=True")
+            mask = self.action_mask
+        return masked_logp(logits, actions, mask, temperature)
 
     def step_logits(self, logits, **opts):
         """act(logits, **opts) followed by step_keys of the keys it chose -> (obs, reward, done, act_result)."""

@@ -84,7 +84,8 @@ class ParallelRogueEnv:
 
     def act(self, logits, **opts):
         """ActResult(keys, actions, logp, entropy, source) of numpy arrays [N]: RogueEnv.act for the whole batch, logits [N, ACTION_LEN] float32 or float16,
-        teacher uint8 [N] key bytes, given int32 [N] action indices.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd."""
+        teacher uint8 [N] key bytes, given int32 [N] action indices.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd
+        (rogue_gym.masked_logp_np is the learner's numpy form)."""
         return self.game.act(logits, **opts)
 
     def path_keys(self, goal: str = "stairs"):

@@ -212,7 +212,8 @@ class RogueEnv(Env):
         """ActResult(keys, actions, logp, entropy, source) of numpy arrays of length 1: one masked categorical action from a row of policy logits
         [ACTION_LEN] (float32 or float16), by the rule HipVecRogueEnv.act runs on the device -- the softmax over the keys action_mask() calls legal, and
         bit for bit the device call's answer on the same state.  Options as there: greedy, temperature, epsilon, teacher (a key byte), beta, given (an
-        action index), seed, draw (default 0: the caller counts), keys.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd."""
+        action index), seed, draw (default 0: the caller counts), keys.  `logp` is the behaviour log-probability for the rollout buffer; there is no autograd
+        (rogue_gym.masked_logp_np is the learner's numpy form: logp, entropy and a grad_fn for stored actions and masks)."""
         if opts.get("teacher") is not None:
             t = opts["teacher"]
             opts["teacher"] = [ord(t) if isinstance(t, (str, bytes)) else int(t)]

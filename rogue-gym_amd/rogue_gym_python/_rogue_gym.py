@@ -82,7 +82,7 @@ EPISODE_REC = [("serial", "<u4"), ("env", "<i4"), ("ret", "<f4"), ("length", "<i
 
 _lib = None
 
-vp, i32, u32, u64, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t
+vp, i32, u32, u64, sz, i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int64
 _P = C.POINTER
 
 # The C-ABI (include/rogue_gym_hip.h), every entry point once: name -> (argtypes, restype, may be absent).  In the two tables below a plain list is the
@@ -146,6 +146,8 @@ _abi(True, {
     "rg_sample_index": ([u64, u32, u64, u32], u32),
     "rg_act": [vp, vp, i32, vp, i32, _P(RgActOpts), vp, vp, vp, vp, vp, vp, vp, vp],
     "rg_act_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, _P(RgActOpts), u32, i32, i32, vp, vp, vp, vp, vp],
+    "rg_policy_eval": [vp, i64, i32, vp, i32, vp, vp, C.c_float, vp, vp], "rg_policy_grad": [vp, i64, i32, vp, i32, vp, vp, C.c_float, vp, vp, vp],
+    "rg_policy_eval_host": [i64, i32, vp, i32, vp, vp, C.c_float, vp, vp], "rg_policy_grad_host": [i64, i32, vp, i32, vp, vp, C.c_float, vp, vp, vp],
     "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
     "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
     "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, _P(RgEpisodeArrays)],
