@@ -205,8 +205,9 @@ def pack_w0(x, y, kind, alive=True, active=False):
     return (x << 8 | y) | kind << 16 | ((MF_ALIVE if alive else 0) | (MF_ACTIVE if active else 0)) << 24
 
 
-def inject_monsters(hip, w0, hp):
+def inject_monsters(hip, w0, hp, rect=None, meta=None):
     """Replace the monster words of every env of a HipBatch through its state records: w0 u32 [n][rooms] (pack_w0), hp i32 [n][rooms]; mon_cnt follows them.
+    rect u32 [n][rooms] (x0 | y0 << 8 | x1 << 16 | y1 << 24) and meta [n][rooms] (RM_*: kind in bits 0..1) replace the room words likewise when given.
     Everything else stays (call grid_util.inject first for cells, player and the dead bit).  As there: such a handle is only read, never stepped."""
     import torch
     import grid_util as gu
@@ -226,6 +227,10 @@ def inject_monsters(hip, w0, hp):
     words = host.view(np.uint32)
     words[:, o_words + word_w0(nr, 0):o_words + word_w0(nr, 0) + nr] = w0
     words[:, o_words + word_hp(nr, 0):o_words + word_hp(nr, 0) + nr] = hp.view(np.uint32)
+    if rect is not None:
+        words[:, o_words + WORD_ROOMS:o_words + WORD_ROOMS + nr] = np.asarray(rect, np.uint32)
+    if meta is not None:
+        words[:, o_words + WORD_ROOMS + nr:o_words + WORD_ROOMS + 2 * nr] = np.asarray(meta, np.uint32)
     alive, act = ((w0 >> 24) & MF_ALIVE) != 0, ((w0 >> 24) & MF_ACTIVE) != 0
     words[:, o_words + WORD_MON_CNT] = (alive.sum(1) | (alive & act).sum(1) << 8).astype(np.uint32)
     recs.copy_(torch.from_numpy(host))

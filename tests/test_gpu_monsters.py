@@ -203,6 +203,8 @@ def _constructed(n, nr, w, h):
             alive = pattern in (0, 3) or (pattern == 1 and s >= nr - 4) or (pattern == 2 and s % 2 == 1)
             w0[i, s] = mo.pack_w0(x, y, int(rng.randint(0, 12)), alive, bool(rng.randint(0, 2)))
             hp[i, s] = int(rng.choice([1, 7, 300, 32767, 32768, 40000])) if alive else 0
+        if i % 16 == 5:                                           # slot 0 on the player's own cell: alive, never shown ('@' is drawn there)
+            w0[i, 0], hp[i, 0] = mo.pack_w0(px, py, 3, True, True), 9
         dark = rng.rand(h, w) < 0.2
         grids[i][dark] = 0x01                                     # floor the player has not seen
         grids[i][rng.rand(h, w) < 0.1] |= mo.C_GOLD
@@ -234,9 +236,69 @@ def test_constructed_tables_loaded_as_records(goldens, lib):
                 assert np.array_equal(th[i], threat), ("constructed", name, cap, i)
                 over += int(len(rows) > cap)
                 ties += int(cap == 16 and len(rows) >= 16 and len(set(rows[:16, 3].tolist())) == 1)
+    own = [i for i, f in enumerate(feeds) if not f.dead and any((int(x), int(y)) == (f.px, f.py) for x, y in zip(f.mx, f.my))]
+    assert len(own) >= 4 and all(mo.rule_list(feeds[i], mo.ALL)[0][0, 3:5].tolist() == [0, 0] for i in own)      # a monster on the player's cell: listed by ALL, not shown
+    assert sum(f.py == 0 and not f.dead for f in feeds) >= 4                                                      # players in row 0: in no area
     print("rows with more qualifiers than cap:", over, "; 16-row tables of one cheb:", ties)
     assert over >= 200 and ties >= 10
     assert (dead == 1).sum() >= 4 and all(not dev_call(hip.h, mo.ALL, 16)[0][i].any() for i in np.flatnonzero(dead))
+    hip.h.close()
+
+
+# the rooms of tests/test_monsters_host.py's hand-built cases (32 x 16, 2 x 2 areas of 16 x 8), room 2 Empty with a rect of x 4..8, y 10..12
+EMPTY_RECTS = [2 | 2 << 8 | 10 << 16 | 7 << 24, 18 | 2 << 8 | 28 << 16 | 7 << 24, 4 | 10 << 8 | 9 << 16 | 13 << 24, 18 | 9 << 8 | 28 << 16 | 14 << 24]
+EMPTY_METAS = [0, 0, 2, 0]
+
+
+def _empty_room_cases(n):
+    """Per env of 32 x 16 lit floor: a player in area 2 (x 0..15, y 8..14) and four monsters.  Envs 0 and 1 are test_monsters_host.py's two hand-answered feeds
+    (the player inside the Empty room's rect, then outside it); the others put the player on a random cell of the area, one monster inside the rect, one on
+    the rect's edge row or column just outside it, one anywhere in the area and one in another area."""
+    rng = np.random.RandomState(77)
+    players, w0 = [], np.zeros((n, 4), np.uint32)
+    for i in range(n):
+        if i == 0:
+            p, mons = (5, 11), [(12, 13), (6, 11), (0, 8), (16, 11)]
+        elif i == 1:
+            p, mons = (12, 13), [(5, 11), (14, 9), (12, 7), (20, 12)]
+        else:
+            while True:
+                p = (int(rng.randint(0, 16)), int(rng.randint(8, 15)))
+                mons = [(int(rng.randint(4, 9)), int(rng.randint(10, 13))), ((3, 9)[rng.randint(2)], int(rng.randint(10, 13))) if rng.randint(2) else (int(rng.randint(4, 9)), (9, 13)[rng.randint(2)]),
+                        (int(rng.randint(0, 16)), int(rng.randint(8, 15))), (int(rng.randint(16, 32)), int(rng.randint(1, 15)))]
+                if len(set(mons + [p])) == 5:
+                    break
+        players.append(p)
+        for s, (x, y) in enumerate(mons):
+            w0[i, s] = mo.pack_w0(x, y, (i + s) % 12, True, bool((i + s) % 2))
+    return players, w0
+
+
+def test_an_empty_room_whose_rect_has_some_area_loaded_as_records(goldens, lib):
+    """Floor::in_same_room answers true for an Empty room before it looks at the rect.  Play never shows it (an Empty room's rect holds no cell), so room words
+    are loaded as records: 70 mini envs whose room 2 is Empty with a rect of 5 x 3 cells, the player and the monsters on either side of its edge inside one
+    area.  Device == host entry == numpy rule, the two hand-answered feeds of tests/test_monsters_host.py among them, and the clause decides most envs."""
+    n = 70
+    hip = HipBatch(dict(goldens["configs"]["mini"], enemies=mu.ENEMIES), [7700 + i for i in range(n)], max_steps=1000)
+    players, w0 = _empty_room_cases(n)
+    gu.inject(hip, np.full((n, 16, 32), 0x41, np.uint16), players, np.zeros(n, np.uint32), check_every=9)
+    mo.inject_monsters(hip, w0, np.full((n, 4), 9, np.int32), rect=np.tile(np.array(EMPTY_RECTS, np.uint32), (n, 1)), meta=np.tile(np.array(EMPTY_METAS, np.uint32), (n, 1)))
+    feeds = feeds_of(hip.h, (2, 2))
+    for i, f in enumerate(feeds):                               # read back by rg_debug_fetch: the injected rooms, player and monsters
+        assert f.rect.tolist() == EMPTY_RECTS and [int(m) & 3 for m in f.meta] == EMPTY_METAS and (f.px, f.py) == players[i] and len(f.mx) == 4, i
+    check_against_host(lib, hip.h, feeds, "empty room")
+    tb, th = dev_call(hip.h, mo.SHOWN, 16)
+    decided = 0
+    for i, f in enumerate(feeds):
+        rows, threat, _ = mo.rule_list(f, mo.SHOWN)
+        assert np.array_equal(tb[i], mo.capped(rows, 16)) and np.array_equal(th[i], threat), ("empty room", i, tb[i], rows)
+        f.meta = np.array([0, 0, 0, 0], np.int32)               # the same feed with room 2 read as a normal room: the rect would divide the area
+        decided += int(len(mo.rule_list(f, mo.SHOWN)[0]) != len(rows))
+        f.meta = np.array(EMPTY_METAS, np.int32)
+    shown = lambda i: sorted(mo.listed(feeds[i], [r for r in tb[i] if r[4]]))  # noqa: E731
+    assert shown(0) == [(0, 8), (6, 11), (12, 13)] and shown(1) == [(5, 11), (14, 9)]      # by hand, as in tests/test_monsters_host.py
+    print("envs in which the Empty-room clause decides a row:", decided, "of", n)
+    assert decided >= n // 2
     hip.h.close()
 
 

@@ -166,6 +166,11 @@ def shape_envs(name):
     envs.append(("snake with secrets", doors, far_d))
     envs.append(("all gold from a corner", golden, (w - 1, 0)))
     envs.append(("bare at the end", bare, (w - 1, h - 1)))
+    unseen = np.full((h, w), gu.WALLX | C_DRAWN, np.uint16)                # tests/test_objects_host.py's hand-answered grid in the top left corner: a drawn
+    unseen[1, :7] = gu.PASSAGE | C_DRAWN                                   # passage with gold on it, a door and the stairs beyond that are not on the map
+    unseen[1, 2] |= C_GOLD
+    unseen[1, 4], unseen[1, 6] = gu.DOOR, STAIR
+    envs.append(("unseen objects", unseen, (0, 1)))
     for p in (0.55, 0.75, 0.9):
         envs.append(("random %.2f" % p, gu.random_words(w, h, rng, p), None))
         envs.append(("random %.2f again" % p, gu.random_words(w, h, rng, p), None))
@@ -218,6 +223,10 @@ def test_constructed_grids(lib, name):
     assert {(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1)} <= seam_cells and all((x, y) in seam_cells for x in (31, 32, 63, 64, 95, 96) if x < w for y in (0, h - 1))
     half_known, half_all = ou.objects_call(hd, SGD | FRONTIER, KNOWN, 32)[0][env["half known"]], ou.objects_call(hd, SGD, 0, 32)[0][env["half known"]]
     assert STAIRS in half_all[:, 0] and STAIRS not in half_known[:, 0] and FRONTIER in half_known[:, 0] and (half_known[:, 0] & DOOR).any()
+    i = env["unseen objects"]                                              # by hand: on the player's map only the gold counts; without KNOWN all three do
+    t2, c2 = ou.objects_call(hd, SGD, KNOWN, 5)
+    assert c2[i].tolist() == [0, 1, 0, 0] and t2[i][0].tolist() == [GOLD, 2, 0, 2, 2, 1, 2, 0] and not t2[i][1:].any(), (name, t2[i], c2[i])
+    assert cnt[i].tolist() == [1, 1, 1, 0] and [r[[0, 3, 4]].tolist() for r in tb[i][:3]] == [[GOLD, 2, 2], [DOOR, 4, 4], [STAIRS, 6, 6]], (name, tb[i])
     i = env["snake with secrets"]                                          # only with SECRETS does the walk pass the first door
     plain, through = ou.objects_call(hd, SGD, 0, 8)[0][i], ou.objects_call(hd, SGD, SECRETS, 8)[0][i]
     assert not (plain[:, 0] & STAIRS).any() and (through[:, 0] & STAIRS).any() and through[:, 3].max() >= (w // 2) * (h // 2), (name, plain, through)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import mask_util as mu
+import policy_edge_rows as pe
 import policy_util as pu
 from parity_util import HipBatch, compare_internal, compare_mirrors, make_oracles
 from policy_util import BF16, GIVEN, GREEDY, KEYS, LISTS, SAMPLE
@@ -145,6 +146,48 @@ def test_kernel_equals_the_host_twin_mini(goldens):
     hip.sync()
     print("sources under epsilon 0.2, beta 0.3:", total.tolist())
     assert total[0] > 0 and total[1] > 0 and total[2] > 0     # the policy, the uniform draw and the teacher all chose
+
+
+def test_kernel_equals_the_host_twin_on_edge_rows_and_boundary_words(goldens):
+    """256 mini envs as they stand after reset.  policy_edge_rows.edge_batch as the logits of every dtype, mode and inverse temperature; then the committed boundary
+    words (u or v exactly on a running sum or a bound), each at ITS env index with equal logits over a list of keys that are all legal there: the kernel answers
+    what the twin answers, and at the word's env what rg_policy.h's comment says."""
+    torch_mod()
+    cfg = dict(goldens["configs"]["mini"], enemies=mu.ENEMIES)
+    n = 256
+    hip = HipBatch(cfg, [4000 + i for i in range(n)], max_steps=40, auto_reset=True)
+    hd = hip.h
+    states = states_of(hd)
+    x32 = pe.edge_batch(n, 11, seed=7)[0]
+    rng = np.random.RandomState(3)
+    given = rng.randint(0, 11, n).astype(np.int32)
+    teacher = np.frombuffer(KEYS, np.uint8)[rng.randint(0, 11, n)]
+    for dtype in (0, 1, 2):
+        logits = coded(x32, dtype)
+        for inv_temp in pe.INV_TEMPS:
+            for o in (dict(mode=SAMPLE), dict(mode=GREEDY), dict(mode=GIVEN), dict(mode=SAMPLE, epsilon=0.2, beta=0.3)):
+                kw = dict(o, inv_temp=inv_temp, seed=11, draw=dtype)
+                assert_same(device(hd, logits, dtype, None, teacher, given, **kw), twin(hd, states, logits, dtype, None, teacher, given, **kw), "edge rows dtype %d, %s" % (dtype, kw))
+    legal = hd.action_mask()
+    used = total = 0
+    for (kind, value), words in pe.BOUNDARY_WORDS.items():
+        for seed, env, draw in words:
+            total += 1
+            n_keys = pe.U_EXPECT[value][0] if kind == "u" else 4
+            if legal[env].sum() < 4:
+                continue
+            used += 1
+            keys = bytes(KEYS[k] for k in np.flatnonzero(legal[env])[:n_keys])
+            zeros = np.zeros((n, n_keys), np.float32)
+            cases = [(dict(), pe.U_EXPECT[value][1], 0)] if kind == "u" else [(dict(beta=b, epsilon=e), None, src) for b, e, src in pe.V_EXPECT[value]]
+            for o, action, src in cases:
+                t = np.full(n, keys[2], np.uint8) if o.get("beta") else None
+                got = device(hd, zeros, 0, keys, t, **dict(o, seed=seed, draw=draw))
+                assert_same(got, twin(hd, states, zeros, 0, keys, t, **dict(o, seed=seed, draw=draw)), "word %s %#x env %d draw %d %s" % (kind, value, env, draw, o))
+                assert got["source"][env] == src and (action is None or got["action"][env] == action), (kind, hex(value), env, draw, o, got["action"][env], got["source"][env])
+    print("%d of %d boundary words exercised" % (used, total))
+    assert 2 * used >= total
+    hip.sync()
 
 
 def test_kernel_equals_the_host_twin_dead_envs(goldens):

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import mask_util as mu
+import policy_edge_rows as pe
 import policy_grad_util as pg
+import policy_util as pu
 from policy_grad_util import BF16, F16, F32
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +106,51 @@ def test_kernels_equal_the_host_twins_bit_for_bit(dtype):
                 for t, h in ((dx_, x), (dm, mask), (da, a)):
                     assert (t.cpu().numpy() == np.ascontiguousarray(h).view(np.uint8).reshape(-1)).all()
     print("%d launches" % launches)
+
+
+@pytest.mark.parametrize("dtype", [F32, F16, BF16])
+def test_kernels_equal_the_host_twins_on_the_edge_rows(dtype):
+    """policy_edge_rows.edge_batch through k_pg_eval / k_pg_grad: the six logit families (|d| up to 86 and past the cut-off, 1e6, near ties, subnormal logits and
+    subnormal products w * inv), the cut-off pair, gradients that are exact binary16 ties, flat rows -- at inverse temperatures 0.01, 1, 7.3 and 100, where the
+    host tests hold the twin against float64, the kernels against the twin as bit patterns."""
+    torch = torch_mod()
+    lib = lib_mod()
+    dev = torch.device("cuda:0")
+    nk, esz = 11, 4 if dtype == F32 else 2
+    for B in (65, 200):                                      # a wave and one row; three waves and a tail
+        x32, mask, a, g_lp, g_ent = pe.edge_batch(B, nk, seed=B)
+        if dtype == F16:
+            with np.errstate(over="ignore"):
+                x = x32.astype(np.float16)
+        else:
+            x = pu.to_bf16(x32) if dtype == BF16 else x32
+        ar = Arena(torch, dev, 1 << 16)
+        dx_, dm, da, dgl, dge = ar.put(x), ar.put(mask.view(np.uint8)), ar.put(a), ar.put(g_lp), ar.put(g_ent)
+        olp, oent, odx = ar.carve(4 * B), ar.carve(4 * B), ar.carve(B * nk * esz)
+        for inv_temp in pe.INV_TEMPS:
+            olp.fill_(SENT), oent.fill_(SENT)
+            rc = lib.rg_policy_eval(None, B, nk, ptr(dx_), dtype, ptr(dm), ptr(da), inv_temp, ptr(olp), ptr(oent))
+            assert rc == 0, lib.rg_last_error(None).decode()
+            lp, ent = pg.eval_host(lib, x, dtype, mask, a, inv_temp)
+            for o, e, what in ((olp, lp, "logp"), (oent, ent, "entropy")):
+                bad = np.flatnonzero(o.cpu().numpy().view(np.uint32) != pg.bits(e))
+                assert len(bad) == 0, (what, B, inv_temp, bad[:4], [r % 12 for r in bad[:4]])
+            for gl_host, gl_dev, ge_host, ge_dev in ((g_lp, dgl, g_ent, dge), (g_lp, dgl, None, None), (None, None, g_ent, dge)):
+                odx.fill_(SENT)
+                rc = lib.rg_policy_grad(None, B, nk, ptr(dx_), dtype, ptr(dm), ptr(da), inv_temp, ptr(gl_dev), ptr(ge_dev), ptr(odx))
+                assert rc == 0, lib.rg_last_error(None).decode()
+                exp = pg.grad_host(lib, x, dtype, mask, a, gl_host, ge_host, inv_temp)
+                got = odx.cpu().numpy().view(pg.bits(exp).dtype).reshape(B, nk)
+                bad = np.argwhere(got != pg.bits(exp))
+                assert len(bad) == 0, (B, inv_temp, gl_host is None, ge_host is None, bad[:4], [r % 12 for r, _ in bad[:4]])
+            if inv_temp == 1.0 and dtype == F32:             # the rows are what they are meant to be (the twin's answers, which the host tests hold against the rule)
+                kind = np.arange(B) % 12
+                assert np.isfinite(lp[kind == 6]).all() and (lp[kind == 7] == -np.inf).all() and (ent[kind == 7] == 0).all()
+                assert (np.abs(lp[kind == 11] + np.log(mask[kind == 11].sum(1))) < 1e-6).all()
+        torch.cuda.synchronize()
+        assert ar.intact(), B
+        for t, h in ((dx_, x), (dm, mask), (da, a)):
+            assert (t.cpu().numpy() == np.ascontiguousarray(h).view(np.uint8).reshape(-1)).all()
 
 
 @pytest.mark.parametrize("bf16", [False, True])

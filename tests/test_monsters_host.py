@@ -130,12 +130,12 @@ RECTS = [2 | 2 << 8 | 10 << 16 | 7 << 24, 18 | 2 << 8 | 28 << 16 | 7 << 24, 5 | 
 METAS = [0, 0, 2, 0]
 
 
-def _feed(px, py, mons, dead=0, cells=None):
+def _feed(px, py, mons, dead=0, cells=None, rects=None):
     """mons: [(x, y)] or [(x, y, type, active, hp)]."""
     g = np.full((16, 32), LIT, np.uint16) if cells is None else cells
     m = [(q + (k % 26, k % 2, 10 + k))[:5] if len(q) == 2 else q for k, q in enumerate(mons)]
     cols = list(zip(*m)) if m else [[], [], [], [], []]
-    return mo.Feed(g, px, py, dead, cols[0], cols[1], cols[2], cols[3], cols[4], 2, 2, RECTS, METAS)
+    return mo.Feed(g, px, py, dead, cols[0], cols[1], cols[2], cols[3], cols[4], 2, 2, RECTS if rects is None else rects, METAS)
 
 
 def _both(lib, f, cap=16):
@@ -203,6 +203,35 @@ def test_inside_the_rect_against_outside(lib):
 def test_empty_room_is_one_room(lib):
     f = _feed(3, 10, [(12, 13), (5, 10), (0, 8), (15, 14), (0, 15), (16, 10)])   # area 2 = x 0..15, y 8..14
     assert _shown_cells(f, _both(lib, f)[mo.SHOWN][0]) == [(0, 8), (5, 10), (12, 13), (15, 14)]
+
+
+# The three cases below close what the mutant probe (tests/rule_mutants.py) found alive in rg_monsters.h.  They stand on this file's 32 x 16 grid of 2 x 2
+# areas, not on a 5 x 5 to 9 x 9 one: each clause is about a room's assigned area and rect, which need that much room; tests/test_gpu_monsters.py loads the
+# same feeds as state records (room words included) for k_monsters.
+def test_an_empty_room_whose_rect_has_some_area(lib):
+    """Floor::in_same_room (floor.rs:381-393) answers true for an Empty room before it looks at the rect: with the player inside a rect of some area and a monster
+    outside it (and the other way round) the same area alone decides.  (test_empty_room_is_one_room's rect holds no cell, so inside == outside there.)"""
+    rects = RECTS[:2] + [4 | 10 << 8 | 9 << 16 | 13 << 24] + RECTS[3:]          # the Empty room 2 with a rect of x 4..8, y 10..12
+    f = _feed(5, 11, [(12, 13), (6, 11), (0, 8), (16, 11), (12, 7)], rects=rects)   # the player inside it; (16, 11) and (12, 7) stand in other areas
+    assert _shown_cells(f, _both(lib, f)[mo.SHOWN][0]) == [(0, 8), (6, 11), (12, 13)]
+    f = _feed(12, 13, [(5, 11), (14, 9)], rects=rects)                              # the player outside it
+    assert _shown_cells(f, _both(lib, f)[mo.SHOWN][0]) == [(5, 11), (14, 9)]
+
+
+def test_a_monster_on_the_players_own_cell(lib):
+    """RunTime::draw_screen draws the player over whatever stands on its cell (rogue/mod.rs:398-404): a monster there is alive and not shown, and it is not the
+    nearest shown monster at distance 0."""
+    f = _feed(5, 4, [(5, 4), (6, 4)])
+    r = _both(lib, f)
+    assert _shown_cells(f, r[mo.SHOWN][0]) == [(6, 4)] and r[mo.SHOWN][1].tolist() == [1, 1, 1 << 3, 1]
+    tb, th = r[mo.ALL]
+    assert th.tolist() == [1, 1, 1 << 3, 2] and [int(v) for v in tb[0, 1:5]] == [0, 0, 0, 0] and tb[0, 0] != 0      # listed first (cheb 0), not shown
+
+
+def test_a_player_in_row_0_stands_in_no_area(lib):
+    """Room::assigned_area (rooms.rs:192-209) starts the top areas at row 1: from row 0 only the near clause is left, as from the last row."""
+    f = _feed(5, 0, [(5, 1), (6, 1), (7, 1), (5, 2)])      # d2 = 1, 2, 5, 4
+    assert _shown_cells(f, _both(lib, f)[mo.SHOWN][0]) == [(5, 1), (6, 1)]
 
 
 def test_another_area_at_d2_2(lib):

@@ -251,6 +251,20 @@ def test_an_object_that_is_known_while_the_way_is_not(lib):
     assert tb[0].tolist() == [STAIRS, 6, 0, 6, 6, 1, 6, 0]
 
 
+def test_an_object_the_player_has_not_seen(lib):
+    """Stairs and doors count by their surface WHERE the cell is on the player's map: with RG_ROUTE_KNOWN a door and the stairs that were never drawn are neither
+    listed nor counted, the gold on a drawn cell is; without it all three are."""
+    g = np.full((3, 7), WALL | DRAWN, np.uint16)
+    g[1, :] = PASSAGE | DRAWN
+    g[1, 2] |= GOLDBIT
+    g[1, 4] = DOORS                                                          # not on the map
+    g[1, 6] = STAIR                                                          # not on the map
+    tb, c = both(lib, g, 0, 1, SGD, KNOWN)
+    assert c.tolist() == [0, 1, 0, 0] and tb[0].tolist() == [GOLD, 2, 0, 2, 2, 1, 2, 0] and not tb[1:].any()
+    tb, c = both(lib, g, 0, 1, SGD, 0)
+    assert c.tolist() == [1, 1, 1, 0] and [r[[0, 3, 4]].tolist() for r in tb[:3]] == [[GOLD, 2, 2], [DOOR, 4, 4], [STAIRS, 6, 6]]
+
+
 def test_order_inside_one_walk(lib):
     g = grid(7, 7, x1y3=FLOOR | GOLDBIT, x5y3=FLOOR | GOLDBIT, x3y1=FLOOR | GOLDBIT, x3y5=STAIR, x5y5=DOORS, x1y1=FLOOR | GOLDBIT)
     tb, c = both(lib, g, 3, 3, SGD, 0, cap=8)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mask_util as mu
+import policy_edge_rows as pe
 import policy_grad_util as pg
 import policy_util as pu
 from policy_grad_util import BF16, F16, F32
@@ -193,6 +194,91 @@ def test_gradient_accuracy_against_the_float64_chain(lib):
         part = float(np.abs(pg.grad_host(lib, x, F32, mask, a, gl, ge, it).astype(np.float64) - dx64).max())
         print("g_lp %s, g_ent %s, inv_temp %g: |dlogits - float64| %.3g" % (gl is not None, ge is not None, it, part))
         assert part <= 4 * pg.MEASURED_GRAD
+
+
+def test_the_weight_cut_off_on_either_side(lib):
+    """policy_edge_rows.cutoff_pair: against a key at 0, d_in weighs 2^-125 and has a gradient that is not zero; d_out, one float32 further, weighs nothing:
+    logp -inf, gradient exactly +0.0, and as an action it does not count (the g_lp term of the whole row is +0.0)."""
+    d_in, d_out = pe.cutoff_pair()
+    x = np.array([[0.0, d_in], [0.0, d_out]], np.float32)
+    a = np.ones(2, np.int32)
+    one = np.ones(2, np.float32)
+    lp, ent = pg.eval_host(lib, x, F32, None, a)
+    assert np.isfinite(lp[0]) and abs(float(lp[0]) - float(d_in)) <= 1e-5 and lp[1] == -np.inf
+    d_lp, d_ent = pg.grad_host(lib, x, F32, None, a, one, None), pg.grad_host(lib, x, F32, None, a, None, one)
+    # inside: dlogit[1] = 1 - pi = 1 (pi = 2^-125 is lost beside 1), dlogit[0] = 0 - 1; the entropy term is -pi * (lp + H), about 86.6 * 2^-125
+    assert d_lp[0, 1] == 1.0 and d_lp[0, 0] == -1.0
+    assert d_ent[0, 1] != 0 and abs(float(d_ent[0, 1]) / (2.0 ** -125 * -float(d_in)) - 1) < 1e-5
+    # outside: every gradient of the light key is +0.0, and the action does not count
+    assert (pg.bits(d_lp[1]) == 0).all() and pg.bits(d_ent[1:2, 1])[0] == 0
+    # ... while as a bystander of action 0 the inside key still gets its -pi, the outside one +0.0
+    by = pg.grad_host(lib, x, F32, None, np.zeros(2, np.int32), one, None)
+    assert abs(float(by[0, 1]) / -(2.0 ** -125) - 1) < 1e-5 and pg.bits(by[1:2, 1])[0] == 0
+
+
+def test_binary16_gradients_on_exact_subnormal_ties(lib):
+    """policy_edge_rows.tie_values: f32 gradients exactly half way between two subnormal binary16 values, the lower neighbour even and odd, the tie at 2^-25 and the
+    one under the smallest normal, both signs -- through g_lp on two equal legal logits (pi = 1/2 exactly) -- against rne16 and against the values by hand."""
+    ties = pe.tie_values()
+    by_hand = {0.5: 0x0000, 1.5: 0x0002, 2.5: 0x0002, 3.5: 0x0004, 100.5: 0x0064, 101.5: 0x0066, 511.5: 0x0200, 512.5: 0x0200, 1022.5: 0x03FE, 1023.5: 0x0400}
+    assert sorted(by_hand) == sorted(pe.TIE_UNITS)
+    B = len(ties)
+    x = np.full((B, 3), 0.25, np.float16)
+    mask = np.tile(np.array([True, False, True]), (B, 1))            # the illegal key in between stays +0.0
+    for act, col, sign in ((0, 0, 1.0), (0, 2, -1.0), (2, 2, 1.0)):   # dlogit[a] = g_lp / 2, the other legal key's = -g_lp / 2
+        a = np.full(B, act, np.int32)
+        got = pg.bits(pg.grad_host(lib, x, F16, mask, a, 2 * ties, None))
+        full = pg.grad_host(lib, x.astype(np.float32), F32, mask, a, 2 * ties, None)
+        assert (full[:, col] == sign * ties).all() and (pg.bits(full[:, 1]) == 0).all()
+        for r in range(B):
+            want = pg.rne16(int(pg.bits(full[r:r + 1, col])[0]), F16)
+            unit = abs(float(ties[r])) * 2.0 ** 24
+            assert want & 0x7FFF == by_hand[unit] and (want >> 15) == int(sign * ties[r] < 0), (unit, hex(want))
+            assert got[r, col] == want and got[r, 1] == 0, (r, unit, hex(got[r, col]), hex(want))
+    # with an entropy term of exactly zero upstream the tie stays a tie
+    got = pg.bits(pg.grad_host(lib, x, F16, mask, np.zeros(B, np.int32), 2 * ties, np.zeros(B, np.float32)))
+    assert all(got[r, 0] & 0x7FFF == by_hand[abs(float(ties[r])) * 2.0 ** 24] for r in range(B))
+
+
+def domain_cell(lib, family, inv_temp, n=2000, nk=11):
+    """One (family, inv_temp) cell of the domain test -> (rows compared / n, worst logp ratio, worst |entropy| error, worst entropy excess over ln count, worst
+    gradient ratio).  The reference is float64 on f32(logit * inv_temp), the rule's own first step."""
+    rng = np.random.RandomState(1000 + 17 * pe.FAMILIES.index(family) + pe.INV_TEMPS.index(inv_temp))
+    x = pe.family_rows(family, rng, n, nk)
+    mask = pg.random_masks(rng, n, nk, lo=1)
+    a = np.array([rng.choice(np.flatnonzero(m)) for m in mask], np.int32)
+    g_lp, g_ent = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    it = np.float32(inv_temp)
+    xs = (x * it).astype(np.float32)
+    lp64, ent64, dxs64 = pg.chain64(xs, mask, a, g_lp, g_ent)
+    dx64 = dxs64 * float(it)                                          # d / d logit = inv_temp * d / d x
+    top = np.where(mask, xs.astype(np.float64), -np.inf).max(1)
+    keep = np.exp2((xs[np.arange(n), a].astype(np.float64) - top) * np.log2(np.e)) >= 2.0 ** -120      # below that the rule answers -inf by design
+    lp, ent = pg.eval_host(lib, x, F32, mask, a, float(it))
+    dx = pg.grad_host(lib, x, F32, mask, a, g_lp, g_ent, float(it)).astype(np.float64)
+    assert np.isfinite(ent).all() and np.isfinite(dx).all() and np.isfinite(lp[keep]).all()
+    r_lp = np.abs(lp.astype(np.float64) - lp64) / np.maximum(1.0, np.abs(lp64))
+    e_ent = np.abs(ent.astype(np.float64) - ent64)
+    excess = ent.astype(np.float64) - np.log(mask.sum(1))
+    scale = float(it) * (np.abs(g_lp) + np.abs(g_ent) * np.maximum(1.0, np.abs(lp64 + ent64)))
+    r_dx = np.abs(dx - dx64).max(1) / scale
+    return float(keep.mean()), float(r_lp[keep].max()), float(e_ent[keep].max()), float(excess[keep].max()), float(r_dx[keep].max())
+
+
+def test_accuracy_over_the_domain(lib):
+    """logp, entropy and gradient against float64 over policy_edge_rows' six families x four inverse temperatures, 1 to 11 legal keys, 2 000 rows each: rows the
+    sampled accuracy tests above never draw (|d| up to 86 and beyond the cut-off, logits at 1e6, near ties, subnormal logits and products).  Bounds relative to
+    the size of what is computed, measured here (policy_edge_rows.MEASURED_DOMAIN) times 2."""
+    worst = np.zeros(4)
+    for family in pe.FAMILIES:
+        for inv_temp in pe.INV_TEMPS:
+            share, *cell = domain_cell(lib, family, inv_temp)
+            print("%-20s inv_temp %-5g compared %5.1f %%  logp ratio %.3g  |entropy| %.3g  entropy - ln count %.3g  gradient ratio %.3g" % ((family, inv_temp, 100 * share) + tuple(cell)))
+            assert share >= 0.4 or inv_temp > 1, (family, inv_temp, share)
+            worst = np.maximum(worst, cell)
+    print("worst: logp ratio %.3g, |entropy| %.3g, entropy - ln count %.3g, gradient ratio %.3g" % tuple(worst))
+    m = pe.MEASURED_DOMAIN
+    assert worst[0] <= 2 * m["logp"] and worst[1] <= 2 * m["entropy"] and worst[2] <= 2 * m["excess"] and worst[3] <= 2 * m["grad"], (worst.tolist(), m)
 
 
 def test_refusals_name_the_argument_and_write_nothing(lib):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import mask_util as mu
+import policy_edge_rows as pe
 import policy_util as pu
 from policy_util import GIVEN, GREEDY, KEYS, STAIR, WALL, grid5
 
@@ -205,6 +206,93 @@ def test_the_random_word_and_its_bit_fields(lib, inner):
     # a stream of its own: with equal seed and draw the uniform index is not rg_sample_index's
     same = sum(((pu.fields(pu.word(5, e, 9))[2] * 11) >> 16) == lib.rg_sample_index(5, e, 9, 11) for e in range(4096))
     assert same < 2 * 4096 / 11, same
+
+
+def test_words_whose_fields_stand_on_a_boundary(lib, inner):
+    """policy_edge_rows.BOUNDARY_WORDS: random words whose u or v field is EXACTLY a running sum or a bound.  `c > t`, `v < beta` and `v < beta + epsilon` are strict,
+    and u keeps all its 24 bits -- random words never say so (a 24-bit field hits a given value once in 1.7e7 draws)."""
+    g = grid5(x2y2=STAIR)
+    for (kind, value), words in pe.BOUNDARY_WORDS.items():
+        assert len(words) >= 4
+        for seed, env, draw in words:
+            u, v, _ = pu.fields(pu.word(seed, env, draw))
+            assert pe.field_of(kind, seed, env, draw) == value and (u if kind == "u" else v) * (1 << 24) == value, (kind, value, seed, env, draw)
+            if kind == "u":
+                n, want = pe.U_EXPECT[value]
+                got = pu.act_host(lib, inner, g, 2, 2, np.zeros(n, np.float32), keys=b"hjkl"[:n], env=env, seed=seed, draw=draw)
+                assert got[1] == want and got[4] == 0, (hex(value), env, draw, got)
+                # the same boundary under a temperature and a common offset: equal logits stay equal
+                assert pu.act_host(lib, inner, g, 2, 2, np.full(n, -3.5, np.float32), keys=b"hjkl"[:n], env=env, seed=seed, draw=draw, inv_temp=0.37)[1] == want
+            else:
+                pol = pu.act_host(lib, inner, g, 2, 2, np.zeros(4, np.float32), keys=b"hjkl", env=env, seed=seed, draw=draw)
+                for beta, epsilon, src in pe.V_EXPECT[value]:
+                    got = pu.act_host(lib, inner, g, 2, 2, np.zeros(4, np.float32), keys=b"hjkl", env=env, seed=seed, draw=draw, beta=beta, epsilon=epsilon, teacher=ord("k"))
+                    assert got[4] == src and got == pol, (hex(value), beta, epsilon, got, pol)
+                # ... and one step of the bound further the word IS below it: the teacher's, the uniform draw's
+                up = float(np.nextafter(np.float32(value / float(1 << 24)), np.float32(1)))
+                assert pu.act_host(lib, inner, g, 2, 2, np.zeros(4, np.float32), keys=b"hjkl", env=env, seed=seed, draw=draw, beta=up, teacher=ord("k"))[4] == 2
+                assert pu.act_host(lib, inner, g, 2, 2, np.zeros(4, np.float32), keys=b"hjkl", env=env, seed=seed, draw=draw, epsilon=up)[4] == 1
+
+
+def test_given_mode_on_a_flat_row(lib, inner):
+    """RG_ACT_GIVEN answers source 0 whatever the row: on a row no legal key of which weighs (SAMPLE and GREEDY say source 1 there), logp = -ln count."""
+    g = grid5()                                          # all legal but '>'
+    for fill in (np.nan, -np.inf):
+        row = np.full(11, fill, np.float32)
+        row[9] = 4.0                                     # the illegal key's logit does not count
+        for k in (0, 3, 10):
+            key, a, lp, ent, src = pu.act_host(lib, inner, g, 2, 2, row, mode=GIVEN, given=k, env=k)
+            assert (key, a, src) == (KEYS[k], k, 0) and abs(lp + np.log(10)) < 1e-6 and abs(ent - np.log(10)) < 1e-6, (fill, k, lp, ent, src)
+        assert pu.act_host(lib, inner, g, 2, 2, row, mode=GIVEN, given=9)[2:5:2] == (NINF, 0)       # the illegal key: -inf, and still source 0
+        assert pu.act_host(lib, inner, g, 2, 2, row, mode=GREEDY)[4] == 1 and pu.act_host(lib, inner, g, 2, 2, row)[4] == 1
+
+
+def test_two_largest_keys_beside_one_infinitely_far_below(lib, inner):
+    """+inf is FLT_MAX and a key at -3e38 stands at d = -inf below it: it weighs 0 and adds NOTHING to the sums (0 * -inf would be NaN), so two +inf keys share the
+    row: logp -ln 2, entropy ln 2."""
+    g = grid5(x2y2=STAIR)
+    for row in (np.array([np.inf, np.inf, -3.0e38], np.float32), np.array([-3.0e38, np.finfo(np.float32).max, np.inf], np.float32)):
+        k = int(np.argmax(row))
+        _, _, lp, ent, _ = pu.act_host(lib, inner, g, 2, 2, row, keys=b"hjk", mode=GIVEN, given=k)
+        assert abs(lp + np.log(2)) < 1e-6 and abs(ent - np.log(2)) < 1e-6, (row, lp, ent)
+        assert pu.act_host(lib, inner, g, 2, 2, row, keys=b"hjk", mode=GIVEN, given=int(np.argmin(row)))[2] == NINF
+
+
+def test_the_weight_cut_off_on_either_side(lib, inner):
+    """w = 0 where d * log2 e is below -125, from the f32 product: d_in weighs 2^-125 (logp = d - ln S, finite), its neighbour d_out weighs nothing (-inf)."""
+    g = grid5(x2y2=STAIR)
+    d_in, d_out = pe.cutoff_pair()
+    for d, finite in ((d_in, True), (d_out, False)):
+        row = np.array([0.0, d], np.float32)            # m = 0: x - m is d itself
+        _, _, lp, ent, _ = pu.act_host(lib, inner, g, 2, 2, row, keys=b"hj", mode=GIVEN, given=1)
+        if finite:
+            assert np.isfinite(lp) and abs(float(lp) - float(d)) <= 1e-5, (d, lp)
+            assert 0 < ent < 1e-34                       # 2^-125 * 86.6 = 2.0e-36: the weight is in the sums
+        else:
+            assert lp == NINF and ent == 0, (d, lp, ent)
+        # the dominant key is unmoved either way, and the light key is never drawn
+        assert pu.act_host(lib, inner, g, 2, 2, row, keys=b"hj", mode=GIVEN, given=0)[2] == 0.0
+        assert all(pu.act_host(lib, inner, g, 2, 2, row, keys=b"hj", env=e)[1] == 0 for e in range(64))
+
+
+def test_the_polynomials_exhaustively(tmp_path):
+    """tests/policy_poly_main.cpp: rg_pol_exp2 over every float32 of [-125, -2^-12] and rg_pol_ln over every one of [1, 32] against float64 libm, no worse than
+    the worst case measured (written beside the bounds there); 6 s of CPU time on up to 16 threads.  No sanitizer: the program is arithmetic on registers."""
+    cxx = shutil.which("g++") or shutil.which("clang++") or ("/opt/rocm/lib/llvm/bin/clang++" if os.path.exists("/opt/rocm/lib/llvm/bin/clang++") else None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    rocm_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+    if not os.path.exists(os.path.join(rocm_inc, "hip", "hip_runtime.h")):
+        pytest.skip("no ROCm include directory (the rule headers include hip/hip_runtime.h for __host__ __device__)")
+    exe = str(tmp_path / "policy_poly_main")
+    # the rule headers that are swept: the checkout's, or the copy that tests/rule_mutants.py names when it runs this file against a mutant (RULE_MUTANT_PKG)
+    pkg = os.environ.get("RULE_MUTANT_PKG") or os.path.join(ROOT, "rogue-gym_amd")
+    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", rocm_inc, "-I", os.path.join(pkg, "csrc"), "-I", pkg,
+                    os.path.join(ROOT, "tests", "policy_poly_main.cpp"), "-o", exe], check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().endswith("policy_poly_main: 0 bad") and "83385 steps back, 0 of them more than one ulp" in r.stdout, r.stdout
 
 
 def random_case(lib, rng):
