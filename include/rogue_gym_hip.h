@@ -351,6 +351,40 @@ int rg_policy_eval_host(int64_t n_rows, int n_keys, const void *logits, int dtyp
 int rg_policy_grad_host(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp,
                         const float *g_logp, const float *g_entropy, void *dlogits);
 
+/* RETURNS AND ADVANTAGES OF A ROLLOUT: GAE(lambda), discounted reward-to-go and V-trace for a whole [n_steps, n_envs] rollout in ONE launch -- what stands between
+ * the stored reward / done / value rows and a PPO / A2C / IMPALA loss.  Stateless: no handle.  The rule is stated once, in rogue-gym_amd/csrc/rg_returns.h;
+ * kernels (k_gae, k_vtrace in librogue_gym_returns.so) and host twins agree bit for bit.
+ *   Arrays: time-major and contiguous, row t = n_envs consecutive elements, f32 except done and trunc (u8, any byte != 0 counts); last_value f32 [n_envs].
+ *     Nullable: value (rg_gae only: +0.0), last_value (+0.0), done, trunc (never), trunc_value, and one of the two outputs.
+ *   Each column is scanned from t = n_steps - 1 down to 0.  rg_gae, from adv_next = +0.0 and v_next = last_value[n]:
+ *       end = done[t] || trunc[t];   boot = trunc[t] ? (trunc_value ? trunc_value[t] : value[t]) : (done[t] ? +0.0 : v_next)
+ *       delta = fma(gamma, boot, reward[t]) - value[t];   adv[t] = fma(gamma * lam, end ? +0.0 : adv_next, delta);   ret[t] = value[t] + adv[t]
+ *     value == NULL with lam = 1 is the discounted reward-to-go (in ret and adv alike), bootstrapped from last_value.  trunc marks a time-limit end, which
+ *     bootstraps from the caller's trunc_value[t] (the value of the state that the rebuild replaced) and without it from value[t] itself, the partial-episode
+ *     approximation.  The carry across an end is selected, not multiplied by 0: a NaN or an infinity stays inside its episode.
+ *   rg_vtrace (Espeholt et al. 2018, lambda as in rlax): with ratio(bar) = min(bar, exp(logp_target[t] - logp_behaviour[t])), rho = ratio(rho_bar),
+ *     c = lam * ratio(c_bar), rho_pg = ratio(pg_rho_bar), from acc = +0.0 and v_next = vs_next = last_value[n]:
+ *       delta = rho * (fma(gamma, boot, reward[t]) - value[t]);   acc = fma(gamma * c, end ? +0.0 : acc, delta);   vs[t] = value[t] + acc
+ *       pg_adv[t] = rho_pg * (fma(gamma, end ? boot : vs_next, reward[t]) - value[t])
+ *     With logp_target == logp_behaviour and rho_bar == c_bar == 1, vs equals rg_gae's ret for the same lam bit for bit.
+ *   A NaN is the canonical quiet NaN.  Asynchronous on hip_stream (NULL = the null stream), on the caller's current device; nothing is read or written past
+ *   column n_envs - 1 or outside rows 0 .. n_steps - 1.  n_steps == 0 or n_envs == 0 is a valid no-op.  An output may be EXACTLY one of the [n_steps, n_envs]
+ *   f32 inputs (adv == reward, ret == value) or the other output (the second one then stands).
+ *   Refused, non-zero with a message (rg_last_error(NULL)) naming the argument, nothing launched, outputs untouched: n_steps or n_envs < 0; NULL reward; NULL
+ *   value, logp_behaviour or logp_target for rg_vtrace; both outputs NULL; gamma or lam outside [0, 1] or not finite; a bar not finite or <= 0; trunc_value
+ *   without trunc; an output that overlaps an input or the other output in any other way than exactly.
+ * The *_host twins: the same rule over host pointers, no stream, no device. */
+int rg_gae(void *hip_stream, int64_t n_steps, int64_t n_envs, const float *reward, const float *value, const float *last_value, const uint8_t *done, const uint8_t *trunc,
+           const float *trunc_value, float gamma, float lam, float *adv, float *ret);
+int rg_vtrace(void *hip_stream, int64_t n_steps, int64_t n_envs, const float *logp_behaviour, const float *logp_target, const float *reward, const float *value,
+              const float *last_value, const uint8_t *done, const uint8_t *trunc, const float *trunc_value, float gamma, float lam, float rho_bar, float c_bar, float pg_rho_bar,
+              float *vs, float *pg_adv);
+int rg_gae_host(int64_t n_steps, int64_t n_envs, const float *reward, const float *value, const float *last_value, const uint8_t *done, const uint8_t *trunc,
+                const float *trunc_value, float gamma, float lam, float *adv, float *ret);
+int rg_vtrace_host(int64_t n_steps, int64_t n_envs, const float *logp_behaviour, const float *logp_target, const float *reward, const float *value, const float *last_value,
+                   const uint8_t *done, const uint8_t *trunc, const float *trunc_value, float gamma, float lam, float rho_bar, float c_bar, float pg_rho_bar, float *vs,
+                   float *pg_adv);
+
 /* SHORTEST-PATH FIELDS AND TEACHER KEYS: for each env the number of moves from every cell to the nearest goal cell, that number at the player's cell, and the
  * key that takes the player one move closer, on the device.  The moves are the engine's own: rg_action_mask's move test (Floor::can_move_impl as the player).
  * The field is PRIVILEGED: it sees stairs, gold and passages the player has not discovered.  It is a teacher (imitation, DAgger), a shaping potential

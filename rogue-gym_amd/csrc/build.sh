@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds librogue_gym_hip.so, librogue_gym_novelty.so, librogue_gym_archive.so, librogue_gym_obsfix.so, librogue_gym_stepenc.so, librogue_gym_policy.so and librogue_gym_learn.so for gfx950 in-tree (cross-compiles without a GPU).  The translation units and
+# Builds librogue_gym_hip.so, librogue_gym_novelty.so, librogue_gym_archive.so, librogue_gym_obsfix.so, librogue_gym_stepenc.so, librogue_gym_policy.so, librogue_gym_learn.so and librogue_gym_returns.so for gfx950 in-tree (cross-compiles without a GPU).  The translation units and
 # their -O levels: units.sh.
 set -e
 cd "$(dirname "$0")"
@@ -50,11 +50,18 @@ for u in $LEARN_UNITS; do
     hipcc $F ${u##*:} -c $src -o $obj
     LOBJS="$LOBJS $obj"
 done
+ROBJS=
+for u in $RETURNS_UNITS; do
+    src=${u%%:*}; obj=../build/${src%.*}.o
+    hipcc $F ${u##*:} -c $src -o $obj
+    ROBJS="$ROBJS $obj"
+done
 hipcc --offload-arch=gfx950 -shared $NOBJS -o ../librogue_gym_novelty.so
 hipcc --offload-arch=gfx950 -shared $AOBJS -o ../librogue_gym_archive.so
 hipcc --offload-arch=gfx950 -shared $FOBJS -o ../librogue_gym_obsfix.so
 hipcc --offload-arch=gfx950 -shared $EOBJS -o ../librogue_gym_stepenc.so
 hipcc --offload-arch=gfx950 -shared $POBJS -o ../librogue_gym_policy.so
 hipcc --offload-arch=gfx950 -shared $LOBJS -o ../librogue_gym_learn.so
-hipcc --offload-arch=gfx950 -shared $OBJS -L.. -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_obsfix -lrogue_gym_stepenc -lrogue_gym_policy -lrogue_gym_learn '-Wl,-rpath,$ORIGIN' -o "$OUT"
+hipcc --offload-arch=gfx950 -shared $ROBJS -o ../librogue_gym_returns.so
+hipcc --offload-arch=gfx950 -shared $OBJS -L.. -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_obsfix -lrogue_gym_stepenc -lrogue_gym_policy -lrogue_gym_learn -lrogue_gym_returns '-Wl,-rpath,$ORIGIN' -o "$OUT"
 echo "built $OUT"

@@ -65,6 +65,14 @@ void rgk_pg_eval(int64_t n_rows, int n_keys, const void *logits, int dtype, cons
 void rgk_pg_grad(int64_t n_rows, int n_keys, const void *logits, int dtype, const uint8_t *mask, const int32_t *action, float inv_temp, const float *g_lp, const float *g_ent,
                  void *dlogits, hipStream_t st);
 const char *rgk_learn_build_id(void);
+// ... and rg_returns.hip (librogue_gym_returns.so): stateless.  WEAK: a build of the host units that is linked without that library (tests/rule_mutants.py's
+// fixed list) still loads, and the device entries, which test the address first, refuse with a message.
+__attribute__((weak)) void rgk_gae(int64_t n_steps, int64_t n_envs, const float *reward, const float *value, const float *last_value, const uint8_t *done, const uint8_t *trunc,
+                                   const float *trunc_value, float gamma, float gl, float *adv, float *ret, hipStream_t st);
+__attribute__((weak)) void rgk_vtrace(int64_t n_steps, int64_t n_envs, const float *logp_behaviour, const float *logp_target, const float *reward, const float *value,
+                                      const float *last_value, const uint8_t *done, const uint8_t *trunc, const float *trunc_value, float gamma, float lam, const float *bars,
+                                      float *vs, float *pg_adv, hipStream_t st);
+__attribute__((weak)) const char *rgk_returns_build_id(void);
 void rgk_path(const RgState *S, const RgConfig *c, uint32_t goals, const int32_t *gcell, uint16_t *field, int32_t *dist, uint8_t *key, hipStream_t st);
 void rgk_route(const RgState *S, const RgConfig *c, uint32_t goals, uint32_t fallback, uint32_t mode, const int32_t *gcell, int32_t *dist, uint8_t *key, uint8_t *tier,
                hipStream_t st);

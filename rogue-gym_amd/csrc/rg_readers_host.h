@@ -4,6 +4,7 @@
 // (tests/readers_host_main.cpp) runs this source under sanitizers.  Every refusal goes into `err`, the entry's name its prefix, before anything is written.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -18,6 +19,7 @@
 #include "rg_novelty.h"
 #include "rg_policy.h"  // (last: it switches floating-point contraction off for what follows)
 #include "rg_policy_grad.h"
+#include "rg_returns.h"
 
 // ---- the argument checks: `what` is the entry's name ----
 static inline int grid_check(std::string &err, const char *what, const uint16_t *cells, int height, int width) {
@@ -257,6 +259,98 @@ static inline int rgh_policy_grad(std::string &err, int64_t n_rows, int n_keys, 
                             if (dtype == RG_OBS_F32) static_cast<float *>(out)[k] = v;
                             else static_cast<uint16_t *>(out)[k] = (uint16_t)rg_pol_narrow(v, dtype);
                         });
+    }
+    return 0;
+}
+// the arguments of the returns entries (rg_returns.h), shared by rg_gae / rg_vtrace and their host twins.  vt: the V-trace entry (value and the two
+// log-probability rows required, bars = rho_bar, c_bar, pg_rho_bar; outputs vs and pg_adv); else GAE (outputs adv and ret).
+static inline int ret_args_check(std::string &err, const char *what, bool vt, int64_t n_steps, int64_t n_envs, const float *lb, const float *lt, const float *reward,
+                                 const float *value, const float *last_value, const uint8_t *done, const uint8_t *trunc, const float *trunc_value, float gamma, float lam,
+                                 const float *bars, const float *out_a, const float *out_b) {
+    const std::string w = std::string(what) + ": ";
+    const char *na = vt ? "vs" : "adv", *nb = vt ? "pg_adv" : "ret";
+    const float fmax = 3.4028234663852886e38f;
+    if (n_steps < 0) { err = w + "n_steps must not be negative, got " + std::to_string(n_steps); return 1; }
+    if (n_envs < 0) { err = w + "n_envs must not be negative, got " + std::to_string(n_envs); return 1; }
+    if (n_envs > (int64_t)0x7fffffff * 64) { err = w + "n_envs must not exceed 2^37 - 64, got " + std::to_string(n_envs); return 1; }
+    if (n_envs > 0 && n_steps > ((int64_t)1 << 60) / n_envs) { err = w + "n_steps * n_envs must not exceed 2^60, got n_steps " + std::to_string(n_steps); return 1; }
+    if (!reward) { err = w + "reward must not be NULL"; return 1; }
+    if (vt && !value) { err = w + "value must not be NULL"; return 1; }
+    if (vt && !lb) { err = w + "logp_behaviour must not be NULL"; return 1; }
+    if (vt && !lt) { err = w + "logp_target must not be NULL"; return 1; }
+    if (!out_a && !out_b) { err = w + na + " and " + nb + " are both NULL"; return 1; }
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) { err = w + "gamma must lie in [0, 1], got " + std::to_string(gamma); return 1; }
+    if (!(lam >= 0.0f && lam <= 1.0f)) { err = w + "lam must lie in [0, 1], got " + std::to_string(lam); return 1; }
+    if (vt) {
+        const char *bn[3] = {"rho_bar", "c_bar", "pg_rho_bar"};
+        for (int i = 0; i < 3; i++)
+            if (!(bars[i] > 0.0f && bars[i] <= fmax)) { err = w + bn[i] + " must be finite and > 0, got " + std::to_string(bars[i]); return 1; }
+    }
+    if (trunc_value && !trunc) { err = w + "trunc_value without trunc"; return 1; }
+    // an output may be exactly one of the [T, N] float arrays, and overlap nothing in any other way
+    const uint64_t cells = (uint64_t)n_steps * (uint64_t)n_envs;
+    struct Span { const char *name; const void *p; uint64_t bytes; };
+    const Span in[] = {{"reward", reward, cells * 4}, {"value", value, cells * 4}, {"last_value", last_value, (uint64_t)n_envs * 4}, {"done", done, cells},
+                       {"trunc", trunc, cells}, {"trunc_value", trunc_value, cells * 4}, {"logp_behaviour", vt ? lb : nullptr, cells * 4},
+                       {"logp_target", vt ? lt : nullptr, cells * 4}, {na, out_a, cells * 4}};
+    const Span out[] = {{na, out_a, cells * 4}, {nb, out_b, cells * 4}};
+    for (int o = 0; o < 2; o++)
+        for (const Span &i : in) {
+            if (!out[o].p || !i.p) continue;
+            if (o == 0 && &i == &in[8]) continue;                              // (the first output against itself)
+            if (i.p == out[o].p && i.bytes == out[o].bytes) continue;          // the exact alias
+            const uintptr_t a0 = (uintptr_t)out[o].p, b0 = (uintptr_t)i.p;
+            if (a0 < b0 + i.bytes && b0 < a0 + out[o].bytes) {
+                err = w + out[o].name + " overlaps " + i.name + " (an output may be exactly one of the [n_steps, n_envs] float arrays, nothing else)";
+                return 1;
+            }
+        }
+    return 0;
+}
+static inline float ret_gl(float gamma, float lam) { return gamma * lam; }
+// the three bars and ln_bar = (float)log((double)bar) of each, as the launcher and the twin take them
+static inline void ret_bars(float rho_bar, float c_bar, float pg_rho_bar, float out[6]) {
+    out[0] = rho_bar; out[1] = c_bar; out[2] = pg_rho_bar;
+    for (int i = 0; i < 3; i++) out[3 + i] = (float)std::log((double)out[i]);
+}
+static inline RgRetRow ret_host_row(int64_t at, const float *reward, const float *value, const uint8_t *done, const uint8_t *trunc, const float *trunc_value) {
+    const bool tv = trunc && trunc_value;
+    return {reward[at], value ? value[at] : 0.0f, tv ? trunc_value[at] : 0.0f, done && done[at] != 0, trunc && trunc[at] != 0, tv};
+}
+static inline int rgh_gae(std::string &err, int64_t n_steps, int64_t n_envs, const float *reward, const float *value, const float *last_value, const uint8_t *done,
+                          const uint8_t *trunc, const float *trunc_value, float gamma, float lam, float *adv, float *ret) {
+    if (ret_args_check(err, "rg_gae_host", false, n_steps, n_envs, nullptr, nullptr, reward, value, last_value, done, trunc, trunc_value, gamma, lam, nullptr, adv, ret)) return 1;
+    const float gl = ret_gl(gamma, lam);
+    for (int64_t n = 0; n < n_envs; n++) {
+        RgGaeState s = {0.0f, last_value ? last_value[n] : 0.0f};
+        for (int64_t t = n_steps - 1; t >= 0; t--) {
+            const int64_t at = t * n_envs + n;
+            const RgRetPair o = rg_gae_step(s, ret_host_row(at, reward, value, done, trunc, trunc_value), gamma, gl);   // (the row is read before anything is written)
+            if (adv) adv[at] = o.a;
+            if (ret) ret[at] = o.b;
+        }
+    }
+    return 0;
+}
+static inline int rgh_vtrace(std::string &err, int64_t n_steps, int64_t n_envs, const float *logp_behaviour, const float *logp_target, const float *reward, const float *value,
+                             const float *last_value, const uint8_t *done, const uint8_t *trunc, const float *trunc_value, float gamma, float lam, float rho_bar, float c_bar,
+                             float pg_rho_bar, float *vs, float *pg_adv) {
+    const float raw[3] = {rho_bar, c_bar, pg_rho_bar};
+    if (ret_args_check(err, "rg_vtrace_host", true, n_steps, n_envs, logp_behaviour, logp_target, reward, value, last_value, done, trunc, trunc_value, gamma, lam, raw, vs, pg_adv))
+        return 1;
+    float b[6];
+    ret_bars(rho_bar, c_bar, pg_rho_bar, b);
+    const RgVtBars bars = {b[0], b[1], b[2], b[3], b[4], b[5]};
+    for (int64_t n = 0; n < n_envs; n++) {
+        const float lv = last_value ? last_value[n] : 0.0f;
+        RgVtState s = {0.0f, lv, lv};
+        for (int64_t t = n_steps - 1; t >= 0; t--) {
+            const int64_t at = t * n_envs + n;
+            const float lb = logp_behaviour[at], lt = logp_target[at];
+            const RgRetPair o = rg_vtrace_step(s, ret_host_row(at, reward, value, done, trunc, trunc_value), lb, lt, gamma, lam, bars);
+            if (vs) vs[at] = o.a;
+            if (pg_adv) pg_adv[at] = o.b;
+        }
     }
     return 0;
 }

@@ -22,6 +22,9 @@ POLICY_UNITS="rg_policy.hip:-O3"
 # The learner's side of that rule likewise, librogue_gym_learn.so: k_pg_eval and k_pg_grad state rg_policy_grad.h's rule (log-probability of stored actions, entropy
 # under stored masks, their gradient), which the host twins share; librogue_gym_policy.so stays the three k_act instances (-O3, as that unit).
 LEARN_UNITS="rg_policy_grad.hip:-O3"
+# Returns and advantages of a [T, N] rollout likewise, librogue_gym_returns.so: k_gae and k_vtrace state rg_returns.h's rule (GAE, reward-to-go, V-trace), which the
+# host twins share (-O3: a register pipeline of loads around a short dependent chain).
+RETURNS_UNITS="rg_returns.hip:-O3"
 # The units of UNITS that the development library (variants/librogue_gym_hip_dev.so) compiles again with -DRG_DEV_KNOBS; it links the product's objects of all others.
 # Of the host units only the core reads the environment (tests/test_novelty_resources.py).
 KNOB_UNITS="rg_kernels.hip rg_regen_lanes.hip rg_obs.hip rg_api.cpp"

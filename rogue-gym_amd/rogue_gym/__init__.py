@@ -3,5 +3,6 @@ from .envs import (DungeonType, FirstFloorEnv, HipVecRogueEnv, HipVecStairReward
                    StatusFlag)
 from . import envs  # noqa: F401
 from .learn import masked_logp, masked_logp_np  # noqa: F401
+from .returns import discounted_returns, discounted_returns_np, gae, gae_np, vtrace, vtrace_np  # noqa: F401
 
 __version__ = "0.0.2"

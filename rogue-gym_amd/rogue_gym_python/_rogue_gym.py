@@ -148,6 +148,8 @@ _abi(True, {
     "rg_act_host": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, _P(RgActOpts), u32, i32, i32, vp, vp, vp, vp, vp],
     "rg_policy_eval": [vp, i64, i32, vp, i32, vp, vp, C.c_float, vp, vp], "rg_policy_grad": [vp, i64, i32, vp, i32, vp, vp, C.c_float, vp, vp, vp],
     "rg_policy_eval_host": [i64, i32, vp, i32, vp, vp, C.c_float, vp, vp], "rg_policy_grad_host": [i64, i32, vp, i32, vp, vp, C.c_float, vp, vp, vp],
+    "rg_gae": [vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp], "rg_gae_host": [i64, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp],
+    "rg_vtrace": [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_float] * 5 + [vp, vp], "rg_vtrace_host": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp] + [C.c_float] * 5 + [vp, vp],
     "rg_path": [vp, u32, vp, vp, vp, vp], "rg_path_host": [vp, i32, i32, i32, i32, i32, u32, i32, i32, vp, vp, vp],
     "rg_route": [vp, u32, u32, u32, vp, vp, vp, vp], "rg_route_host": [vp, i32, i32, i32, i32, i32, u32, u32, u32, i32, i32, vp, vp, vp, vp],
     "rg_episode_enable": [vp, u32, i32], "rg_episode_update": [vp], "rg_episode_cut": [vp, vp, i32, i32, vp, i32], "rg_episode_arrays": [vp, _P(RgEpisodeArrays)],

@@ -28,6 +28,6 @@ done
 for p in $PIDS; do wait $p; done   # (a failed compile ends the script: set -e)
 hipcc --offload-arch=gfx950 -shared $FOBJS -o ../variants/librogue_gym_obsfix_$name.so
 hipcc --offload-arch=gfx950 -shared $EOBJS -o ../variants/librogue_gym_stepenc_$name.so
-# (the novelty pass, the cell archive, the policy pass and its learner's side are the product's own libraries beside the variant's directory: csrc/build.sh or __graft_entry__.build() made them)
-hipcc --offload-arch=gfx950 -shared $OBJS -L.. -L../variants -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_policy -lrogue_gym_learn -lrogue_gym_obsfix_$name -lrogue_gym_stepenc_$name '-Wl,-rpath,$ORIGIN/..:$ORIGIN' -o ../variants/librogue_$name.so
+# (the novelty pass, the cell archive, the policy pass, its learner's side and the returns pass are the product's own libraries beside the variant's directory: csrc/build.sh or __graft_entry__.build() made them)
+hipcc --offload-arch=gfx950 -shared $OBJS -L.. -L../variants -lrogue_gym_novelty -lrogue_gym_archive -lrogue_gym_policy -lrogue_gym_learn -lrogue_gym_returns -lrogue_gym_obsfix_$name -lrogue_gym_stepenc_$name '-Wl,-rpath,$ORIGIN/..:$ORIGIN' -o ../variants/librogue_$name.so
 echo "built variants/librogue_$name.so"
